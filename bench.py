@@ -19,9 +19,14 @@ Workloads (synthetic 120k-point sweeps already resident in HBM when the clock st
 ``--dry-run-cpu`` replaces ONLY the device work by a host stand-in (gloo instead of RCCL): it exists so that the launch,
 barrier, max-over-ranks and gather logic is covered by CPU tests; its numbers mean nothing and the line says so.
 Every rank owns its own frames (frames shard embarrassingly; weak scaling); the only collective is the final
-gather of per-rank counts after the timed region.  Rank 0 prints ONE JSON line that also carries
+gather of per-rank counts after the timed region.  Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the
+K steps and prints the headline (``value``, ``ms_per_step``, ``dtype``); ``--full`` adds everything else the line used to carry:
   "roofline":     dominant kernel: algorithmic flops|bytes per launch / HIP-event-timed launch duration vs peak,
-  "cpu_baseline": the CPU restatement (oracle) timed on this host on a bounded sample.
+  "kernels":      one extra, fully profiled step; "parity": a spot check against the CPU restatement,
+  "cpu_baseline": the CPU restatement (oracle) timed on this host on a bounded sample,
+  "leg_*":        (N = 1) the other precisions, workloads and the host-fed / .h5 / evaluator / training-program legs.
+``--dump-outputs DIR`` writes what the timed path computed in its last step as DIR/<name>.npy (float32 / float64, at most
+64 MB in all: a fixed, seeded row sample of larger outputs), so that two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -42,6 +47,7 @@ HBM_PEAK_GBS = 8000.0            # MI355X HBM3E spec peak (MI355X_MICROARCH.md);
 MFMA_F32_PEAK_TF = 157.3         # dense float32-input MFMA peak (MI355X_MICROARCH.md)
 MFMA_BF16_PEAK_TF = 2500.0       # dense bf16 MFMA peak (MI355X_MICROARCH.md; AMD's 5 PF figure is 2:1 sparse)
 POINTS_PER_FRAME = 120_000       # BASELINE.json metric
+DUMP_LIMIT_BYTES = 64 << 20      # --dump-outputs: all files together
 
 
 def parse_args():
@@ -102,6 +108,13 @@ def parse_args():
     ap.add_argument("--dry-run-cpu", action="store_true",
                     help="CPU test switch: host stand-in for the device work, gloo for RCCL; the reported numbers are meaningless")
     ap.add_argument("--traffic-json", default=str(REPO / "profiles" / "traffic_latest.json"))
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: roofline (a second, profiled region where it needs one), the per-kernel table, the "
+                         "parity spot check, the CPU baseline and (N = 1) the extra legs; the --no-* / --leg-* / --cpu-* switches "
+                         "above only matter with it.  Off: the run does only what the headline figure needs")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64, "
+                         f"at most {DUMP_LIMIT_BYTES >> 20} MB in all; larger outputs as a fixed, seeded sample of their rows)")
     a = ap.parse_args()
     if a.workload == "fastnsf":
         a.steps = 5 if a.steps is None else a.steps
@@ -310,6 +323,45 @@ def reduce_job(elapsed: float, frames_done: int, device, world: int, rank: int):
     return float(el.item()), sum(per_rank), per_rank
 
 
+# ------------------------------------------------------------------------------------------------------
+# --dump-outputs: what the timed path computed in its last step
+# ------------------------------------------------------------------------------------------------------
+def last_step_outputs(args, result: dict, out: dict, trainer) -> dict:
+    """The arrays a caller of the timed path receives from its last step (device tensors; read after the region's final sync,
+    before anything else runs on the device)."""
+    if args.workload == "compdis":
+        return {k: out[k] for k in ("comp_dis", "refined", "eval_mask") if out.get(k) is not None}
+    if args.workload == "fastnsf":
+        return {"flow": result["flow"]}
+    if args.workload == "train":
+        return {"loss": result["loss"], "params": trainer.flat_p}
+    return {k: result[k] for k in ("flow", "comp_dis", "refined") if result.get(k) is not None}
+
+
+def dump_outputs(directory, arrays: dict, limit: int = DUMP_LIMIT_BYTES) -> dict:
+    """Writes every array as ``directory/<name>.npy``: float64 stays float64, integers become float64 (exact), everything else
+    float32.  When the files would exceed ``limit`` bytes together, every array of more than one row keeps the same fraction of its
+    rows: a sample drawn by a fixed seed (sorted, so it depends only on the row count).  Returns {name: {shape, rows_kept, dtype}}."""
+    import torch
+    host = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        dt = np.float64 if (a.dtype == np.float64 or np.issubdtype(a.dtype, np.integer)) else np.float32
+        host[name] = np.atleast_1d(a.astype(dt, copy=False))
+    total = sum(a.nbytes for a in host.values())
+    room = limit - 1024 * len(host)                      # (an .npy header is 128 bytes)
+    frac = min(1.0, room / total) if total else 1.0
+    path = Path(directory)
+    path.mkdir(parents=True, exist_ok=True)
+    manifest = {}
+    for name, a in host.items():
+        rows = a.shape[0]
+        if frac < 1.0 and rows > 1:
+            keep = np.sort(np.random.default_rng(0).choice(rows, size=max(1, int(rows * frac)), replace=False))
+            a = a[keep]
+        np.save(path / f"{name}.npy", np.ascontiguousarray(a))
+        manifest[name] = {"shape": list(host[name].shape), "rows_kept": int(a.shape[0]), "dtype": str(a.dtype)}
+    return manifest
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -492,7 +544,7 @@ def run_rank(args, rank: int, world: int, device, sync) -> dict | None:
     if not dry:
         from himo_amd import _lib
 
-    out, result, host_frames, params, pipe, batch, sets, overlapped = {}, {}, None, None, None, None, None, None
+    out, result, host_frames, params, pipe, batch, sets, overlapped, trainer = {}, {}, None, None, None, None, None, None, None
     turn = [0]
     if dry:
         step = _dry_run_step(args, rank, world)
@@ -548,9 +600,9 @@ def run_rank(args, rank: int, world: int, device, sync) -> dict | None:
         step()
     sync()
 
-    # parity spot-check on rank 0 (not timed): EPE / max abs vs the CPU oracle on one frame
+    # parity spot-check on rank 0 (not timed, --full): EPE / max abs vs the CPU oracle on one frame
     parity, ref_flow = None, None
-    if rank == 0 and not dry:
+    if rank == 0 and not dry and args.full:
         import himo_oracle as oracle
         if args.workload == "compdis":
             step()
@@ -606,7 +658,8 @@ def run_rank(args, rank: int, world: int, device, sync) -> dict | None:
         torch.set_num_threads(1)
         time.sleep(1.0)
     train_overlap = args.workload == "train" and not dry and trainer.overlap_wgrad
-    if _lib is not None and overlapped is None and not train_overlap:
+    profiled = args.full and _lib is not None
+    if profiled and overlapped is None and not train_overlap:
         _lib.prof_start(only=dominant)
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -619,8 +672,11 @@ def run_rank(args, rank: int, world: int, device, sync) -> dict | None:
     if grouped:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    dumped = None
+    if args.dump_outputs and rank == 0 and not dry:
+        dumped = dump_outputs(args.dump_outputs, last_step_outputs(args, result, out, trainer))
     single = None
-    if overlapped is not None:
+    if args.full and overlapped is not None:
         # the roofline kernel alone: the SAME K steps with one batch in flight (with two, a launch's HIP-event time includes
         # whatever the other stream co-runs, and `roofline` is a statement about that kernel)
         for _ in range(2):
@@ -634,7 +690,7 @@ def run_rank(args, rank: int, world: int, device, sync) -> dict | None:
             pipe.sync_check()
         sync()
         single = time.perf_counter() - t1
-    elif train_overlap:
+    elif args.full and train_overlap:
         # the training step's roofline kernel alone: the SAME K steps with the weight gradients back on the main stream
         trainer.set_side_streams(False)
         for _ in range(2):
@@ -649,9 +705,9 @@ def run_rank(args, rank: int, world: int, device, sync) -> dict | None:
         trainer.set_side_streams(True)
     gc.enable()
     torch.set_num_threads(n_threads)
-    prof = _lib.prof_stop() if _lib is not None else {}
+    prof = _lib.prof_stop() if profiled else {}
     all_kernels = {}
-    if _lib is not None:
+    if profiled:
         # one extra, untimed step with every kernel timed (rank 0's table).  EVERY rank runs it: the train workload's step
         # contains the gradient all-reduce, and a collective only rank 0 entered would never complete
         if rank == 0:
@@ -667,7 +723,7 @@ def run_rank(args, rank: int, world: int, device, sync) -> dict | None:
 
     traffic = {}
     try:
-        traffic = json.loads(Path(args.traffic_json).read_text())
+        traffic = json.loads(Path(args.traffic_json).read_text()) if args.full else {}
     except Exception:
         pass
     per_kernel = {n: {"avg_ms": v["avg_ms"], "launches_per_step": v["count"], "ms_per_step": v["total_ms"]}
@@ -700,7 +756,8 @@ def run_rank(args, rank: int, world: int, device, sync) -> dict | None:
     elif args.workload == "train":
         roofline, workload, dtype = train_roofline(args, prof, B * args.steps, single if single is not None else elapsed)
         # the parameter BITS this rank ends with (every rank holds the same): two runs that must agree bit for bit compare this
-        extra["param_bits_sum_at_end"] = int(trainer.flat_p.view(torch.int32).to(torch.int64).sum().item())
+        if args.full:
+            extra["param_bits_sum_at_end"] = int(trainer.flat_p.view(torch.int32).to(torch.int64).sum().item())
         extra["gradient_exchange"] = ("bucket by bucket under the backward pass (BucketedAllReduce)" if (args.train_batch > 1 and trainer.overlap_allreduce)
                                       else "one flat all-reduce after the backward pass")
         if single is not None:
@@ -717,7 +774,7 @@ def run_rank(args, rank: int, world: int, device, sync) -> dict | None:
             extra["leg_single_stream"] = {"frames_per_s": B * args.steps / single, "ms_per_step": single / args.steps * 1e3, "steps": args.steps,
                                           "note": "HiMoPipeline, one batch in flight: the round-3 headline configuration; the roofline "
                                                   "kernel's launches are timed here"}
-        if rank == 0 and _lib is not None:
+        if rank == 0 and _lib is not None and args.full:
             # what the matrix pipes of THIS box sustain on their own (register-resident chains, no memory traffic; ~0.4 s per
             # leg, outside the timed region): the clock is power-managed and the power of a matrix instruction depends on its
             # operand bits, so the nameplate `peak` is a zero-operand figure
@@ -748,16 +805,16 @@ def run_rank(args, rank: int, world: int, device, sync) -> dict | None:
         roofline["traffic_source"] = (f"{Path(args.traffic_json).name}: builder-run rocprofv3 PMC passes of this workload (scripts/collect_traffic.sh: "
                                       "FETCH_SIZE x2 per the gfx950 note + WRITE_SIZE, separate passes, per launch of the tuned kernels) -- "
                                       "a cross-reference read from profiles/, NOT measured in this run") if roofline.get("traffic") else None
-        if world == 1 and not args.no_extra_precisions:
+        if world == 1 and args.full and not args.no_extra_precisions:
             extra.update(extra_precision_legs(args, params, sets, device, ref_flow, exclude=args.precision))
-        if world == 1 and not args.no_extra_workloads:
+        if world == 1 and args.full and not args.no_extra_workloads:
             extra.update(extra_workload_legs(args, device))
-        if world == 1 and not args.no_hostfed_leg:
+        if world == 1 and args.full and not args.no_hostfed_leg:
             extra.update(hostfed_leg(args, overlapped if overlapped is not None else pipe, host_frames, device))
             extra.update(h5fed_leg(args, overlapped if overlapped is not None else pipe, host_frames, device))
-        if world == 1 and not args.no_extra_workloads and args.leg_fit_steps > 0:
+        if world == 1 and args.full and not args.no_extra_workloads and args.leg_fit_steps > 0:
             extra.update(fit_h5_leg(args, device))
-        if world == 1 and not args.no_hostfed_leg:
+        if world == 1 and args.full and not args.no_hostfed_leg:
             extra.update(eval_h5_leg(args, device))
     line = {
         "metric": "lidar_frames_per_sec_120k", "value": total_frames / elapsed, "unit": "frames/s",
@@ -768,11 +825,14 @@ def run_rank(args, rank: int, world: int, device, sync) -> dict | None:
                    "sweeps_per_frame": 3 if args.workload == "pipeline" else 1,
                    "parallelism": f"frames sharded x{world}", "refined_output": bool(args.refined),
                    "frames_per_rank": per_rank},
-        "roofline": roofline, "kernels": per_kernel,
-        "kernels_note": "one extra untimed step with every kernel timed; the timed region times only the roofline kernel",
-        "parity": parity,
     }
+    if args.full:
+        line.update({"roofline": roofline, "kernels": per_kernel,
+                     "kernels_note": "one extra untimed step with every kernel timed; the timed region times only the roofline kernel",
+                     "parity": parity})
     line.update(extra)
+    if dumped is not None:
+        line["outputs_dumped"] = {"dir": str(args.dump_outputs), "arrays": dumped}
     if args.workload == "pipeline":
         line["config"]["batches_in_flight"] = 1 if overlapped is None else len(overlapped.pipes)
         line["config"]["matrix_arithmetic"] = args.precision
@@ -790,7 +850,7 @@ def run_rank(args, rank: int, world: int, device, sync) -> dict | None:
         line["config"]["matrix_arithmetic"] = args.train_precision
         line["config"]["batchnorm"] = args.train_batchnorm
         line["config"]["samples_per_pass_and_optimiser_step"] = args.train_batch
-    if not dry and not args.no_cpu_baseline and args.workload in ("pipeline", "compdis") and world == 1:     # CPU leg: rank 0 at N = 1 only
+    if args.full and not dry and not args.no_cpu_baseline and args.workload in ("pipeline", "compdis") and world == 1:     # CPU leg: rank 0 at N = 1 only
         if args.workload == "compdis":
             frames = [frame_to_host(batch, i) for i in range(min(8, B))]
             line["cpu_baseline"] = cpu_baseline_compdis(frames, args.cpu_seconds, args.cpu_frames)

@@ -8,7 +8,10 @@ not against the reference.  Only tests/, __graft_entry__.smoke() and bench.py's 
 may import it.
 
 All functions are functional: they take the parameter dict produced by
-``himo_amd.seflow.spec.init_params`` (numpy float32 arrays) and numpy / torch inputs.
+``himo_amd.seflow.spec.init_params`` (numpy float32 arrays) and numpy / torch inputs.  The point geometry (transforms,
+pillar assignment, pillar means / centres) is float32 whatever the parameters are; each part of the network after it runs in
+the dtype of its own parameters (the pillar net in that of ``pfn.*``, its images cast to the encoder's), so the gradient tests
+can take the pillar net's sums over millions of points in float64.
 """
 from __future__ import annotations
 
@@ -83,9 +86,10 @@ def pillar_image(params, xyz: torch.Tensor, training: bool = False):
     cell = torch.stack([ix[valid].float(), iy[valid].float(), torch.zeros(len(pv))], dim=1)
     centre = cell * vs + off
     feats = torch.cat([pts, pts - mean, pts - centre], dim=1)                        # (n, 9)
-    y = feats @ _t(params["pfn.weight"])
+    w = _t(params["pfn.weight"])
+    y = feats.to(w.dtype) @ w
     y = torch.relu(_batch_norm(params, "pfn.bn", y, BN_EPS_PFN, training and len(pv) > 0))
-    acc = torch.zeros(n_cells, y.shape[1], dtype=torch.float32).index_add_(0, pv, y)
+    acc = torch.zeros(n_cells, y.shape[1], dtype=y.dtype).index_add_(0, pv, y)
     img = acc / cnt.clamp(min=1.0)[:, None]
     img = img.T.reshape(-1, GRID_H, GRID_W).contiguous()
     offsets = torch.zeros_like(xyz)
@@ -137,9 +141,9 @@ def backbone(params, imgs: torch.Tensor, training: bool = False):
 
 def head(params, img0, img1, dec, pid, offsets):
     """per-point GRU head for the valid pc0 points; pid / offsets already restricted to them."""
-    gather = lambda im: im.reshape(im.shape[0], -1)[:, pid].T                          # (n, C)
+    gather = lambda im: im.reshape(im.shape[0], -1)[:, pid].T.to(dec.dtype)           # (n, C)
     h = torch.cat([gather(img0), gather(img1), gather(dec)], dim=1)                    # (n, 128)
-    x = offsets @ _t(params["head.offset.weight"]) + _t(params["head.offset.bias"])    # (n, 64)
+    x = offsets.to(dec.dtype) @ _t(params["head.offset.weight"]) + _t(params["head.offset.bias"])    # (n, 64)
     W = lambda g: _t(params[f"head.gru.{g}.weight"])
     B = lambda g: _t(params[f"head.gru.{g}.bias"])
     for _ in range(GRU_ITERS):
@@ -191,7 +195,7 @@ def forward_train(params, pch1, pc0, pc1, pose_h1, pose0, pose1, training: bool 
     img_h, *_ = pillar_image(params, pht, training)
     img0, valid0, pid0, off0 = pillar_image(params, p0t, training)
     img1, *_ = pillar_image(params, p1, training)
-    imgs = torch.stack([img_h, img0, img1])
+    imgs = torch.stack([img_h, img0, img1]).to(_t(params["enc1.0.weight"]).dtype)
     dec = backbone(params, imgs, training)
     res = head(params, img0, img1, dec, pid0[valid0], off0[valid0])
     return res, valid0, p0t
@@ -214,7 +218,8 @@ def pillar_images_batch(params, sweeps, training: bool = False):
         mean = sums[pv] / cnt[pv, None]
         centre = torch.stack([ix[valid].float(), iy[valid].float(), torch.zeros(len(pv))], dim=1) * vs + off
         feats = torch.cat([pts, pts - mean, pts - centre], dim=1)
-        ys.append(feats @ _t(params["pfn.weight"]))
+        w = _t(params["pfn.weight"])
+        ys.append(feats.to(w.dtype) @ w)
         pre.append((valid, pid, pv, cnt, pts - centre, xyz))
     total = sum(len(y) for y in ys)
     y_all = torch.relu(_batch_norm(params, "pfn.bn", torch.cat(ys, dim=0), BN_EPS_PFN, training and total > 0))
@@ -222,7 +227,7 @@ def pillar_images_batch(params, sweeps, training: bool = False):
     for (valid, pid, pv, cnt, rel, xyz), y0 in zip(pre, ys):
         y = y_all[at:at + len(y0)]
         at += len(y0)
-        acc = torch.zeros(n_cells, y.shape[1], dtype=torch.float32).index_add_(0, pv, y)
+        acc = torch.zeros(n_cells, y.shape[1], dtype=y.dtype).index_add_(0, pv, y)
         img = (acc / cnt.clamp(min=1.0)[:, None]).T.reshape(-1, GRID_H, GRID_W).contiguous()
         offsets = torch.zeros_like(xyz)
         offsets[valid] = rel
@@ -246,7 +251,7 @@ def forward_train_batch(params, samples, training: bool = False):
         p0ts.append(p0t)
     per_slot = [pillar_images_batch(params, sw, training) for sw in slots]            # call order: history, pc0, pc1
     B, Fr = len(samples), len(slots)
-    imgs = torch.stack([per_slot[f][b][0] for b in range(B) for f in range(Fr)])      # (B * F, 32, H, W), image b * F + f
+    imgs = torch.stack([per_slot[f][b][0] for b in range(B) for f in range(Fr)]).to(_t(params["enc1.0.weight"]).dtype)   # (B * F, 32, H, W), image b * F + f
     f1, f2, f3 = encoder(params, imgs, training)
     cat = lambda t: t.reshape(B, -1, t.shape[2], t.shape[3])                          # a sample's frames stacked on channels
     s = upsample_skip(params, "dec1", cat(f3), cat(f2))

@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/nsf_gaps
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-timeout 600 rocprofv3 --kernel-trace --output-format csv -d $OUT -o t -- python $R/bench.py --workload fastnsf --no-cpu-baseline --no-extra-workloads --steps 3 --warmup 1 > $OUT/bench.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --output-format csv -d $OUT -o t -- python $R/bench.py --full --workload fastnsf --no-cpu-baseline --no-extra-workloads --steps 3 --warmup 1 > $OUT/bench.log 2>&1
 cd $R
 python - <<PY
 import csv, glob

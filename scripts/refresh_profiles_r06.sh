@@ -11,9 +11,9 @@ mkdir -p $OUT
 cd $R
 timeout 900 bash scripts/collect_traffic.sh > $OUT/traffic.log 2>&1            # PMC passes first: bench.py reads profiles/traffic_latest.json
 cp gpurun_out/pmc/traffic.json $OUT/traffic_latest.json && cp $OUT/traffic_latest.json profiles/traffic_latest.json
-timeout 1200 python bench.py > $OUT/${RN}_bench_default_n1.json 2> $OUT/default.err
-timeout 300 python bench.py --workload train --no-extra-workloads > $OUT/${RN}_bench_train_n1.json 2> $OUT/train.err
-timeout 300 python bench.py --workload train --train-batch 8 --no-extra-workloads > $OUT/${RN}_bench_train_b8_n1.json 2>> $OUT/train.err
+timeout 1200 python bench.py --full > $OUT/${RN}_bench_default_n1.json 2> $OUT/default.err
+timeout 300 python bench.py --full --workload train --no-extra-workloads > $OUT/${RN}_bench_train_n1.json 2> $OUT/train.err
+timeout 300 python bench.py --full --workload train --train-batch 8 --no-extra-workloads > $OUT/${RN}_bench_train_b8_n1.json 2>> $OUT/train.err
 timeout 300 python scripts/prof_fit_stages.py > $OUT/${RN}_fit_stages.txt 2>&1
 timeout 300 python scripts/exp_eval.py > $OUT/${RN}_evaluator_throughput.txt 2>&1
 timeout 300 python scripts/exp_eval_feed.py > $OUT/${RN}_exp_eval_feed.txt 2>&1
@@ -29,7 +29,7 @@ cd /tmp && export TMPDIR=/tmp
 HIMO_EXP_LABELS_ONLY=1 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_labels -o lab -- python $R/scripts/exp_labels.py > /dev/null 2>&1
 f=$(find $OUT/prof_labels -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $OUT/${RN}_labels_rocprofv3_kernel_stats.csv; rm -rf $OUT/prof_labels
 for wl in pipeline train train_b8 fastnsf; do
-  ARGS="--workload ${wl%_b8} --no-cpu-baseline --no-extra-precisions"
+  ARGS="--full --workload ${wl%_b8} --no-cpu-baseline --no-extra-precisions"
   [ $wl = train ] && ARGS="$ARGS --steps 5 --warmup 2 --no-extra-workloads"
   [ $wl = train_b8 ] && ARGS="$ARGS --steps 5 --warmup 2 --no-extra-workloads --train-batch 8"
   [ $wl = fastnsf ] && ARGS="$ARGS --steps 2 --warmup 1 --no-extra-workloads --single-stream"   # one fit at a time: a launch's duration is its own

@@ -7,7 +7,7 @@ OUT=$R/gpurun_out/${1:-trace_layers}
 shift || true
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-timeout 600 rocprofv3 --kernel-trace --output-format csv -d $OUT -o t -- python $R/bench.py --no-cpu-baseline --no-extra-precisions --steps 6 --warmup 1 "$@" > $OUT/bench.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --output-format csv -d $OUT -o t -- python $R/bench.py --full --no-cpu-baseline --no-extra-precisions --steps 6 --warmup 1 "$@" > $OUT/bench.log 2>&1
 cd $R
 python - <<PY
 import csv, glob, collections

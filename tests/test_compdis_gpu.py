@@ -202,7 +202,7 @@ def test_bench_nccl_branch_runs_as_a_one_rank_communicator(gpu, workload):
     env.update({"MASTER_ADDR": "127.0.0.1", "MASTER_PORT": str(port), "HSA_ENABLE_IPC_MODE_LEGACY": "0"})
     extra = ["--frames-per-step", "32", "--steps", "5"] if workload == "compdis" else ["--points", "20000", "--steps", "2"]
     r = subprocess.run([sys.executable, str(repo / "bench.py"), "--gpus", "1", "--force-process-group", "--workload", workload,
-                        "--warmup", "1", "--no-cpu-baseline"] + extra, env=env, capture_output=True, text=True, timeout=600)
+                        "--warmup", "1", "--full", "--no-cpu-baseline"] + extra, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["n_gpus"] == 1 and line["config"]["collectives"] == "nccl x1" and line["value"] > 0

@@ -95,7 +95,41 @@ def test_bench_cli_contract(monkeypatch):
         a = bench.parse_args()
         assert (a.steps, a.warmup, a.frames_per_step) == (steps, warmup, frames), argv
         assert a.points == 120_000 and a.precision == "f16x2"
+        assert a.full is False and a.dump_outputs is None          # a plain run: the headline only, nothing written
     assert a.gpus == 8
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse_args()
+    assert a.full is True and a.dump_outputs == "out"
+
+
+def test_bench_dump_outputs_writes_float_arrays_within_the_budget(tmp_path):
+    """--dump-outputs: every array as <name>.npy in float32 / float64 (integers exactly, as float64), and over the budget the same
+    seeded row sample in every run, so that two builds' files compare row for row"""
+    import sys
+    import torch
+    sys.argv = ["bench.py"]
+    import bench
+    rng = np.random.default_rng(5)
+    arrays = {"flow": torch.from_numpy(rng.normal(size=(20_000, 3)).astype(np.float32)), "cd": rng.normal(size=(20_000, 3)),
+              "mask": torch.from_numpy(rng.random(20_000) < 0.5), "ids": np.arange(20_000, dtype=np.int64) + (1 << 40),
+              "loss": torch.tensor(2.5, dtype=torch.float64)}
+    whole = bench.dump_outputs(tmp_path / "whole", arrays)
+    for name, a in arrays.items():
+        got = np.load(tmp_path / "whole" / f"{name}.npy")
+        want = np.atleast_1d(a.numpy() if isinstance(a, torch.Tensor) else a)
+        assert got.dtype in (np.float32, np.float64) and np.array_equal(got, want.astype(got.dtype)), name
+        assert whole[name]["rows_kept"] == len(want)
+    assert np.load(tmp_path / "whole" / "ids.npy").dtype == np.float64 and np.load(tmp_path / "whole" / "mask.npy").dtype == np.float32
+    limit = 300_000
+    for run in ("a", "b"):
+        m = bench.dump_outputs(tmp_path / run, arrays, limit=limit)
+        assert sum(f.stat().st_size for f in (tmp_path / run).iterdir()) <= limit
+        assert 0 < m["flow"]["rows_kept"] < 20_000 and m["flow"]["shape"] == [20_000, 3] and m["loss"]["rows_kept"] == 1
+    for name in arrays:
+        assert np.array_equal(np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")), name
+    rows = np.load(tmp_path / "a" / "ids.npy") - (1 << 40)                   # the kept rows, in order, are the same in every array
+    assert np.all(np.diff(rows) > 0)
+    assert np.array_equal(np.load(tmp_path / "a" / "flow.npy"), arrays["flow"].numpy()[rows.astype(np.int64)])
 
 
 def test_save_program_takes_the_reference_style_overrides():

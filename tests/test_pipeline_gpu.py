@@ -419,6 +419,43 @@ def test_bench_two_ranks_on_this_box(gpu, workload):
     assert line["value"] > 0 and np.isfinite(line["value"])
 
 
+def test_bench_plain_run_dumps_the_last_steps_outputs(gpu, tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`: a plain run carries the headline alone (no roofline, kernel
+    table, parity, CPU baseline or legs), and the flow / comp_dis of its last timed step land in DIR -- the same bits in a second run
+    with the same arguments (same inputs, deterministic kernels), equal to the pipeline run on that step's batch here"""
+    import json, os, subprocess, sys
+    from pathlib import Path
+    root = Path(__file__).resolve().parents[1]
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    lines = []
+    for run in ("a", "b"):
+        cmd = [sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--points", "20000",
+               "--frames-per-step", "2", "--dump-outputs", str(tmp_path / run)]
+        out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines.append(json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1]))
+    line = lines[0]
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["config"]["frames_per_rank"] == [6]
+    assert line["value"] == pytest.approx(2 / (line["ms_per_step"] * 1e-3), rel=1e-6) and line["dtype"].startswith("f16x2")
+    assert not {"roofline", "kernels", "parity", "cpu_baseline"} & set(line) and not any(k.startswith("leg_") for k in line)
+    assert sorted(line["outputs_dumped"]["arrays"]) == ["comp_dis", "flow"]
+    got = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in ("flow", "comp_dis")}
+    for k, a in got.items():
+        assert a.dtype == np.float32 and a.shape == (2 * 20_000, 3) and np.isfinite(a).all(), k
+        assert np.array_equal(a, np.load(tmp_path / "b" / f"{k}.npy")), k
+    # the last timed step is step 1 + (batches in flight - 1) + W + K of the rotation over the sample sets
+    import bench
+    from himo_amd.pipeline import HiMoPipeline
+    from himo_amd.seflow import spec
+    from himo_amd.seflow.model import SeFlowNet
+    sets, _ = bench.synthetic_sample_sets(3, 2, 20_000, gpu, seed=0)
+    last = (line["config"]["batches_in_flight"] + 1 + 3 - 1) % 3
+    pipe = HiMoPipeline(SeFlowNet(spec.init_params(0), device=gpu, max_points=20_000, precision="f16x2", max_batch=2), device=gpu)
+    res = pipe.run(sets[last], sensor_dt=0.1)
+    torch.cuda.synchronize()
+    assert np.array_equal(res["flow"].cpu().numpy(), got["flow"]) and np.array_equal(res["comp_dis"].cpu().numpy(), got["comp_dis"])
+
+
 def test_overlapped_gradient_exchange_ends_in_the_flat_exchange_bits_two_ranks(gpu):
     """the gradient all-reduce bucket by bucket UNDER the backward pass (seflow.train.BucketedAllReduce: head + decoder,
     encoder stages 3 + 2, stage 1 + pillar net; the sample count and loss ride with the first) against ONE flat all-reduce after it --
@@ -432,7 +469,7 @@ def test_overlapped_gradient_exchange_ends_in_the_flat_exchange_bits_two_ranks(g
         env = dict(os.environ, HIMO_TRAIN_OVERLAP_ALLREDUCE=overlap)
         env.pop("WORLD_SIZE", None); env.pop("RANK", None); env.pop("LOCAL_RANK", None)
         cmd = [sys.executable, str(root / "bench.py"), "--gpus", "2", "--share-gpu", "--workload", "train", "--train-batch", "2", "--steps", "4",
-               "--warmup", "2", "--points", "20000", "--no-cpu-baseline", "--no-extra-precisions"]
+               "--warmup", "2", "--points", "20000", "--full", "--no-cpu-baseline", "--no-extra-precisions"]
         out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
         assert out.returncode == 0, out.stderr[-3000:]
         line = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][0])

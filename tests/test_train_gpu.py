@@ -252,6 +252,14 @@ def test_upsample2x_backward_is_the_adjoint(gpu):
 GRAD_BAR = {"f32": 1e-4, "bf16x3": 1e-4, "mixed": 1e-4}
 
 
+def _reference_params(params):
+    """The autograd reference's parameter leaves: the pillar net's in float64, everything else float32.  Its gradients and batch
+    statistics are sums over every point of the pass (~2.9M at 8 x 3 x 120k); taken in float32 they move with the host's thread
+    count by up to 1.3e-3 of their largest element (pfn.bn.beta, 8 against 3 threads), ten times the bar, and they also set the
+    encoder's inputs.  With the pillar net in float64 the whole reference holds still to 4e-5 across thread counts."""
+    return {k: torch.from_numpy(v.astype(np.float64 if k.startswith("pfn.") else np.float32)) for k, v in params.items()}
+
+
 def _record_margins(case: str, worst: dict):
     """gpurun_out/r06_grad_margins.json: {case: {tensor: relative error}} (+ the worst tensor per case), merged across the test's cases"""
     import json
@@ -306,7 +314,7 @@ def test_full_network_gradients_match_autograd(gpu, precision, n_points, batchno
     assert any(k.endswith(".bn.gamma") for k in got) == batch
 
     torch.set_num_threads(max(1, torch.get_num_threads()))
-    P = {k: torch.from_numpy(v.copy()) for k, v in params.items()}
+    P = _reference_params(params)
     for k in P:
         if k.endswith(".weight") or k.endswith(".bias") or (batch and (k.endswith(".gamma") or k.endswith(".beta"))):
             P[k].requires_grad_(True)
@@ -381,7 +389,7 @@ def test_batched_pass_gradients_match_autograd(gpu, precision, n_points, batchno
     got = {k: v.cpu().numpy() for k, v in tr.g.items()}
     res_gpu = [r.cpu().numpy() for r in res]
     batch = batchnorm == "batch"
-    P = {k: torch.from_numpy(v.copy()) for k, v in params.items()}
+    P = _reference_params(params)
     for k in P:
         if k.endswith(".weight") or k.endswith(".bias") or (batch and (k.endswith(".gamma") or k.endswith(".beta"))):
             P[k].requires_grad_(True)
