@@ -5,17 +5,22 @@ device would idle during every read and every copy.  Here
 
 * ``SampleFeeder``: a background thread pulls frame tuples from any iterable (an h5 / npz dataset walk, a socket, a
   synthetic generator), stages the three sweeps and ``lidar_dt`` in PINNED host buffers and issues the host -> device
-  copies on its own HIP stream, ``depth`` batches ahead; the consumer gets ``Sample`` objects whose tensors are already
-  ordered after the copy on the consumer's stream (event wait, no host synchronisation);
+  copies on the process's copy stream, ``depth`` batches ahead;
+* ``BatchFeeder`` (``EvalFeeder``): the same for batch objects a ``build`` callback packs, staged on a small thread pool;
+* ``ProcessBatchFeeder``: batches read and packed by forked reader PROCESSES (``ReaderPool``), copied out of their shared slots;
 * ``TrainFeeder``: the training loop's samples -- sweep triplets read on reader threads, staged, copied and LABELLED
   (``ssl_label=seflow_auto``) one to two samples ahead of the optimiser step;
 * ``ResultDrain``: device -> pinned-host copies of the per-frame results on the compute stream, handed to a writer
   thread that waits on the copy's event and calls the sink (Feather / npz writer) off the launch thread.
 
-PyTorch supplies the streams, events and pinned allocations; no arithmetic happens here.
+The four feeders share one lifecycle (``_Prefetcher``: worker thread, bounded queue, errors raised on the consumer's thread,
+``close()``) and one way onto the device: a batch's arrays lie in ONE pinned block, which goes over as ONE copy (``_upload``), and
+the consumer gets views of the device block at the same offsets (``_view``), ordered after the copy on its own stream by an event
+(no host synchronisation).  PyTorch supplies the streams, events and pinned allocations; no arithmetic happens here.
 """
 from __future__ import annotations
 
+import collections
 import itertools
 import queue
 import threading
@@ -33,51 +38,29 @@ class _PinnedArena:
     each: a batch makes ONE, and only when it outgrows the slot's previous one)."""
 
     def __init__(self):
-        self._buf = torch.empty(0, dtype=torch.uint8)
-        self._used = 0
-        self._extra, self._extra_used = [], []        # further pinned blocks chained on by take_growing
+        self.blocks = [torch.empty(0, dtype=torch.uint8)]     # block 0 is sized by reset(); further ones are chained on by take()
+        self.used = [0]
 
     def reset(self, need_bytes: int):
-        if self._buf.numel() < need_bytes:
-            self._buf = _lib.pinned_empty(int(need_bytes * 1.25) + 4096)
-        self._used = 0
-        self._extra_used = [0] * len(self._extra)
+        if self.blocks[0].numel() < need_bytes:
+            self.blocks[0] = _lib.pinned_empty(int(need_bytes * 1.25) + 4096)
+        self.used = [0] * len(self.blocks)
 
-    def take_growing(self, shape, dtype=torch.float32) -> torch.Tensor:
-        """``take`` without a size known up front: when the block is exhausted a further pinned block is chained on (kept for
-        the following batches, so steady state allocates nothing)."""
-        nbytes = int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size()
-        lo = (self._used + 63) & ~63
-        if lo + nbytes <= self._buf.numel():
-            self._used = lo + nbytes
-            return self._buf[lo:lo + nbytes].view(dtype).view(*shape)
-        for i, blk in enumerate(self._extra):
-            lo = (self._extra_used[i] + 63) & ~63
+    def take(self, shape, dtype=torch.float32):
+        """-> (pinned tensor, index of its block, byte offset inside the block), from the first block with room.  A size known up front
+        (``reset``) always fits block 0; otherwise, when every block is exhausted, a further pinned block is chained on (kept for the
+        following batches, so steady state allocates nothing)."""
+        nbytes = int(np.prod(shape)) * dtype.itemsize
+        for i, blk in enumerate(self.blocks):
+            lo = (self.used[i] + 63) & ~63
             if lo + nbytes <= blk.numel():
-                self._extra_used[i] = lo + nbytes
-                return blk[lo:lo + nbytes].view(dtype).view(*shape)
-        blk = _lib.pinned_empty(max(int(nbytes * 1.25) + 4096, 1 << 24))
-        self._extra.append(blk)
-        self._extra_used.append(nbytes)
-        return blk[:nbytes].view(dtype).view(*shape)
-
-    def take(self, shape, dtype=torch.float32) -> torch.Tensor:
-        nbytes = int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size()
-        lo = (self._used + 63) & ~63
-        self._used = lo + nbytes
-        return self._buf[lo:lo + nbytes].view(dtype).view(*shape)
-
-    def locate(self, pin: torch.Tensor):
-        """(index of the pinned block ``pin`` was carved from, the block, byte offset inside it)"""
-        at = pin.data_ptr()
-        for i, blk in enumerate([self._buf] + self._extra):
-            lo = blk.data_ptr()
-            if blk.numel() and lo <= at < lo + blk.numel():
-                return i, blk, at - lo
-        raise ValueError("not a tensor of this arena")
-
-    def used(self, i: int) -> int:
-        return self._used if i == 0 else self._extra_used[i - 1]
+                break
+        else:
+            i, lo = len(self.blocks), 0
+            self.blocks.append(_lib.pinned_empty(max(int(nbytes * 1.25) + 4096, 1 << 24)))
+            self.used.append(0)
+        self.used[i] = lo + nbytes
+        return self.blocks[i][lo:lo + nbytes].view(dtype).view(*shape), i, lo
 
 
 # pinned staging arenas outlive the feeder that allocated them: a pinned allocation of a batch's ~100 MB costs tens of
@@ -100,28 +83,126 @@ def _return_arenas(arenas: list, events: list) -> None:
         _ARENA_POOL.extend(arenas)
 
 
-_COPY_STREAMS = {}
-_COPY_STREAMS_LOCK = threading.Lock()
-
-
 def copy_stream(device):
-    """The stream the inference / evaluation feeders issue their host -> device copies on: ONE per device and process.  Programs build a
-    feeder per call (per scene list, per bench leg); a stream per feeder would walk through torch's stream pool until one shares a
-    hardware queue with the streams the batches are computed on (``seflow.train.side_streams`` has the measurement)."""
-    key = (device.type, device.index)
-    with _COPY_STREAMS_LOCK:
-        if key not in _COPY_STREAMS:
-            _COPY_STREAMS[key] = torch.cuda.Stream(device=device)
-        return _COPY_STREAMS[key]
+    """The stream every feeder issues its host -> device copies on: ONE per device and process (``_lib.shared_streams``)."""
+    return _lib.shared_streams(device, "copy", 1)[0]
 
 
-class SampleFeeder:
+def _upload(pinned: torch.Tensor, used: int, device, stream, out: torch.Tensor | None = None) -> torch.Tensor:
+    """pinned -> HBM as ONE non-blocking copy of the first ``used`` bytes of the pinned uint8 block ``pinned`` on ``stream``, into
+    ``out`` (a device block made earlier on ``stream``) or a new one; returns the device block.  The arrays of a batch lie in one
+    pinned block and go over as one copy: sixty-four copies of 1.4-1.9 MB per 16-sample batch, or five ~1 MB copies (3 GB/s), ran far
+    below the link's rate (one 6 MB copy: 53 GB/s), and the consumer records ONE storage on its stream instead of one per tensor."""
+    with torch.cuda.stream(stream):
+        if out is None:
+            out = torch.empty(max(used, 1), dtype=torch.uint8, device=device)
+        if used:
+            out[:used].copy_(pinned[:used], non_blocking=True)
+    return out
+
+
+def _view(block: torch.Tensor, off: int, shape, dtype) -> torch.Tensor:
+    """The ``shape`` / ``dtype`` tensor at byte ``off`` of the device block ``block`` (a storage-less empty tensor when it has no bytes)."""
+    n = int(np.prod(shape)) * dtype.itemsize
+    if n == 0:
+        return torch.empty(shape, dtype=dtype, device=block.device)
+    return block[off:off + n].view(dtype).view(shape)
+
+
+def _torch_dtype(dtype) -> torch.dtype:
+    return torch.from_numpy(np.empty(0, dtype)).dtype
+
+
+class _Prefetcher:
+    """The part every feeder shares: a worker thread prepares items ``depth`` ahead of the consumer in a bounded queue.
+
+    An item is ``(payload, event, device tensors allocated off the consumer's stream)``.  Iterating makes the consumer's stream wait
+    for the event (no host wait), records each distinct storage on it ONCE (~0.1 ms of the launch thread per record) and yields the
+    payload.  A worker error is raised on the consumer's thread after the items queued before it -- where the serial loop would have
+    met it.  ``close()`` stops early: the worker returns what it holds and exits, and an iteration blocked at that moment or begun
+    afterwards ends.
+
+    A feeder sets ``device`` and calls ``_start``; its ``_produce()`` runs on the worker (the device set) and hands each item to
+    ``_offer`` until that returns False; ``_teardown()`` runs in the worker's ``finally``; ``_cancel()`` wakes a worker that waits on
+    its source when ``close()`` runs."""
+
+    _END = object()
+
+    def _start(self, depth: int, name: str) -> None:
+        self._q = queue.Queue(maxsize=depth)
+        self._error, self._stop = None, False
+        self._thread = threading.Thread(target=self._run, name=name, daemon=True)
+        self._thread.start()
+
+    def _produce(self) -> None:
+        raise NotImplementedError
+
+    def _teardown(self) -> None:
+        pass
+
+    def _cancel(self) -> None:
+        pass
+
+    def _run(self):
+        try:
+            torch.cuda.set_device(self.device)
+            self._produce()
+        except BaseException as e:                             # surfaced on the consumer's thread
+            self._error = e
+        finally:
+            try:
+                self._teardown()
+            finally:
+                self._offer(self._END)
+
+    def _offer(self, item) -> bool:
+        """queue ``item``, waiting while the queue is full; False (nothing queued) once ``close()`` has run"""
+        while not self._stop:
+            try:
+                self._q.put(item, timeout=0.1)
+                return True
+            except queue.Full:
+                pass
+        return False
+
+    def close(self) -> None:
+        """Stop early (the consumer gave up): the worker returns what it holds and exits.  Idempotent."""
+        self._stop = True
+        self._cancel()
+        try:
+            while True:
+                self._q.get_nowait()
+        except queue.Empty:
+            pass
+        self._thread.join(timeout=30)
+
+    def __iter__(self):
+        while not self._stop:
+            try:
+                got = self._q.get(timeout=0.1)                 # (woken at once by an item; the timeout only notices close())
+            except queue.Empty:
+                continue
+            if got is self._END:
+                if self._error is not None:
+                    raise self._error
+                return
+            payload, ev, tensors = got
+            cur = torch.cuda.current_stream(self.device)
+            cur.wait_event(ev)                                 # order the consumer's stream after the item's copies / kernels
+            seen = set()
+            for t in tensors:
+                key = t.untyped_storage().data_ptr()
+                if key not in seen:
+                    seen.add(key)
+                    t.record_stream(cur)
+            yield payload
+
+
+class SampleFeeder(_Prefetcher):
     """Iterate batches ``[(index, f0, Sample), ...]`` of up to ``batch`` frames, prepared ``depth`` batches ahead.
 
     ``source`` yields ``(index, fh, f0, f1)``: the history / current / next frame dicts of the reference layout (``f1``
     may be None when ``f0`` carries ``pc1`` / ``pose1``), host numpy arrays."""
-
-    _END = object()
 
     def __init__(self, source, device=None, batch: int = 8, depth: int = 2, stage_threads: int = 3):
         """``stage_threads``: threads that copy a batch's sweeps into the pinned staging buffers (plain memcpys that release
@@ -136,92 +217,51 @@ class SampleFeeder:
         self.device = device if device is not None else _lib.require_gpu()
         self.batch, self.depth = batch, depth
         self._source = iter(source)
-        self._q = queue.Queue(maxsize=depth)
         self._slots = [_PinnedArena() for _ in range(depth + 2)]      # a slot is reused only after its copies completed
         self._slot_done = [None] * (depth + 2)
         self._stream = copy_stream(self.device)
-        self._error = None
-        self._thread = threading.Thread(target=self._work, name="himo-feeder", daemon=True)
-        self._thread.start()
+        self._start(depth, "himo-feeder")
 
-    def _stage_all(self, arena, host):
-        """every array of the batch -> its place in the slot's pinned block -> the device as ONE copy of the block's used bytes (on the
-        feeder's stream, which the caller has made current); returns (device views per array, the device block they view).  Sixty-four
-        copies of 1.4-1.9 MB per 16-sample batch ran far below the link's rate and cost the consumer a ``record_stream`` per tensor."""
-        pins = [[arena.take(a.shape) for a in arrs] for arrs in host]
-        # pageable (or file mapping) -> pinned with numpy (a plain memcpy that drops the GIL): torch's copy_ spins up its
-        # intra-op thread pool on every call from a non-main thread (measured 0.96 ms vs 0.03 ms for a 1.9 MB sweep)
-        jobs = [(pin.numpy(), a) for prow, arrs in zip(pins, host) for pin, a in zip(prow, arrs)]
-        if self._copiers is not None and len(jobs) > 1:
-            list(self._copiers.map(lambda j: np.copyto(j[0], j[1]), jobs))
-        else:
-            for dst, src in jobs:
-                np.copyto(dst, src)
-        used = arena.used(0)
-        dev_blk = torch.empty(max(used, 1), dtype=torch.uint8, device=self.device)
-        if used:
-            dev_blk[:used].copy_(arena._buf[:used], non_blocking=True)                            # pinned -> HBM, once
-        base = arena._buf.data_ptr()
-
-        def view(pin):
-            n = pin.numel() * pin.element_size()
-            if n == 0:
-                return torch.empty(pin.shape, dtype=pin.dtype, device=self.device)
-            off = pin.data_ptr() - base
-            return dev_blk[off:off + n].view(pin.dtype).view(pin.shape)
-        return [[view(pin) for pin in prow] for prow in pins], dev_blk
-
-    def _work(self):
-        try:
-            torch.cuda.set_device(self.device)
-            slot = 0
-            while True:
-                items = []
-                for item in self._source:
-                    items.append(item)
-                    if len(items) >= self.batch:
-                        break
-                if not items:
-                    break
-                if self._slot_done[slot] is not None:
-                    self._slot_done[slot].synchronize()      # the copies that last used this slot's pinned buffers
-                arena = self._slots[slot]
-                host = []
-                for index, fh, f0, f1 in items:
-                    pc1 = f1["pc0"] if f1 is not None else f0["pc1"]
-                    host.append([np.ascontiguousarray(a, dtype=np.float32) for a in (fh["pc0"], f0["pc0"], pc1, f0["lidar_dt"])])
-                arena.reset(sum(a.nbytes + 64 for arrs in host for a in arrs))
-                out = []
-                with torch.cuda.stream(self._stream):
-                    staged, dev_blk = self._stage_all(arena, host)
-                    for (index, fh, f0, f1), (dh, d0, d1, dt) in zip(items, staged):
-                        s = Sample(dh, d0, d1, np.asarray(fh["pose0"], np.float64), np.asarray(f0["pose0"], np.float64),
-                                   np.asarray(f0["pose1"], np.float64), dt, f0.get("scene_id", ""), int(f0.get("timestamp", 0)))
-                        out.append((index, f0, s))
-                    ev = torch.cuda.Event()
-                    ev.record(self._stream)
-                self._slot_done[slot] = ev
-                self._q.put((out, ev, dev_blk))
-                slot = (slot + 1) % len(self._slots)
-        except BaseException as e:                             # surfaced on the consumer's thread
-            self._error = e
-        finally:
-            if self._copiers is not None:
-                self._copiers.shutdown(wait=False)
-            self._q.put(self._END)
-
-    def __iter__(self):
+    def _produce(self):
+        slot = 0
         while True:
-            got = self._q.get()
-            if got is self._END:
-                if self._error is not None:
-                    raise self._error
+            items = list(itertools.islice(self._source, self.batch))
+            if not items:
                 return
-            out, ev, dev_blk = got
-            cur = torch.cuda.current_stream(self.device)
-            cur.wait_event(ev)                                  # order the consumer's stream after the copy: no host wait
-            dev_blk.record_stream(cur)                          # (the batch's tensors view ONE block) allocated on the feeder's stream, used on this one
-            yield out
+            if self._slot_done[slot] is not None:
+                self._slot_done[slot].synchronize()          # the copies that last used this slot's pinned buffers
+            arena = self._slots[slot]
+            host = []
+            for index, fh, f0, f1 in items:
+                pc1 = f1["pc0"] if f1 is not None else f0["pc1"]
+                host.append([np.ascontiguousarray(a, dtype=np.float32) for a in (fh["pc0"], f0["pc0"], pc1, f0["lidar_dt"])])
+            arena.reset(sum(a.nbytes + 64 for arrs in host for a in arrs))
+            pins = [[arena.take(a.shape) for a in arrs] for arrs in host]
+            # pageable (or file mapping) -> pinned with numpy (a plain memcpy that drops the GIL): torch's copy_ spins up its
+            # intra-op thread pool on every call from a non-main thread (measured 0.96 ms vs 0.03 ms for a 1.9 MB sweep)
+            jobs = [(pin.numpy(), a) for prow, arrs in zip(pins, host) for (pin, _, _), a in zip(prow, arrs)]
+            if self._copiers is not None and len(jobs) > 1:
+                list(self._copiers.map(lambda j: np.copyto(j[0], j[1]), jobs))
+            else:
+                for dst, src in jobs:
+                    np.copyto(dst, src)
+            blk = _upload(arena.blocks[0], arena.used[0], self.device, self._stream)
+            out = []
+            for (index, fh, f0, f1), prow in zip(items, pins):
+                dh, d0, d1, dt = (_view(blk, off, pin.shape, pin.dtype) for pin, _, off in prow)
+                s = Sample(dh, d0, d1, np.asarray(fh["pose0"], np.float64), np.asarray(f0["pose0"], np.float64),
+                           np.asarray(f0["pose1"], np.float64), dt, f0.get("scene_id", ""), int(f0.get("timestamp", 0)))
+                out.append((index, f0, s))
+            ev = torch.cuda.Event()
+            ev.record(self._stream)
+            self._slot_done[slot] = ev
+            if not self._offer((out, ev, [blk])):
+                return
+            slot = (slot + 1) % len(self._slots)
+
+    def _teardown(self):
+        if self._copiers is not None:
+            self._copiers.shutdown(wait=False)
 
 
 class ResultDrain:
@@ -295,17 +335,15 @@ class ResultDrain:
             raise self._error
 
 
-class BatchFeeder:
+class BatchFeeder(_Prefetcher):
     """Iterate device-resident batch objects prepared ``depth`` batches ahead of the consumer.
 
     ``source`` yields items (lists of host frame dicts, ...); ``build(item, upload)`` packs one item into a batch object whose
     device tensors all come from ``upload(parts, dtype)`` and returns ``(object to yield, [its device tensors])``.  A background
     thread runs ``build``: ``upload`` concatenates (and converts) the parts STRAIGHT into pinned staging memory on a small
     thread pool (numpy releases the GIL: the arrays of a batch are staged in parallel) and issues the host -> device copies on
-    the feeder's own stream; the consumer's stream is ordered after them by an event, so it never waits for a copy it did not
+    the process's copy stream; the consumer's stream is ordered after them by an event, so it never waits for a copy it did not
     need yet."""
-
-    _END = object()
 
     def __init__(self, source, build, device=None, depth: int = 2, stage_threads: int = 4):
         """``stage_threads``: threads that copy a batch's arrays into the pinned staging memory; 0 = on the feeder thread itself, one
@@ -315,115 +353,62 @@ class BatchFeeder:
         self.device = device if device is not None else _lib.require_gpu()
         self.depth, self._build = depth, build
         self._source = iter(source)
-        self._q = queue.Queue(maxsize=depth)
         self._slots = _borrow_arenas(depth + 2)
         self._slot_done = [None] * (depth + 2)
         self._stream = copy_stream(self.device)
-        self._error = None
-        self._stop = False
         from concurrent.futures import ThreadPoolExecutor
         self._pool = ThreadPoolExecutor(max_workers=stage_threads, thread_name_prefix="himo-stage") if stage_threads > 0 else None
-        self._thread = threading.Thread(target=self._work, name="himo-batch-feeder", daemon=True)
-        self._thread.start()
+        self._start(depth, "himo-batch-feeder")
 
-    def _work(self):
-        try:
-            torch.cuda.set_device(self.device)
-            slot = 0
-            for item in self._source:
-                if self._slot_done[slot] is not None:
-                    self._slot_done[slot].synchronize()
-                arena = self._slots[slot]
-                arena.reset(0)
-                jobs = []
+    def _produce(self):
+        slot = 0
+        for item in self._source:
+            if self._slot_done[slot] is not None:
+                self._slot_done[slot].synchronize()
+            arena = self._slots[slot]
+            arena.reset(0)
+            jobs, twins = [], {}                               # (pinned block index -> its device twin)
 
-                def upload(parts, dtype):
-                    parts = [np.asarray(p) for p in parts]
-                    shape = (sum(p.shape[0] for p in parts),) + tuple(parts[0].shape[1:])
-                    tdt = torch.from_numpy(np.empty(0, dtype)).dtype
-                    pin = arena.take_growing(shape, tdt)
-                    # the device tensor is a view of a device twin of the PINNED BLOCK the staging tensor came from, at the same
-                    # offset: a batch goes over as one copy per block (a handful) instead of one per tensor -- small copies run
-                    # far below the link's rate (five ~1 MB copies: 3 GB/s; one 6 MB copy: 53 GB/s) -- and the consumer records ONE
-                    # storage per block on its stream instead of eleven tensors (0.12 ms of its launch thread each)
-                    if pin.numel() == 0:
-                        return torch.empty(shape, dtype=tdt, device=self.device)
-                    bi, blk, off = arena.locate(pin)
-                    if bi not in blocks:
-                        blocks[bi] = (blk, torch.empty(blk.numel(), dtype=torch.uint8, device=self.device))
-                    nbytes = pin.numel() * pin.element_size()
-                    dst = blocks[bi][1][off:off + nbytes].view(tdt).view(shape)
-                    # one copy job per PART (a frame's array), not per tensor: a batch's largest tensor (16 sweeps of points:
-                    # 30 MB) as one job kept one thread busy for 6 ms while the others idled
-                    # (small tensors -- masks, labels, time stamps -- stay ONE job: a future costs ~40 us of interpreter time)
-                    host, at = pin.numpy(), 0
-                    if self._pool is None:
-                        np.concatenate(parts, 0, host, casting="unsafe")
-                    elif pin.numel() * pin.element_size() < (4 << 20) or len(parts) == 1:
-                        jobs.append((self._pool.submit(np.concatenate, parts, 0, host, casting="unsafe"), None, None))
-                    else:
-                        for p in parts:
-                            n = p.shape[0]
-                            jobs.append((self._pool.submit(np.copyto, host[at:at + n], p, casting="unsafe"), None, None))
-                            at += n
-                    return dst
+            def upload(parts, dtype):
+                parts = [np.asarray(p) for p in parts]
+                shape = (sum(p.shape[0] for p in parts),) + tuple(parts[0].shape[1:])
+                pin, bi, off = arena.take(shape, _torch_dtype(dtype))
+                # the device tensor is a view of a device twin of the PINNED BLOCK the staging tensor came from, at the same offset:
+                # a batch goes over as one copy per block (a handful) instead of one per tensor (``_upload``)
+                if bi not in twins:
+                    twins[bi] = torch.empty(arena.blocks[bi].numel(), dtype=torch.uint8, device=self.device)
+                # one copy job per PART (a frame's array), not per tensor: a batch's largest tensor (16 sweeps of points:
+                # 30 MB) as one job kept one thread busy for 6 ms while the others idled
+                # (small tensors -- masks, labels, time stamps -- stay ONE job: a future costs ~40 us of interpreter time)
+                host, at = pin.numpy(), 0
+                if self._pool is None:
+                    np.concatenate(parts, 0, host, casting="unsafe")
+                elif pin.numel() * pin.element_size() < (4 << 20) or len(parts) == 1:
+                    jobs.append(self._pool.submit(np.concatenate, parts, 0, host, casting="unsafe"))
+                else:
+                    for p in parts:
+                        n = p.shape[0]
+                        jobs.append(self._pool.submit(np.copyto, host[at:at + n], p, casting="unsafe"))
+                        at += n
+                return _view(twins[bi], off, shape, pin.dtype)
 
-                with torch.cuda.stream(self._stream):
-                    blocks = {}
-                    obj, _ = self._build(item, upload)
-                    for job, _, _ in jobs:
-                        job.result()
-                    for bi, (blk, dev_blk) in blocks.items():
-                        n = arena.used(bi)
-                        dev_blk[:n].copy_(blk[:n], non_blocking=True)
-                    tensors = [dev_blk for _, dev_blk in blocks.values()]
-                    ev = torch.cuda.Event()
-                    ev.record(self._stream)
-                self._slot_done[slot] = ev
-                if not self._offer((obj, tensors, ev)):
-                    break
-                slot = (slot + 1) % len(self._slots)
-        except BaseException as e:
-            self._error = e
-        finally:
-            _return_arenas(self._slots, self._slot_done)
-            if self._pool is not None:
-                self._pool.shutdown(wait=False)
-            self._offer(self._END)
-
-    def _offer(self, item) -> bool:
-        while not self._stop:
-            try:
-                self._q.put(item, timeout=0.1)
-                return True
-            except queue.Full:
-                pass
-        return False
-
-    def close(self) -> None:
-        """Stop early (the consumer gave up): the worker returns its pinned arenas and exits."""
-        self._stop = True
-        try:
-            while True:
-                self._q.get_nowait()
-        except queue.Empty:
-            pass
-        self._thread.join(timeout=10)
-
-    def __iter__(self):
-        while True:
-            got = self._q.get()
-            if got is self._END:
-                if self._error is not None:
-                    raise self._error
+            with torch.cuda.stream(self._stream):
+                obj, _ = self._build(item, upload)
+            for job in jobs:
+                job.result()
+            for bi, twin in twins.items():
+                _upload(arena.blocks[bi], arena.used[bi], self.device, self._stream, out=twin)
+            ev = torch.cuda.Event()
+            ev.record(self._stream)
+            self._slot_done[slot] = ev
+            if not self._offer((obj, ev, list(twins.values()))):
                 return
-            obj, tensors, ev = got
-            cur = torch.cuda.current_stream(self.device)
-            cur.wait_event(ev)
-            for t in tensors:
-                if t is not None:
-                    t.record_stream(cur)
-            yield obj
+            slot = (slot + 1) % len(self._slots)
+
+    def _teardown(self):
+        _return_arenas(self._slots, self._slot_done)
+        if self._pool is not None:
+            self._pool.shutdown(wait=False)
 
 
 class _Ref:
@@ -628,15 +613,13 @@ class ReaderPool:
         self._free.append(slot)
 
 
-class ProcessBatchFeeder:
+class ProcessBatchFeeder(_Prefetcher):
     """``BatchFeeder`` whose batches are read and packed by forked reader processes (``ReaderPool``): iterate device-resident batch
     objects, ``depth`` ahead of the consumer.  ``make(k)`` reads item k (a list of frame dicts, ...) and ``build(item, upload)`` packs
     it -- both run in a worker; this process's feeder thread issues ONE host -> device copy per batch out of the worker's slot (the
     part of a slot that batches have used is registered with the HIP runtime: the copy is a DMA at the link's rate, asynchronous)
     and turns the placeholders into views of the device block.  The constructor forks the workers BEFORE it touches the device:
     construct it before anything else starts the HIP runtime (see ``ReaderPool``)."""
-
-    _END = object()
 
     def __init__(self, n_items: int, make, build, device=None, depth: int = 2, workers: int = 4, slot_bytes: int = 2 << 30):
         self._registered = {}                          # slot -> bytes of its head registered with the runtime
@@ -648,12 +631,8 @@ class ProcessBatchFeeder:
         self.pool.start()
         self.device = device if device is not None else _lib.require_gpu()
         self.depth = depth
-        self._q = queue.Queue(maxsize=depth)
         self._stream = copy_stream(self.device)
-        self._error = None
-        self._stop = False
-        self._thread = threading.Thread(target=self._work, name="himo-process-feeder", daemon=True)
-        self._thread.start()
+        self._start(depth, "himo-process-feeder")
 
     def _ensure_registered(self, s: int, used: int) -> None:
         """the first ``used`` bytes of slot s are pinned and mapped for the GPU (grown in steps: registering commits the pages)"""
@@ -676,68 +655,27 @@ class ProcessBatchFeeder:
             if self._registered.pop(s, 0):
                 rt.cudaHostUnregister(t.data_ptr())
 
-    def _work(self):
-        try:
-            torch.cuda.set_device(self.device)
-            for k, s, used, obj in self.pool:
-                self._ensure_registered(s, used)
-                with torch.cuda.stream(self._stream):
-                    dev_blk = torch.empty(max(used, 1), dtype=torch.uint8, device=self.device)
-                    if used:
-                        dev_blk[:used].copy_(self.pool.slots[s][:used], non_blocking=True)
-                    ev = torch.cuda.Event()
-                    ev.record(self._stream)
+    def _produce(self):
+        for k, s, used, obj in self.pool:
+            self._ensure_registered(s, used)
+            blk = _upload(self.pool.slots[s], used, self.device, self._stream)
+            ev = torch.cuda.Event()
+            ev.record(self._stream)
+            _swap_refs(obj, lambda ref: _view(blk, ref.off, ref.shape, _torch_dtype(ref.dtype)))
+            ev.synchronize()            # the slot goes back to a reader only after the copy out of it (a few ms; this thread idles anyway)
+            self.pool.release(s)
+            if not self._offer((obj, ev, [blk])):
+                return
 
-                def view(ref, blk=dev_blk):
-                    tdt = torch.from_numpy(np.empty(0, np.dtype(ref.dtype))).dtype
-                    n = int(np.prod(ref.shape)) * np.dtype(ref.dtype).itemsize
-                    if n == 0:
-                        return torch.empty(ref.shape, dtype=tdt, device=self.device)
-                    return blk[ref.off:ref.off + n].view(tdt).view(ref.shape)
-                _swap_refs(obj, view)
-                ev.synchronize()            # the slot goes back to a reader only after the copy out of it (a few ms; this thread idles anyway)
-                self.pool.release(s)
-                if not self._offer((obj, [dev_blk], ev)):
-                    break
-        except BaseException as e:
-            self._error = e
-        finally:
-            self.pool.close()
-            self._offer(self._END)
-
-    _offer = BatchFeeder._offer
-    __iter__ = BatchFeeder.__iter__
-
-    def close(self) -> None:
-        self._stop = True
+    def _cancel(self):
         self.pool.close()
-        try:
-            while True:
-                self._q.get_nowait()
-        except queue.Empty:
-            pass
-        self._thread.join(timeout=10)
-        if self.pool._procs and not self._thread.is_alive():      # never iterated: the workers of the constructor are still there
-            self.pool._halt()
+
+    def _teardown(self):
+        self.pool.close()
+        self.pool._halt()               # (the workers the constructor forked, when the pool was never iterated; else a no-op)
 
 
-_TRAIN_STREAMS = {}
-_TRAIN_STREAMS_LOCK = threading.Lock()
-
-
-def _train_streams(device, n_label: int, priority: int = 0):
-    """(copy stream, label streams) of the training feeders, ONE set per device and process: a run builds a feeder per epoch, and a
-    stream per feeder would walk through torch's stream pool until one of them shares a hardware queue with the training step's
-    streams (``seflow.train.side_streams`` has the measurement)."""
-    key = (device.type, device.index, priority)
-    with _TRAIN_STREAMS_LOCK:
-        copy, labels = _TRAIN_STREAMS.setdefault(key, (copy_stream(device), []))            # (the process's one copy stream)
-        while len(labels) < n_label:
-            labels.append(torch.cuda.Stream(device=device, priority=priority))
-        return copy, labels[:n_label]
-
-
-class TrainFeeder:
+class TrainFeeder(_Prefetcher):
     """Iterate training samples ``(pch1, pc0, pc1, pose_h1, pose0, pose1, label0, label1, n_labels)`` -- the tuples
     ``seflow.fit.make_sample`` builds on the spot -- prepared AHEAD of the optimiser step, the way the reference's job keeps
     its steps fed (``num_workers=16`` dataloader workers prefetching beside ``train.py``'s step, assets/slurm/ssl-train-av2.sh:31-34;
@@ -759,8 +697,6 @@ class TrainFeeder:
     run ends in the parameter bits of the run that builds every sample inside the step (tests/test_fit_gpu.py).  ``close()``
     stops early."""
 
-    _END = object()
-
     def __init__(self, dataset, trips, device=None, label_key: str = "seflow_auto", depth: int = 2, workers: int = 1,
                  label_lanes: int = 1, label_priority: int = 0, label_cache: dict | None = None, label_cache_bytes: int = 4 << 30):
         """``label_cache``: a dict the caller keeps between feeders over the SAME dataset (``fit``: one per dataset, for the whole
@@ -780,23 +716,21 @@ class TrainFeeder:
         for a in self._arenas:
             self._free.put((a, None))
         self._events = []                                      # copy events of arenas handed back (for _return_arenas)
-        self._q = queue.Queue(maxsize=depth)
-        self._copy, self._label_streams = _train_streams(self.device, label_lanes, label_priority)
+        # (the process's one copy stream, then its label streams: ONE set per device and process, a run builds a feeder per epoch)
+        self._copy = copy_stream(self.device)
+        self._label_streams = _lib.shared_streams(self.device, "label", label_lanes, label_priority)
         self._lane_ids = itertools.count()
         self._tls = threading.local()                          # per label thread: its stream and its pinned word
         self._pool = ThreadPoolExecutor(max_workers=workers, thread_name_prefix="himo-train-read")
         self._labellers = ThreadPoolExecutor(max_workers=label_lanes, thread_name_prefix="himo-train-label")
-        self._error, self._stop = None, False
         self._stat_lock = threading.Lock()
         self.stage_seconds = {"read": 0.0, "upload": 0.0, "labels": 0.0, "samples": 0}      # host time per stage (profiles/r06_fit_stages.txt)
-        self._thread = threading.Thread(target=self._work, name="himo-train-feeder", daemon=True)
-        self._thread.start()
+        self._start(depth, "himo-train-feeder")
 
     # ---- reader threads ------------------------------------------------------------------------------------------
     _F32 = ("pch1", "pc0", "pc1")
 
     def _read(self, trip):
-        import time
         from .seflow.fit import host_sample
         t0 = time.perf_counter()
         h = host_sample(self.dataset, trip, self.label_key)
@@ -807,20 +741,15 @@ class TrainFeeder:
         arena, ev = self._free.get()
         if ev is not None:
             ev.synchronize()                                   # the copies that last read this arena's pinned memory
-        arrs = {k: np.asarray(h[k]) for k in self._F32}
-        if "gm0" in h:
-            small = {"gm0": (np.asarray(h["gm0"]), torch.uint8), "gm1": (np.asarray(h["gm1"]), torch.uint8)}
-        else:
-            small = {"lab0": (np.asarray(h["lab0"]), torch.int32), "lab1": (np.asarray(h["lab1"]), torch.int32)}
-        arena.reset(sum(a.size * 4 + 64 for a in arrs.values()) + sum(a.size * 4 + 64 for a, _ in small.values()))
+        arrs = {k: (np.asarray(h[k]), torch.float32) for k in self._F32}
+        small = ("gm0", "gm1", torch.uint8) if "gm0" in h else ("lab0", "lab1", torch.int32)
+        arrs.update((k, (np.asarray(h[k]), small[2])) for k in small[:2])
+        arena.reset(sum(a.size * 4 + 64 for a, _ in arrs.values()))
         pins = {}
-        for k, a in arrs.items():
-            pins[k] = arena.take(a.shape, torch.float32)
-            np.copyto(pins[k].numpy(), a, casting="unsafe")   # file mapping (or array) -> pinned: the one host copy of a sweep
-        n_host = None
-        for k, (a, tdt) in small.items():
+        for k, (a, tdt) in arrs.items():
             pins[k] = arena.take(a.shape, tdt)
-            np.copyto(pins[k].numpy(), a, casting="unsafe")
+            np.copyto(pins[k][0].numpy(), a, casting="unsafe")  # file mapping (or array) -> pinned: the one host copy of a sweep
+        n_host = None
         if cached is not None:
             n_host = cached[2]
         elif "lab0" in h:                                      # stored labels: their count needs no device pass
@@ -830,8 +759,7 @@ class TrainFeeder:
         return arena, pins, (h["pose_h1"], h["pose0"], h["pose1"]), n_host, trip[1:]
 
     # ---- label threads -------------------------------------------------------------------------------------------
-    def _labels(self, dev, copied, poses, n_labels, key=None):
-        import time
+    def _labels(self, block, dev, copied, poses, n_labels, key=None):
         t0 = time.perf_counter()
         tls = self._tls
         if getattr(tls, "stream", None) is None:
@@ -840,26 +768,30 @@ class TrainFeeder:
             tls.word = torch.zeros(1, dtype=torch.int32).pin_memory()
         with torch.cuda.stream(tls.stream):
             tls.stream.wait_event(copied)
-            for t in dev.values():
-                t.record_stream(tls.stream)
+            block.record_stream(tls.stream)                    # (the sample's arrays are views of the one uploaded block)
             if "gm0" in dev:
                 from .seflow.ssl_label import auto_labels
                 l0, l1, top = auto_labels(dev["pc0"], dev["pc1"], dev["gm0"], dev["gm1"], poses[1], poses[2], return_top=True)
                 tls.word.copy_(top.reshape(1), non_blocking=True)
-                keep = self._cache is not None and self._cache_budget > 0
+                n = l0.numel() + l1.numel()
+                keep = False
+                if self._cache is not None:                    # reserve the host copy's bytes BEFORE making it
+                    with self._stat_lock:
+                        keep = 4 * n <= self._cache_budget
+                        if keep:
+                            self._cache_budget -= 4 * n
                 if keep:                                       # a host copy for the later epochs, behind the same wait as the count
-                    if getattr(tls, "host", None) is None or tls.host.numel() < l0.numel() + l1.numel():
-                        tls.host = _lib.pinned_empty(int((l0.numel() + l1.numel()) * 1.25) + 16, torch.int32)
+                    if getattr(tls, "host", None) is None or tls.host.numel() < n:
+                        tls.host = _lib.pinned_empty(int(n * 1.25) + 16, torch.int32)
                     tls.host[:l0.numel()].copy_(l0, non_blocking=True)
-                    tls.host[l0.numel():l0.numel() + l1.numel()].copy_(l1, non_blocking=True)
+                    tls.host[l0.numel():n].copy_(l1, non_blocking=True)
                 counted = torch.cuda.Event()
                 counted.record(tls.stream)
                 counted.synchronize()                          # this thread's wait, not the training thread's
                 n_labels = int(tls.word[0]) + 1
                 if keep:
-                    both = tls.host[:l0.numel() + l1.numel()].numpy().copy()
+                    both = tls.host[:n].numpy().copy()
                     with self._stat_lock:
-                        self._cache_budget -= both.nbytes
                         self._cache[key] = (both[:l0.numel()], both[l0.numel():], n_labels)
             else:
                 l0, l1 = dev["lab0"], dev["lab1"]
@@ -868,90 +800,37 @@ class TrainFeeder:
         with self._stat_lock:
             self.stage_seconds["labels"] += time.perf_counter() - t0
             self.stage_seconds["samples"] += 1
-        return (dev["pch1"], dev["pc0"], dev["pc1"], poses[0], poses[1], poses[2], l0, l1, n_labels), done
+        return (dev["pch1"], dev["pc0"], dev["pc1"], poses[0], poses[1], poses[2], l0, l1, n_labels), done, [block, l0, l1]
 
     # ---- feeder thread -------------------------------------------------------------------------------------------
-    def _work(self):
-        import collections
-        import time
-        try:
-            torch.cuda.set_device(self.device)
-            reads, labelled, nxt = collections.deque(), collections.deque(), 0
-            while not self._stop:
-                while nxt < len(self.trips) and len(reads) < self._window:
-                    reads.append(self._pool.submit(self._read, self.trips[nxt]))
-                    nxt += 1
-                # keep ``lanes`` + 1 samples uploaded and in (or waiting for) the label stage, then hand the oldest on
-                while reads and len(labelled) < self.lanes + 1:
-                    arena, pins, poses, n_labels, key = reads.popleft().result()
-                    t0 = time.perf_counter()
-                    with torch.cuda.stream(self._copy):
-                        # pinned -> HBM as ONE copy of the arena's used bytes (the sample's five arrays lie in one pinned block: five
-                        # ~1 MB copies ran at 3 GB/s, one 6 MB copy at the link's rate), then device views at the same offsets
-                        block = arena._buf[:arena._used].to(self.device, non_blocking=True)
-                        base = arena._buf.data_ptr()
-                        dev = {}
-                        for k, v in pins.items():
-                            lo = v.data_ptr() - base
-                            dev[k] = block[lo:lo + v.numel() * v.element_size()].view(v.dtype).view(v.shape)
-                        copied = torch.cuda.Event()
-                        copied.record(self._copy)
-                    self._free.put((arena, copied))
-                    self._events.append(copied)
-                    del self._events[:-(self._window + 2)]
-                    with self._stat_lock:
-                        self.stage_seconds["upload"] += time.perf_counter() - t0
-                    labelled.append(self._labellers.submit(self._labels, dev, copied, poses, n_labels, key))
-                    dev = None
-                if not labelled:
-                    break
-                if not self._offer(labelled.popleft().result()):
-                    break
-        except BaseException as e:                             # surfaced on the consumer's thread
-            self._error = e
-        finally:
-            self._pool.shutdown(wait=True, cancel_futures=True)
-            self._labellers.shutdown(wait=True, cancel_futures=True)
-            _return_arenas(self._arenas, self._events)
-            self._offer(self._END)
-
-    def _offer(self, item) -> bool:
+    def _produce(self):
+        reads, labelled, nxt = collections.deque(), collections.deque(), 0
         while not self._stop:
-            try:
-                self._q.put(item, timeout=0.1)
-                return True
-            except queue.Full:
-                pass
-        return False
-
-    def close(self) -> None:
-        """Stop early (the consumer gave up, or ``max_steps`` ended the run): the workers return their pinned arenas and exit."""
-        self._stop = True
-        try:
-            while True:
-                self._q.get_nowait()
-        except queue.Empty:
-            pass
-        self._thread.join(timeout=30)
-
-    def __iter__(self):
-        while True:
-            got = self._q.get()
-            if got is self._END:
-                if self._error is not None:
-                    raise self._error
+            while nxt < len(self.trips) and len(reads) < self._window:
+                reads.append(self._pool.submit(self._read, self.trips[nxt]))
+                nxt += 1
+            # keep ``lanes`` + 1 samples uploaded and in (or waiting for) the label stage, then hand the oldest on
+            while reads and len(labelled) < self.lanes + 1:
+                arena, pins, poses, n_labels, key = reads.popleft().result()
+                t0 = time.perf_counter()
+                block = _upload(arena.blocks[0], arena.used[0], self.device, self._copy)
+                dev = {k: _view(block, off, pin.shape, pin.dtype) for k, (pin, _, off) in pins.items()}
+                copied = torch.cuda.Event()
+                copied.record(self._copy)
+                self._free.put((arena, copied))
+                self._events.append(copied)
+                del self._events[:-(self._window + 2)]
+                with self._stat_lock:
+                    self.stage_seconds["upload"] += time.perf_counter() - t0
+                labelled.append(self._labellers.submit(self._labels, block, dev, copied, poses, n_labels, key))
+                block = dev = None
+            if not labelled or not self._offer(labelled.popleft().result()):
                 return
-            sample, done = got
-            cur = torch.cuda.current_stream(self.device)
-            cur.wait_event(done)                                # after the sample's copies and label kernels: no host wait
-            seen = set()
-            for t in sample:                                    # allocated on the feeder's streams, used on this one: ONE record per storage
-                if isinstance(t, torch.Tensor):                 # (the sweeps -- and uploaded labels -- are views of one block; a record costs
-                    key = t.untyped_storage().data_ptr()        #  ~0.1 ms of the launch thread)
-                    if key not in seen:
-                        seen.add(key)
-                        t.record_stream(cur)
-            yield sample
+
+    def _teardown(self):
+        self._pool.shutdown(wait=True, cancel_futures=True)
+        self._labellers.shutdown(wait=True, cancel_futures=True)
+        _return_arenas(self._arenas, self._events)
 
 
 class EvalFeeder(BatchFeeder):

@@ -289,7 +289,7 @@ def run(dataset, res_name: str = "seflowpp_best", params: dict | None = None, si
             sink(i, f0, flow)
 
     drain = ResultDrain(deliver, device=pipe.device)
-    done = 0
+    feeder, done = None, 0
     try:
         feeder = SampleFeeder(frame_source(dataset, rank, world, by_scene=by_scene), device=pipe.device, batch=max(1, batch_frames),
                               depth=max(2, len(getattr(pipe, "pipes", [0, 0]))))       # as many batches ahead as the pipeline keeps in flight
@@ -308,6 +308,8 @@ def run(dataset, res_name: str = "seflowpp_best", params: dict | None = None, si
                 drain.put((i, f0), flow)
                 done += 1
     finally:
+        if feeder is not None:
+            feeder.close()                                     # (a loop left early: the feeder thread stops reading)
         drain.close()
         if hasattr(sink, "close"):
             sink.close()

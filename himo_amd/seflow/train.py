@@ -506,8 +506,8 @@ class BucketedAllReduce:
         self.backend = dist.get_backend() if self.active else None
         self.works, self.launched = [], set()
         # ONE communication stream per device and process (an exchange object is built every step: a stream per object would walk torch's
-        # stream pool across the hardware queues, side_streams below)
-        self.stream = comm_stream(flat.device) if (flat.is_cuda and self.active) else None
+        # stream pool across the hardware queues, _lib.shared_streams)
+        self.stream = _lib.shared_streams(flat.device, "comm", 1)[0] if (flat.is_cuda and self.active) else None
 
     def _reduce(self, t: torch.Tensor):
         import torch.distributed as dist
@@ -546,30 +546,6 @@ class BucketedAllReduce:
         for w in self.works:
             w.wait()                                             # RCCL: the current stream waits; gloo: the host does
         self.works = []
-
-
-_SIDE_STREAMS = {}
-_COMM_STREAMS = {}
-
-
-def comm_stream(device):
-    """The stream the gradient exchange runs on: one per device and process (see ``side_streams``)."""
-    key = (device.type, device.index)
-    if key not in _COMM_STREAMS:
-        _COMM_STREAMS[key] = torch.cuda.Stream(device=device)
-    return _COMM_STREAMS[key]
-
-
-def side_streams(device) -> tuple:
-    """The three side streams of the training step, ONE set per device and process: every trainer of a process shares them.  The HIP
-    runtime multiplexes a process's streams onto a few hardware queues (GPU_MAX_HW_QUEUES, 8 here) and streams that share a queue
-    serialise; a process that builds trainer after trainer (bench.py's legs, a sweep over configurations) would otherwise walk
-    through torch's stream pool until a side stream lands on the queue of the stream it is meant to run beside (measured: the 8-sample
-    step 58 -> 71 ms in the default bench process, 58 ms in a fresh one)."""
-    key = (device.type, device.index)
-    if key not in _SIDE_STREAMS:
-        _SIDE_STREAMS[key] = tuple(torch.cuda.Stream(device=device) for _ in range(3))
-    return _SIDE_STREAMS[key]
 
 
 class SeFlowTrainer:
@@ -732,7 +708,7 @@ class SeFlowTrainer:
         if self.tune_tiles and precision != "f32":   # the decoder's forward runs through net._conv: the same restricted candidates
             net.autotune = True
             net._tune = lambda d: self._tune_tile(d) if (d.ksize == 3 and d.w_packed) else 0
-        self.side, self.side2, self.side3 = side_streams(dev)
+        self.side, self.side2, self.side3 = _lib.shared_streams(dev, "side", 3)           # (every trainer of the process shares them)
         self.ws_side = torch.empty(ws + 64, dtype=torch.uint8, device=dev)
         # ... and the DECODER's weight gradients on a second side stream (the encoder's ping-pong waits on the first: a backlog of
         # decoder work there would stall the chain).  Their gradient operands get a buffer per block instead of the shared scratch

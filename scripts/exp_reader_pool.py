@@ -1,6 +1,6 @@
 """Where does a batch's time go when reader PROCESSES feed the evaluator?  8 h5 scenes x 33 sweeps of 120k points; per batch of 16: read
-(h5lite, views of the mapping) and pack (into the shared slot) timed inside the worker; then the pool alone, the pool with its slots
-registered with the HIP runtime, and the whole ProcessBatchFeeder without a consumer.
+(h5lite, views of the mapping) and pack (into the shared slot) timed inside the worker; then the pool alone, before and after the HIP
+runtime started, and the whole ProcessBatchFeeder (whose slots are registered with the runtime) without a consumer.
 usage: python scripts/exp_reader_pool.py [cpu]"""
 import pickle, shutil, sys, tempfile, time, warnings
 from pathlib import Path
@@ -49,8 +49,8 @@ try:
         eb.t_read, eb.t_pack = t_read, time.perf_counter() - t0
         return eb
 
-    def run_pool(workers, on=None, off=None):
-        pool = ReaderPool(len(key_lists) * REPEAT, lambda k: make(k % len(key_lists)), build, workers=workers, slot_bytes=128 << 20, on_slots=on, off_slots=off)
+    def run_pool(workers):
+        pool = ReaderPool(len(key_lists) * REPEAT, lambda k: make(k % len(key_lists)), build, workers=workers, slot_bytes=128 << 20)
         start, halt = pool._start, pool._halt
 
         def timed(fn, what):
@@ -80,11 +80,6 @@ try:
         for workers in (1, 4, 8):
             rate, r, p, used = run_pool(workers)
             print(f"pool alone after the HIP runtime started, {workers} reader processes: {rate:7.0f} sweeps/s; read {r:.1f} ms, pack {p:.1f} ms")
-        fd = ProcessBatchFeeder.__new__(ProcessBatchFeeder)
-        fd._slot_done = {}
-        for workers in (1, 4, 8):
-            rate, r, p, used = run_pool(workers, on=ProcessBatchFeeder._register, off=fd._unregister)
-            print(f"pool with registered slots, {workers} reader processes: {rate:7.0f} sweeps/s; read {r:.1f} ms, pack {p:.1f} ms")
         for workers in (1, 4, 8):
             feeder = ProcessBatchFeeder(len(key_lists) * REPEAT, lambda k: make(k % len(key_lists)), build, device=dev, workers=workers)
             t0 = time.perf_counter()
