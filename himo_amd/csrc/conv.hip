@@ -19,7 +19,7 @@
 //   * epilogues are fused: bias, BatchNorm(eval) scale/shift, exact-erf GELU, the GRU gate math.
 // Channel concatenation never copies: every tensor is addressed as base + n*batch_stride +
 // pixel*pitch + channel, so frames live as channel groups of one wider buffer.
-#include "conv_common.h"
+#include "conv_plan.h"
 
 namespace himo {
 
@@ -418,106 +418,52 @@ __global__ __launch_bounds__(256) void upsample2x_split_lds_kernel(UpArgs a) {
 }
 
 template <int KS, int S, int BN, int MI>
-static void launch_epi(const ConvArgs& a_in, int epi, dim3 grid, hipStream_t s) {
-    ConvArgs a = a_in;
-    // row GEMMs: 16-byte epilogue stores when the output (and, for the ReLU-mask epilogue, the mask source) admits them
-    if (KS == 1 && vec_store_ok(a) && !(a.Cout & 31) &&
-        (epi != kEpiReluMask || (!(reinterpret_cast<uintptr_t>(a.aux_in) & 15u) && !(a.aux_in_pitch & 3))))
-        a.act_flags |= kActVecStore;
-    switch (epi) {
-        case kEpiBias: hipLaunchKernelGGL((conv_mfma_kernel<KS, S, BN, kEpiBias, MI>), grid, dim3(256), 0, s, a); break;
-        case kEpiBiasBnGelu: hipLaunchKernelGGL((conv_mfma_kernel<KS, S, BN, kEpiBiasBnGelu, MI>), grid, dim3(256), 0, s, a); break;
-        case kEpiBiasGelu: hipLaunchKernelGGL((conv_mfma_kernel<KS, S, BN, kEpiBiasGelu, MI>), grid, dim3(256), 0, s, a); break;
-        case kEpiGruZR: hipLaunchKernelGGL((conv_mfma_kernel<KS, S, BN, kEpiGruZR, MI>), grid, dim3(256), 0, s, a); break;
-        case kEpiBiasRelu: hipLaunchKernelGGL((conv_mfma_kernel<KS, S, BN, kEpiBiasRelu, MI>), grid, dim3(256), 0, s, a); break;
-        case kEpiReluMask: hipLaunchKernelGGL((conv_mfma_kernel<KS, S, BN, kEpiReluMask, MI>), grid, dim3(256), 0, s, a); break;
-        default: hipLaunchKernelGGL((conv_mfma_kernel<KS, S, BN, kEpiGruQ, MI>), grid, dim3(256), 0, s, a); break;
+static void launch_epi(const ConvPlan& p, hipStream_t s) {
+    switch (p.epi) {
+        case kEpiBias: hipLaunchKernelGGL((conv_mfma_kernel<KS, S, BN, kEpiBias, MI>), p.grid, dim3(256), 0, s, p.args); break;
+        case kEpiBiasBnGelu: hipLaunchKernelGGL((conv_mfma_kernel<KS, S, BN, kEpiBiasBnGelu, MI>), p.grid, dim3(256), 0, s, p.args); break;
+        case kEpiBiasGelu: hipLaunchKernelGGL((conv_mfma_kernel<KS, S, BN, kEpiBiasGelu, MI>), p.grid, dim3(256), 0, s, p.args); break;
+        case kEpiGruZR: hipLaunchKernelGGL((conv_mfma_kernel<KS, S, BN, kEpiGruZR, MI>), p.grid, dim3(256), 0, s, p.args); break;
+        case kEpiBiasRelu: hipLaunchKernelGGL((conv_mfma_kernel<KS, S, BN, kEpiBiasRelu, MI>), p.grid, dim3(256), 0, s, p.args); break;
+        case kEpiReluMask: hipLaunchKernelGGL((conv_mfma_kernel<KS, S, BN, kEpiReluMask, MI>), p.grid, dim3(256), 0, s, p.args); break;
+        default: hipLaunchKernelGGL((conv_mfma_kernel<KS, S, BN, kEpiGruQ, MI>), p.grid, dim3(256), 0, s, p.args); break;
     }
 }
 
 template <int KS, int S>
-static void launch_tile(const ConvArgs& a, int epi, int bn, int mi, dim3 grid, hipStream_t s) {
-    if (bn == 128) { if (mi == 2) launch_epi<KS, S, 128, 2>(a, epi, grid, s); else launch_epi<KS, S, 128, 1>(a, epi, grid, s); }
-    else { if (mi == 2) launch_epi<KS, S, 64, 2>(a, epi, grid, s); else launch_epi<KS, S, 64, 1>(a, epi, grid, s); }
+static void launch_tile(const ConvPlan& p, hipStream_t s) {
+    if (p.bn == 128) { if (p.mi == 2) launch_epi<KS, S, 128, 2>(p, s); else launch_epi<KS, S, 128, 1>(p, s); }
+    else { if (p.mi == 2) launch_epi<KS, S, 64, 2>(p, s); else launch_epi<KS, S, 64, 1>(p, s); }
+}
+
+void launch_conv_f32(const ConvPlan& p, hipStream_t s) {
+    if (p.ks == 1) launch_tile<1, 1>(p, s);
+    else if (p.stride == 1) launch_tile<3, 1>(p, s);
+    else launch_tile<3, 2>(p, s);
 }
 
 }  // namespace himo
 
 using namespace himo;
 
+// every decision is plan_conv's (conv_plan.h); here the plan's family is launched
 extern "C" int himo_conv2d(const himo_conv_desc* d, void* stream) {
-    if (!d || !d->x || !d->w || !d->y) return HIMO_ERR_INVALID_ARGUMENT;
-    if (d->n < 1 || d->h < 1 || d->w_in < 1 || d->cin < 1 || d->cout < 1) return HIMO_ERR_INVALID_ARGUMENT;
-    if (!(d->ksize == 1 || d->ksize == 3) || !(d->stride == 1 || d->stride == 2)) return HIMO_ERR_UNSUPPORTED;
-    if (d->ksize == 1 && d->stride != 1) return HIMO_ERR_UNSUPPORTED;
-    if (d->epilogue < 0 || d->epilogue > kEpiReluMask) return HIMO_ERR_INVALID_ARGUMENT;
-    if (d->epilogue == kEpiBiasBnGelu && (!d->scale || !d->shift)) return HIMO_ERR_INVALID_ARGUMENT;
-    if ((d->epilogue == kEpiGruZR || d->epilogue == kEpiGruQ) && (!d->aux_in || !d->aux_out)) return HIMO_ERR_INVALID_ARGUMENT;
-    if (d->epilogue == kEpiReluMask && !d->aux_in) return HIMO_ERR_INVALID_ARGUMENT;
-    // 16-byte vector loads: channel counts / pitches / bases must be multiples of 4 floats
-    if ((d->cin & 3) || (d->cout & 3) || (d->x_pitch & 3) || (d->x_batch_stride & 3) || !aligned16(d->x) || !aligned16(d->w))
-        return HIMO_ERR_UNSUPPORTED;
-    ConvArgs a{};
-    a.x = d->x; a.x_batch_stride = d->x_batch_stride; a.x_pitch = d->x_pitch;
-    a.w = d->w; a.bias = d->bias; a.scale = d->scale; a.shift = d->shift;
-    a.y = d->y; a.y_batch_stride = d->y_batch_stride; a.y_pitch = d->y_pitch;
-    const int n_outer = d->n_outer > 1 ? d->n_outer : 1;
-    if (n_outer > 1 && ((d->x_outer_stride & 3) || (d->y_outer_stride & 3))) return HIMO_ERR_INVALID_ARGUMENT;
-    a.N = d->n * n_outer; a.n_inner = d->n; a.x_outer_stride = d->x_outer_stride; a.y_outer_stride = d->y_outer_stride;
-    a.H = d->h; a.W = d->w_in; a.Cin = d->cin; a.Cout = d->cout;
-    a.Ho = d->stride == 2 ? (d->h + 1) / 2 : d->h;      // 3x3, pad 1: ceil(H / stride)
-    a.Wo = d->stride == 2 ? (d->w_in + 1) / 2 : d->w_in;
-    a.aux_in = d->aux_in; a.aux_in_pitch = d->aux_in_pitch; a.aux_out = d->aux_out; a.aux_out_pitch = d->aux_out_pitch;
-    a.act_flags = d->act_layout;
-    a.range_seen = (d->act_layout & 2) ? d->d_range_seen : nullptr;
-    if (d->act_layout & (8 | 16)) {      // HIMO_ACT_ACCUMULATE (y += result) / HIMO_ACT_STUFFED_2X (compact input read zero-stuffed):
-        // the two-term bf16 3x3 stride-1 kernel with the bias epilogue only
-        // ... or, HIMO_ACT_ACCUMULATE alone, a row GEMM (ksize 1) of either bf16 split with the bias epilogue (csrc/convbf.hip)
-        const bool gemm_acc = d->act_layout == 8 && d->w_packed && d->ksize == 1 && d->epilogue == kEpiBias && (d->packed_format == 0 || d->packed_format == 2);
-        if (!gemm_acc &&
-            ((d->act_layout & ~(8 | 16)) || !d->w_packed || d->packed_format != 2 || d->ksize != 3 || d->stride != 1 || d->epilogue != kEpiBias))
-            return HIMO_ERR_UNSUPPORTED;
-        if ((d->act_layout & 16) && ((d->h & 1) || (d->w_in & 1) || (int64_t)(d->h / 2) * (d->w_in / 2) * d->x_pitch * 4 >= ((int64_t)1 << 31)))
-            return HIMO_ERR_UNSUPPORTED;
-    } else if (d->act_layout) {   // split activation format: fp16-split 3x3 layers only, whole 16-channel groups
-        if ((d->act_layout & ~3) || !d->w_packed || d->packed_format != 1) return HIMO_ERR_UNSUPPORTED;
-        if (d->ksize == 1 && !(d->act_layout & 1)) return HIMO_ERR_UNSUPPORTED;      // 1x1: split output only with split input
-        if (d->epilogue != kEpiBias && d->epilogue != kEpiBiasBnGelu) return HIMO_ERR_UNSUPPORTED;
-        if (((d->act_layout & 1) && ((d->cin & 15) || (d->x_pitch & 15))) ||
-            ((d->act_layout & 2) && ((d->cout & 15) || (d->y_pitch & 15))))
-            return HIMO_ERR_UNSUPPORTED;
-    }
+    if (!d) return HIMO_ERR_INVALID_ARGUMENT;
+    ConvPlan p;
+    const int st = plan_conv(*d, p);
+    if (st != HIMO_OK) return st;
     hipStream_t s = (hipStream_t)stream;
-    // split precision: every stride-1 layer, and the 3x3 stride-2 layers unless the caller pins a float32 tile
-    if (d->w_packed && (d->stride == 1 || (d->ksize == 3 && d->epilogue != kEpiGruZR && d->epilogue != kEpiGruQ &&
-                                          (d->tile_hint == 0 || (d->tile_hint & 0x1000)))))
-        return launch_conv_bf16x3(a, d->ksize, d->epilogue, d->w_packed, d->tile_hint, d->packed_format, d->stride, s);
-    // tile choice: 128 x 128 when that still gives >= 2 blocks per CU, else shrink M then N so the chip is filled
-    auto blocks_for = [&](int bn, int mi) -> int64_t {
-        const int bm = 64 * mi, th = 4 * mi;
-        const int64_t tm = d->ksize == 1 ? (int64_t)a.N * (((int64_t)a.Ho * a.Wo + bm - 1) / bm)
-                                         : (int64_t)a.N * ((a.Ho + th - 1) / th) * ((a.Wo + 15) / 16);
-        return tm * ((d->cout + bn - 1) / bn);
-    };
-    const bool can128 = d->cout >= 128 && (d->cout % 128) == 0;
-    const bool gru = d->epilogue == kEpiGruZR;          // the z|r split needs the 128-wide channel tile
-    int bn = can128 ? 128 : 64, mi = 2;
-    const int64_t want = 512;
-    if (blocks_for(bn, mi) < want) mi = 1;
-    if (blocks_for(bn, mi) < want && bn == 128 && !gru) bn = 64;
-    if (d->tile_hint) {
-        const int hb = d->tile_hint >> 4, hm = d->tile_hint & 15;
-        if ((hb == 64 || (hb == 128 && can128)) && (hm == 1 || hm == 2)) { bn = hb; mi = hm; }
-    }
-    const dim3 grid((unsigned)blocks_for(bn, mi));
-    const char* name = d->ksize == 1 ? "conv1x1_mfma_kernel" : (d->stride == 2 ? "conv3x3s2_mfma_kernel" : "conv3x3_mfma_kernel");
     {
-        ProfScope ps(name, s);
-        if (d->ksize == 1) launch_tile<1, 1>(a, d->epilogue, bn, mi, grid, s);
-        else if (d->stride == 1) launch_tile<3, 1>(a, d->epilogue, bn, mi, grid, s);
-        else launch_tile<3, 2>(a, d->epilogue, bn, mi, grid, s);
+        ProfScope ps(p.prof_name, s);
+        switch (p.family) {
+            case kConvF32: launch_conv_f32(p, s); break;
+            case kConvStaged: launch_conv_staged(p, s); break;
+            case kConvFromL2: launch_conv_from_l2(p, s); break;
+            case kConvPresplit3: launch_conv_presplit3(p, s); break;
+            case kConvPresplit1: launch_conv_presplit1(p, s); break;
+        }
     }
-    HIMO_LAUNCH_CHECK("conv_mfma_kernel");
+    HIMO_LAUNCH_CHECK(p.prof_name);
     return HIMO_OK;
 }
 

@@ -35,7 +35,7 @@ struct ConvArgs {
 };
 enum ActFlags { kActSplitIn = 1, kActSplitOut = 2, kActVecStore = 4, kActAccumulate = 8, kActStuffedIn = 16 };
 // kActStuffedIn (HIMO_ACT_STUFFED_2X): x is a compact [H / 2][W / 2] map read as its zero-stuffed x2 image (two-term bf16 3x3 kernel)
-// kActVecStore: set by the launchers (vec_store_ok).  kActAccumulate (HIMO_ACT_ACCUMULATE): y += result -- float32 output of the
+// kActVecStore: set by plan_conv (conv_plan.h, vec_store_ok).  kActAccumulate (HIMO_ACT_ACCUMULATE): y += result -- float32 output of the
 // two-term bf16 3x3 kernels only (the training step's stride-2 data gradients add into the decoder's skip gradient in place)
 
 // GELU (erf form).  erf by Abramowitz & Stegun 7.1.26 (|error| <= 1.5e-7, below float32 resolution of the 1 + erf sum)
@@ -218,7 +218,7 @@ __device__ inline void store_block_vec(const ConvArgs& a, float* __restrict__ yo
                 const float4 m = *reinterpret_cast<const float4*>(a.aux_in + (pix0 + px) * (int64_t)a.aux_in_pitch + ch0 + piece * 4);
                 d.x = m.x > 0.f ? d.x : 0u; d.y = m.y > 0.f ? d.y : 0u; d.z = m.z > 0.f ? d.z : 0u; d.w = m.w > 0.f ? d.w : 0u;
             }
-            // 32-bit offset from the (uniform) image base: vec_store_ok() admits only images below 2 GB, and a 64-bit multiply-add per
+            // 32-bit offset from the (uniform) image base: vec_store_ok admits only images below 2 GB, and a 64-bit multiply-add per
             // store was ~8 vector instructions of the block's ~60
             float* dst = yout + (((unsigned)pix0 + (unsigned)px) * (unsigned)a.y_pitch + (unsigned)(ch0 + piece * 4));
             if (ACC) {                                     // y += result (float32 words)
@@ -250,8 +250,5 @@ __device__ inline unsigned split_word(float v, bool odd) {
     // v_perm_b32: selector bytes 0-3 pick from the SECOND operand (p), 4-7 from the first (q)
     return __builtin_amdgcn_perm(q, p, odd ? 0x03020706u : 0x05040100u);
 }
-
-// implemented in convbf.hip: stride-1 convolutions / row GEMMs on split-bf16 matrix instructions
-int launch_conv_bf16x3(const ConvArgs& a, int ksize, int epilogue, const void* w_packed, int tile_hint, int format, int stride, hipStream_t s);
 
 }  // namespace himo

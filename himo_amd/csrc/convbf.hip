@@ -20,10 +20,9 @@
 //   * the next tap's weights (and the next slab's patch) are prefetched into registers under the MFMAs.
 //
 // FMT = 2 runs the same structure on the two-term fp16 split (bf16x3.h: x = h + l, three products per block);
-// its two planes leave LDS room to stage a whole kernel row of weights per barrier.  The 3x3 layers normally run the
-// second structure in convsp.hip (weight fragments straight from L2, one barrier per slab); this file keeps the row
-// GEMMs (1x1 layers, GRU epilogues) and remains selectable per layer through himo_conv_desc.tile_hint.
-#include "conv_common.h"
+// its two planes leave LDS room to stage a whole kernel row of weights per barrier.  Which calls run here and
+// which in convsp.hip (weight fragments straight from L2, one barrier per slab): plan_conv, conv_plan.h.
+#include "conv_plan.h"
 #include "bf16x3.h"
 #include <algorithm>
 
@@ -367,90 +366,38 @@ __global__ __launch_bounds__(256) void conv_bf16x3_kernel(ConvArgs a, const unsi
 }
 
 template <int KS, int BN, int MI, int FMT>
-static void launch_bf_epi(const ConvArgs& a, int epi, const unsigned short* w, dim3 grid, hipStream_t s) {
-    if constexpr (FMT == 4) {              // the data-gradient format: bias, or bias + ReLU mask of the layer's input (launch_conv_bf16x3 has checked)
-        if (epi == kEpiReluMask) hipLaunchKernelGGL((conv_bf16x3_kernel<KS, BN, kEpiReluMask, MI, FMT>), grid, dim3(256), 0, s, a, w);
-        else hipLaunchKernelGGL((conv_bf16x3_kernel<KS, BN, kEpiBias, MI, FMT>), grid, dim3(256), 0, s, a, w);
+static void launch_bf_epi(const ConvPlan& p, hipStream_t s) {
+    const unsigned short* w = (const unsigned short*)p.w_packed;
+    if constexpr (FMT == 4) {              // the data-gradient format: bias, or bias + ReLU mask of the layer's input (plan_conv has checked)
+        if (p.epi == kEpiReluMask) hipLaunchKernelGGL((conv_bf16x3_kernel<KS, BN, kEpiReluMask, MI, FMT>), p.grid, dim3(256), 0, s, p.args, w);
+        else hipLaunchKernelGGL((conv_bf16x3_kernel<KS, BN, kEpiBias, MI, FMT>), p.grid, dim3(256), 0, s, p.args, w);
         return;
     }
-    switch (epi) {
-        case kEpiBias: hipLaunchKernelGGL((conv_bf16x3_kernel<KS, BN, kEpiBias, MI, FMT>), grid, dim3(256), 0, s, a, w); break;
-        case kEpiBiasBnGelu: hipLaunchKernelGGL((conv_bf16x3_kernel<KS, BN, kEpiBiasBnGelu, MI, FMT>), grid, dim3(256), 0, s, a, w); break;
-        case kEpiBiasGelu: hipLaunchKernelGGL((conv_bf16x3_kernel<KS, BN, kEpiBiasGelu, MI, FMT>), grid, dim3(256), 0, s, a, w); break;
-        case kEpiGruZR: hipLaunchKernelGGL((conv_bf16x3_kernel<KS, BN, kEpiGruZR, MI, FMT>), grid, dim3(256), 0, s, a, w); break;
-        case kEpiBiasRelu: hipLaunchKernelGGL((conv_bf16x3_kernel<KS, BN, kEpiBiasRelu, MI, FMT>), grid, dim3(256), 0, s, a, w); break;
-        case kEpiReluMask: hipLaunchKernelGGL((conv_bf16x3_kernel<KS, BN, kEpiReluMask, MI, FMT>), grid, dim3(256), 0, s, a, w); break;
-        default: hipLaunchKernelGGL((conv_bf16x3_kernel<KS, BN, kEpiGruQ, MI, FMT>), grid, dim3(256), 0, s, a, w); break;
+    switch (p.epi) {
+        case kEpiBias: hipLaunchKernelGGL((conv_bf16x3_kernel<KS, BN, kEpiBias, MI, FMT>), p.grid, dim3(256), 0, s, p.args, w); break;
+        case kEpiBiasBnGelu: hipLaunchKernelGGL((conv_bf16x3_kernel<KS, BN, kEpiBiasBnGelu, MI, FMT>), p.grid, dim3(256), 0, s, p.args, w); break;
+        case kEpiBiasGelu: hipLaunchKernelGGL((conv_bf16x3_kernel<KS, BN, kEpiBiasGelu, MI, FMT>), p.grid, dim3(256), 0, s, p.args, w); break;
+        case kEpiGruZR: hipLaunchKernelGGL((conv_bf16x3_kernel<KS, BN, kEpiGruZR, MI, FMT>), p.grid, dim3(256), 0, s, p.args, w); break;
+        case kEpiBiasRelu: hipLaunchKernelGGL((conv_bf16x3_kernel<KS, BN, kEpiBiasRelu, MI, FMT>), p.grid, dim3(256), 0, s, p.args, w); break;
+        case kEpiReluMask: hipLaunchKernelGGL((conv_bf16x3_kernel<KS, BN, kEpiReluMask, MI, FMT>), p.grid, dim3(256), 0, s, p.args, w); break;
+        default: hipLaunchKernelGGL((conv_bf16x3_kernel<KS, BN, kEpiGruQ, MI, FMT>), p.grid, dim3(256), 0, s, p.args, w); break;
     }
 }
 
 template <int KS, int FMT>
-static void launch_bf_tile(const ConvArgs& a, int epi, int bn, int mi, const unsigned short* w, dim3 grid, hipStream_t s) {
-    if (bn == 128) { if (mi == 2) launch_bf_epi<KS, 128, 2, FMT>(a, epi, w, grid, s); else launch_bf_epi<KS, 128, 1, FMT>(a, epi, w, grid, s); }
-    else { if (mi == 2) launch_bf_epi<KS, 64, 2, FMT>(a, epi, w, grid, s); else launch_bf_epi<KS, 64, 1, FMT>(a, epi, w, grid, s); }
+static void launch_bf_tile(const ConvPlan& p, hipStream_t s) {
+    if (p.bn == 128) { if (p.mi == 2) launch_bf_epi<KS, 128, 2, FMT>(p, s); else launch_bf_epi<KS, 128, 1, FMT>(p, s); }
+    else { if (p.mi == 2) launch_bf_epi<KS, 64, 2, FMT>(p, s); else launch_bf_epi<KS, 64, 1, FMT>(p, s); }
 }
 
-bool launch_conv3_split(const ConvArgs& a, int epilogue, const void* w_packed, int format, int rows_hint, int stride, hipStream_t s);   // convsp.hip
-
-bool launch_conv3_presplit(const ConvArgs& a, int epilogue, const void* w_packed, int rows_hint, bool out_split, int stride, hipStream_t s);
-bool launch_conv1_presplit(const ConvArgs& a, int epilogue, const void* w_packed, int rows_hint, bool out_split, hipStream_t s);   // convsg.hip
-
-int launch_conv_bf16x3(const ConvArgs& a, int ksize, int epilogue, const void* w_packed, int tile_hint, int format, int stride, hipStream_t s) {
-    if ((a.act_flags & kActSplitIn) && ksize == 1) {
-        if (!launch_conv1_presplit(a, epilogue, w_packed, tile_hint & 15, (a.act_flags & kActSplitOut) != 0, s)) return HIMO_ERR_UNSUPPORTED;
-        HIMO_LAUNCH_CHECK("conv1_presplit_kernel");
-        return HIMO_OK;
+// packed_format 0 | 1 | 2 -> FMT 3 | 2 | 4 (bf16 planes h, m, l | fp16 h, l | bf16 h, m: row GEMMs only)
+void launch_conv_staged(const ConvPlan& p, hipStream_t s) {
+    if (p.ks == 1) {
+        if (p.fmt == 1) launch_bf_tile<1, 2>(p, s);
+        else if (p.fmt == 2) launch_bf_tile<1, 4>(p, s);
+        else launch_bf_tile<1, 3>(p, s);
     }
-    if (a.act_flags & kActSplitIn) {            // input already split in HBM: the LDS-DMA kernel
-        if (!launch_conv3_presplit(a, epilogue, w_packed, tile_hint & 15, (a.act_flags & kActSplitOut) != 0, stride, s)) return HIMO_ERR_UNSUPPORTED;
-        HIMO_LAUNCH_CHECK("conv3_presplit_kernel");
-        return HIMO_OK;
-    }
-    const bool gemm_accumulate = a.act_flags == kActAccumulate && ksize == 1 && epilogue == kEpiBias &&
-                                 (int64_t)a.Ho * a.Wo * a.y_pitch < (1ll << 30);      // (the row GEMMs' 32-bit-offset epilogue: the one that implements it)
-    if (a.act_flags && !gemm_accumulate && !(ksize == 3 && (!tile_hint || (tile_hint & 0x1000) || stride == 2))) return HIMO_ERR_UNSUPPORTED;
-    // 3x3 layers: the weights-from-L2 structure (convsp.hip; tile_hint 0x1000 | rows-per-wave pins its variant) unless the
-    // caller pins a tile of this file's kernel
-    if (ksize == 3 && (!tile_hint || (tile_hint & 0x1000) || stride == 2) &&
-        launch_conv3_split(a, epilogue, w_packed, format, tile_hint & 15, stride, s)) {
-        HIMO_LAUNCH_CHECK("conv3_split_kernel");
-        return HIMO_OK;
-    }
-    if (ksize == 3 && (tile_hint & 0x1000) && (tile_hint & 15) > 4) return HIMO_ERR_UNSUPPORTED;     // a pinned variant this layer does not admit
-    if (stride != 1) return HIMO_ERR_UNSUPPORTED;
-    if ((int64_t)a.H * a.W * a.x_pitch * 4 >= ((int64_t)1 << 31)) return HIMO_ERR_UNSUPPORTED;          // 32-bit byte offsets into an image (buffer resource)
-    if (format == 2 && (ksize != 1 || (epilogue != kEpiBias && epilogue != kEpiReluMask) || (a.act_flags && !gemm_accumulate))) return HIMO_ERR_UNSUPPORTED;     // two-term bf16: 3x3 in convsp.hip, row GEMMs here
-    auto blocks_for = [&](int bn, int mi) -> int64_t {
-        const int bm = 64 * mi, th = 2 * mi;
-        const int64_t tm = ksize == 1 ? (int64_t)a.N * (((int64_t)a.Ho * a.Wo + bm - 1) / bm)
-                                      : (int64_t)a.N * ((a.Ho + th - 1) / th) * ((a.Wo + 31) / 32);
-        return tm * ((a.Cout + bn - 1) / bn);
-    };
-    const bool can128 = a.Cout >= 128 && (a.Cout % 128) == 0;
-    int bn = can128 ? 128 : 64, mi = 2;
-    const int64_t want = 512;
-    if (blocks_for(bn, mi) < want) mi = 1;
-    if (blocks_for(bn, mi) < want && bn == 128) bn = 64;
-    if (tile_hint) {                                            // caller-tuned tile: (bn << 4) | mi
-        const int hb = tile_hint >> 4, hm = tile_hint & 15;
-        if ((hb == 64 || (hb == 128 && can128)) && (hm == 1 || hm == 2)) { bn = hb; mi = hm; }
-    }
-    const dim3 grid((unsigned)blocks_for(bn, mi));
-    const bool f16 = format == 1;
-    const char* name = ksize == 1 ? (f16 ? "conv1x1_f16x2_kernel" : format == 2 ? "conv1x1_bf16x2_kernel" : "conv1x1_bf16x3_kernel")
-                                  : (f16 ? "conv3x3_f16x2_kernel" : "conv3x3_bf16x3_kernel");
-    {
-        ProfScope ps(name, s);
-        const unsigned short* w = (const unsigned short*)w_packed;
-        if (ksize == 1) {
-            if (f16) launch_bf_tile<1, 2>(a, epilogue, bn, mi, w, grid, s);
-            else if (format == 2) launch_bf_tile<1, 4>(a, epilogue, bn, mi, w, grid, s);
-            else launch_bf_tile<1, 3>(a, epilogue, bn, mi, w, grid, s);
-        }
-        else { if (f16) launch_bf_tile<3, 2>(a, epilogue, bn, mi, w, grid, s); else launch_bf_tile<3, 3>(a, epilogue, bn, mi, w, grid, s); }
-    }
-    HIMO_LAUNCH_CHECK("conv_bf16x3_kernel");
-    return HIMO_OK;
+    else { if (p.fmt == 1) launch_bf_tile<3, 2>(p, s); else launch_bf_tile<3, 3>(p, s); }
 }
 
 }  // namespace himo

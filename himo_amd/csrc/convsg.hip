@@ -29,7 +29,7 @@
 // patch memory and leave as 16-byte stores, eight full 128-byte lines per instruction (store_block_vec, conv_common.h);
 // blocks walk the grid in an XCD-aware order (xcd_block_id).
 // Specification / oracle as conv.hip (reference network absent: PARITY UNPINNED).
-#include "conv_common.h"
+#include "conv_plan.h"
 #include "bf16x3.h"
 
 namespace himo {
@@ -372,108 +372,51 @@ void conv1_presplit_kernel(ConvArgs a, const unsigned short* __restrict__ wpk) {
     }
 }
 
-template <int PH, int MI>
-static void launch_sg1(const ConvArgs& a_in, int epi, bool osplit, const unsigned short* w, dim3 grid, hipStream_t s) {
-    ConvArgs a = a_in;
-    if (vec_store_ok(a)) a.act_flags |= kActVecStore;
-#define HIMO_SG(E, O) hipLaunchKernelGGL((conv1_presplit_kernel<E, PH, MI, O>), grid, dim3(256), 0, s, a, w)
-    if (epi == kEpiBias) { if (osplit) HIMO_SG(kEpiBias, true); else HIMO_SG(kEpiBias, false); }
-    else { if (osplit) HIMO_SG(kEpiBiasBnGelu, true); else HIMO_SG(kEpiBiasBnGelu, false); }
-#undef HIMO_SG
-}
+// (epilogue, split output) -> instantiation of KERNEL<EPI, PH, MI, OSPLIT, ...>
+#define HIMO_SG(KERNEL, E, O, ...) hipLaunchKernelGGL((KERNEL<E, PH, MI, O, ##__VA_ARGS__>), p.grid, dim3(256), 0, s, p.args, (const unsigned short*)p.w_packed)
+#define HIMO_SG_EPI(KERNEL, ...)                                                                                                          \
+    do {                                                                                                                                  \
+        const bool osplit = (p.args.act_flags & kActSplitOut) != 0;                                                                       \
+        if (p.epi == kEpiBias) { if (osplit) HIMO_SG(KERNEL, kEpiBias, true, ##__VA_ARGS__); else HIMO_SG(KERNEL, kEpiBias, false, ##__VA_ARGS__); } \
+        else { if (osplit) HIMO_SG(KERNEL, kEpiBiasBnGelu, true, ##__VA_ARGS__); else HIMO_SG(KERNEL, kEpiBiasBnGelu, false, ##__VA_ARGS__); }       \
+    } while (0)
 
-// 1x1 layers whose input is in the split activation format.  rows_hint: 32-pixel segments per wave (4 | 2 | 1).
-bool launch_conv1_presplit(const ConvArgs& a, int epilogue, const void* w_packed, int rows_hint, bool out_split, hipStream_t s) {
-    if ((epilogue != kEpiBias && epilogue != kEpiBiasBnGelu) || (a.Cin & 15) || (out_split && (a.Cout & 15))) return false;
-    if ((int64_t)a.Ho * a.Wo * a.x_pitch * 4 >= (int64_t)1 << 31) return false;       // 32-bit DMA source offsets
-    const bool wide = a.Cout > 64;
-    const int bn = wide ? 128 : 64, ph = wide ? 1 : 2;
-    auto blocks_for = [&](int mi) -> int64_t {
-        return (int64_t)a.N * (((int64_t)a.Ho * a.Wo + mi * ph * 32 - 1) / (mi * ph * 32)) * ((a.Cout + bn - 1) / bn);
-    };
-    int mi = wide ? 4 : 2;
-    while (mi > 1 && blocks_for(mi) < 2048) mi >>= 1;
-    if (rows_hint == 4 || rows_hint == 2 || rows_hint == 1) mi = rows_hint;
-    if (!wide && mi == 4) mi = 2;
-    const dim3 grid((unsigned)blocks_for(mi));
-    const unsigned short* w = (const unsigned short*)w_packed;
-    ProfScope ps("conv1x1_f16x2_kernel", s);
-    if (wide) {
-        if (mi == 4) launch_sg1<1, 4>(a, epilogue, out_split, w, grid, s);
-        else if (mi == 2) launch_sg1<1, 2>(a, epilogue, out_split, w, grid, s);
-        else launch_sg1<1, 1>(a, epilogue, out_split, w, grid, s);
-    } else {
-        if (mi == 2) launch_sg1<2, 2>(a, epilogue, out_split, w, grid, s);
-        else launch_sg1<2, 1>(a, epilogue, out_split, w, grid, s);
-    }
-    return true;
-}
+template <int PH, int MI>
+static void launch_sg1(const ConvPlan& p, hipStream_t s) { HIMO_SG_EPI(conv1_presplit_kernel); }
 
 template <int PH, int MI, int S = 1, int NT = 1>
-static void launch_sg(const ConvArgs& a_in, int epi, bool osplit, const unsigned short* w, dim3 grid, hipStream_t s) {
-    ConvArgs a = a_in;
-    if (vec_store_ok(a)) a.act_flags |= kActVecStore;
-#define HIMO_SG(E, O) hipLaunchKernelGGL((conv3_presplit_kernel<E, PH, MI, O, S, NT>), grid, dim3(256), 0, s, a, w)
-    if (epi == kEpiBias) { if (osplit) HIMO_SG(kEpiBias, true); else HIMO_SG(kEpiBias, false); }
-    else { if (osplit) HIMO_SG(kEpiBiasBnGelu, true); else HIMO_SG(kEpiBiasBnGelu, false); }
+static void launch_sg(const ConvPlan& p, hipStream_t s) { HIMO_SG_EPI(conv3_presplit_kernel, S, NT); }
+#undef HIMO_SG_EPI
 #undef HIMO_SG
+
+// 1x1 layers whose input is in the split activation format: ph 1 = 128-channel blocks, 2 = 64-channel blocks; mi 32-pixel segments per wave
+void launch_conv_presplit1(const ConvPlan& p, hipStream_t s) {
+    if (p.ph == 1) {
+        if (p.mi == 4) launch_sg1<1, 4>(p, s);
+        else if (p.mi == 2) launch_sg1<1, 2>(p, s);
+        else launch_sg1<1, 1>(p, s);
+    } else {
+        if (p.mi == 2) launch_sg1<2, 2>(p, s);
+        else launch_sg1<2, 1>(p, s);
+    }
 }
 
-// 3x3 layers (stride 1 | 2) whose input is in the split activation format (fp16-split weights, Cin a multiple of 16,
-// bias or bias + BN + GELU epilogue).  rows_hint: image rows per wave (4 | 2 | 1), 0 = heuristic.  false = not applicable.
-bool launch_conv3_presplit(const ConvArgs& a, int epilogue, const void* w_packed, int rows_hint, bool out_split, int stride, hipStream_t s) {
-    if ((epilogue != kEpiBias && epilogue != kEpiBiasBnGelu) || (a.Cin & 15) || (out_split && (a.Cout & 15))) return false;
-    if ((int64_t)a.H * a.W * a.x_pitch * 4 >= (int64_t)1 << 31) return false;       // 32-bit DMA source offsets
-    const bool wide = a.Cout > 64;
-    const int bn = wide ? 128 : 64, ph = wide ? 1 : 2;
-    if (stride == 2) {                                  // two output rows per block: a 5-row x 80-slot patch, double-buffered
-        const int64_t blocks = (int64_t)a.N * ((a.Ho + 1) / 2) * ((a.Wo + 31) / 32) * ((a.Cout + bn - 1) / bn);
-        ProfScope ps("conv3x3s2_f16x2_kernel", s);
-        if (wide) launch_sg<1, 2, 2>(a, epilogue, out_split, (const unsigned short*)w_packed, dim3((unsigned)blocks), s);
-        else launch_sg<2, 1, 2>(a, epilogue, out_split, (const unsigned short*)w_packed, dim3((unsigned)blocks), s);
-        return true;
+// 3x3 layers (stride 1 | 2) whose input is in the split activation format: mi image rows per wave, nt 32-channel column tiles per wave
+void launch_conv_presplit3(const ConvPlan& p, hipStream_t s) {
+    if (p.stride == 2) { if (p.ph == 1) launch_sg<1, 2, 2>(p, s); else launch_sg<2, 1, 2>(p, s); }
+    else if (p.nt == 2) {
+        if (p.ph == 4) launch_sg<4, 2, 1, 2>(p, s);
+        else if (p.ph == 1) launch_sg<1, 4, 1, 2>(p, s);
+        else launch_sg<2, 4, 1, 2>(p, s);
     }
-    // 64-channel layers, rows_hint 8: a wave owns 2 rows x 32 pixels x BOTH 32-channel column tiles (every activation fragment
-    // meets two weight fragments), four waves = an 8-row tile on a 10-row patch (1.25x halo instead of 1.5x; 51 KB: three blocks per CU)
-    if (!wide && rows_hint == 8 && vec_store_ok(a)) {
-        const int64_t blocks = (int64_t)a.N * ((a.Ho + 7) / 8) * ((a.Wo + 31) / 32) * ((a.Cout + 63) / 64);
-        ProfScope ps("conv3x3_f16x2_kernel", s);
-        launch_sg<4, 2, 1, 2>(a, epilogue, out_split, (const unsigned short*)w_packed, dim3((unsigned)blocks), s);
-        return true;
-    }
-    // wide layers, rows_hint 12: 4 rows x 64 channels per wave (128 accumulator registers, two waves per SIMD): half the
-    // fragment reads AND half the weight loads per matrix instruction; 3-4 % on the 256-channel decoder layers, slower on
-    // the 128-channel encoder ones (the autotune decides per layer)
-    if (wide && rows_hint == 12 && vec_store_ok(a)) {
-        ProfScope ps("conv3x3_f16x2_kernel", s);
-        if (a.Cout % 256 == 0) {
-            const int64_t blocks = (int64_t)a.N * ((a.Ho + 3) / 4) * ((a.Wo + 31) / 32) * (a.Cout / 256);
-            launch_sg<1, 4, 1, 2>(a, epilogue, out_split, (const unsigned short*)w_packed, dim3((unsigned)blocks), s);
-        } else {
-            const int64_t blocks = (int64_t)a.N * ((a.Ho + 7) / 8) * ((a.Wo + 31) / 32) * ((a.Cout + 127) / 128);
-            launch_sg<2, 4, 1, 2>(a, epilogue, out_split, (const unsigned short*)w_packed, dim3((unsigned)blocks), s);
-        }
-        return true;
-    }
-    auto blocks_for = [&](int mi) -> int64_t {
-        const int th = mi * ph;
-        return (int64_t)a.N * ((a.Ho + th - 1) / th) * ((a.Wo + 31) / 32) * ((a.Cout + bn - 1) / bn);
-    };
-    int mi = blocks_for(4) >= 1024 ? 4 : 2;
-    if (rows_hint == 4 || rows_hint == 2 || rows_hint == 1) mi = rows_hint;
-    if (!wide && mi == 4) mi = 2;                       // 64-channel blocks: 8-row patches would not leave three blocks per CU
-    const dim3 grid((unsigned)blocks_for(mi));
-    const unsigned short* w = (const unsigned short*)w_packed;
-    ProfScope ps("conv3x3_f16x2_kernel", s);
-    if (wide) {
-        if (mi == 4) launch_sg<1, 4>(a, epilogue, out_split, w, grid, s);
-        else if (mi == 2) launch_sg<1, 2>(a, epilogue, out_split, w, grid, s);
-        else launch_sg<1, 1>(a, epilogue, out_split, w, grid, s);
+    else if (p.ph == 1) {
+        if (p.mi == 4) launch_sg<1, 4>(p, s);
+        else if (p.mi == 2) launch_sg<1, 2>(p, s);
+        else launch_sg<1, 1>(p, s);
     } else {
-        if (mi == 2) launch_sg<2, 2>(a, epilogue, out_split, w, grid, s);
-        else launch_sg<2, 1>(a, epilogue, out_split, w, grid, s);
+        if (p.mi == 2) launch_sg<2, 2>(p, s);
+        else launch_sg<2, 1>(p, s);
     }
-    return true;
 }
 
 }  // namespace himo

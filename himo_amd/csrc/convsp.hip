@@ -19,7 +19,7 @@
 // `SeFlowNet.split_acts = False`); the fp16-split inference network stores its maps already split and runs convsg.hip,
 // which replaces the register staging below by LDS-DMA.  This kernel's epilogue can WRITE that format (kActSplitOut).
 // Specification / oracle as conv.hip (reference network absent: PARITY UNPINNED).
-#include "conv_common.h"
+#include "conv_plan.h"
 #include "bf16x3.h"
 
 namespace himo {
@@ -317,72 +317,44 @@ void conv3_split_kernel(ConvArgs a, const unsigned short* __restrict__ wpk) {
 }
 
 template <int PH, int FMT, int MI, int S>
-static void launch_sp_epi(const ConvArgs& a_in, int epi, const unsigned short* w, dim3 grid, hipStream_t s) {
-    ConvArgs a = a_in;
-    if (vec_store_ok(a) && (!(a.act_flags & kActSplitOut) || !(a.Cout & 15))) a.act_flags |= kActVecStore;
-    if constexpr (FMT == 4) {          // the data-gradient format: bias epilogue only (launch_conv3_split has checked)
+static void launch_sp_epi(const ConvPlan& p, hipStream_t s) {
+    const unsigned short* w = (const unsigned short*)p.w_packed;
+    if constexpr (FMT == 4) {          // the data-gradient format: bias epilogue only (plan_conv has checked)
         if constexpr (S == 1) {
-            if (a.act_flags & kActStuffedIn) { hipLaunchKernelGGL((conv3_split_kernel<kEpiBias, PH, FMT, MI, S, true>), grid, dim3(256), 0, s, a, w); return; }
+            if (p.args.act_flags & kActStuffedIn) { hipLaunchKernelGGL((conv3_split_kernel<kEpiBias, PH, FMT, MI, S, true>), p.grid, dim3(256), 0, s, p.args, w); return; }
         }
-        hipLaunchKernelGGL((conv3_split_kernel<kEpiBias, PH, FMT, MI, S>), grid, dim3(256), 0, s, a, w);
+        hipLaunchKernelGGL((conv3_split_kernel<kEpiBias, PH, FMT, MI, S>), p.grid, dim3(256), 0, s, p.args, w);
         return;
     }
-    switch (epi) {
-        case kEpiBias: hipLaunchKernelGGL((conv3_split_kernel<kEpiBias, PH, FMT, MI, S>), grid, dim3(256), 0, s, a, w); break;
-        case kEpiBiasBnGelu: hipLaunchKernelGGL((conv3_split_kernel<kEpiBiasBnGelu, PH, FMT, MI, S>), grid, dim3(256), 0, s, a, w); break;
-        case kEpiBiasGelu: hipLaunchKernelGGL((conv3_split_kernel<kEpiBiasGelu, PH, FMT, MI, S>), grid, dim3(256), 0, s, a, w); break;
-        case kEpiBiasRelu: hipLaunchKernelGGL((conv3_split_kernel<kEpiBiasRelu, PH, FMT, MI, S>), grid, dim3(256), 0, s, a, w); break;
-        default: hipLaunchKernelGGL((conv3_split_kernel<kEpiReluMask, PH, FMT, MI, S>), grid, dim3(256), 0, s, a, w); break;
+    switch (p.epi) {
+        case kEpiBias: hipLaunchKernelGGL((conv3_split_kernel<kEpiBias, PH, FMT, MI, S>), p.grid, dim3(256), 0, s, p.args, w); break;
+        case kEpiBiasBnGelu: hipLaunchKernelGGL((conv3_split_kernel<kEpiBiasBnGelu, PH, FMT, MI, S>), p.grid, dim3(256), 0, s, p.args, w); break;
+        case kEpiBiasGelu: hipLaunchKernelGGL((conv3_split_kernel<kEpiBiasGelu, PH, FMT, MI, S>), p.grid, dim3(256), 0, s, p.args, w); break;
+        case kEpiBiasRelu: hipLaunchKernelGGL((conv3_split_kernel<kEpiBiasRelu, PH, FMT, MI, S>), p.grid, dim3(256), 0, s, p.args, w); break;
+        default: hipLaunchKernelGGL((conv3_split_kernel<kEpiReluMask, PH, FMT, MI, S>), p.grid, dim3(256), 0, s, p.args, w); break;
     }
 }
 
 template <int PH, int FMT>
-static void launch_sp_mi(const ConvArgs& a, int epi, int mi, int stride, const unsigned short* w, dim3 grid, hipStream_t s) {
-    if (stride == 2) {                                                         // stride 2: two output rows per wave, or one
-        if (mi == 1) launch_sp_epi<PH, FMT, 1, 2>(a, epi, w, grid, s);        // (64-channel blocks: keeps the 5 x 65 patch double-buffered)
-        else launch_sp_epi<PH, FMT, 2, 2>(a, epi, w, grid, s);
+static void launch_sp_mi(const ConvPlan& p, hipStream_t s) {
+    if (p.stride == 2) {                                                    // stride 2: two output rows per wave, or one
+        if (p.mi == 1) launch_sp_epi<PH, FMT, 1, 2>(p, s);
+        else launch_sp_epi<PH, FMT, 2, 2>(p, s);
     }
-    else if (mi == 4) launch_sp_epi<PH, FMT, 4, 1>(a, epi, w, grid, s);
-    else if (mi == 1) launch_sp_epi<PH, FMT, 1, 1>(a, epi, w, grid, s);         // small images: more, smaller blocks
-    else launch_sp_epi<PH, FMT, 2, 1>(a, epi, w, grid, s);
+    else if (p.mi == 4) launch_sp_epi<PH, FMT, 4, 1>(p, s);
+    else if (p.mi == 1) launch_sp_epi<PH, FMT, 1, 1>(p, s);                  // small images: more, smaller blocks
+    else launch_sp_epi<PH, FMT, 2, 1>(p, s);
 }
 
-// 3x3 layers (stride 1 | 2) with a plain epilogue; returns false when this structure does not apply (GRU epilogues).
-// rows_hint: 0 = heuristic, else image rows per wave (4 | 2 | 1; stride 2 always uses 2).
-bool launch_conv3_split(const ConvArgs& a, int epilogue, const void* w_packed, int format, int rows_hint, int stride, hipStream_t s) {
-    if (epilogue == kEpiGruZR || epilogue == kEpiGruQ) return false;
-    if (format == 2 && (epilogue != kEpiBias || (a.act_flags & ~(kActAccumulate | kActStuffedIn)))) return false;   // two-term bf16: float32 maps, bias epilogue
-    if ((a.act_flags & kActAccumulate) && (format != 2 || !vec_store_ok(a))) return false;              // y += result: that kernel's 16-byte store path only
-    if ((a.act_flags & kActStuffedIn) && (format != 2 || stride != 1)) return false;                    // zero-stuffed input: that kernel, stride 1
-    if ((int64_t)a.H * a.W * a.x_pitch * 4 >= ((int64_t)1 << 31)) return false;                         // 32-bit byte offsets into an image (buffer resource)
-    // rows_hint 5 | 6: PH = 2 forced (wide layers too), 1 | 2 rows per wave; 9 | 10: PH = 4, 1 | 2 rows per wave -- stride 1, two-term formats
-    const int ph_hint = (stride == 1 && format != 0 && (rows_hint == 5 || rows_hint == 6)) ? 2
-                      : (stride == 1 && format != 0 && (rows_hint == 9 || rows_hint == 10)) ? 4 : 0;
-    if (!ph_hint && rows_hint > 4) return false;
-    const bool wide = a.Cout > 64 && ph_hint == 0;     // PH = 1: 128-channel tiles; PH = 2: 64-channel tiles
-    const int ph = ph_hint ? ph_hint : (wide ? 1 : 2), bn = (4 / ph) * 32;
-    auto blocks_for = [&](int mi) -> int64_t {
-        const int th = mi * ph;
-        return (int64_t)a.N * ((a.Ho + th - 1) / th) * ((a.Wo + 31) / 32) * ((a.Cout + bn - 1) / bn);
-    };
-    int mi = blocks_for(4) >= 1024 ? 4 : 2;            // two blocks per CU, at least two rounds of them
-    if (rows_hint == 4 || rows_hint == 2 || rows_hint == 1) mi = rows_hint;
-    if (ph_hint) mi = rows_hint & 3;
-    if (stride == 2) mi = (rows_hint == 1 || rows_hint == 2) ? rows_hint : (wide ? 2 : 1);
-    const dim3 grid((unsigned)blocks_for(mi));
-    const unsigned short* w = (const unsigned short*)w_packed;
-    const char* name = stride == 2 ? (format == 1 ? "conv3x3s2_f16x2_kernel" : format == 2 ? "conv3x3s2_bf16x2_kernel" : "conv3x3s2_bf16x3_kernel")
-                                   : (format == 1 ? "conv3x3_f16x2_kernel" : format == 2 ? "conv3x3_bf16x2_kernel" : "conv3x3_bf16x3_kernel");
-    ProfScope ps(name, s);
-    if (ph == 4) {                                      // stride 1, rows per wave 1 | 2 only (fewer instantiations)
-        if (format == 2) { if (mi == 1) launch_sp_epi<4, 4, 1, 1>(a, epilogue, w, grid, s); else launch_sp_epi<4, 4, 2, 1>(a, epilogue, w, grid, s); }
-        else { if (mi == 1) launch_sp_epi<4, 2, 1, 1>(a, epilogue, w, grid, s); else launch_sp_epi<4, 2, 2, 1>(a, epilogue, w, grid, s); }
-        return true;
+// packed_format 0 | 1 | 2 -> FMT 3 | 2 | 4; ph 1 = 128-channel blocks, 2 = 64-channel blocks, 4 = 32-channel blocks
+void launch_conv_from_l2(const ConvPlan& p, hipStream_t s) {
+    if (p.ph == 4) {                                    // stride 1, two-term formats, rows per wave 1 | 2 only (fewer instantiations)
+        if (p.fmt == 2) { if (p.mi == 1) launch_sp_epi<4, 4, 1, 1>(p, s); else launch_sp_epi<4, 4, 2, 1>(p, s); }
+        else { if (p.mi == 1) launch_sp_epi<4, 2, 1, 1>(p, s); else launch_sp_epi<4, 2, 2, 1>(p, s); }
     }
-    if (format == 2) { if (wide) launch_sp_mi<1, 4>(a, epilogue, mi, stride, w, grid, s); else launch_sp_mi<2, 4>(a, epilogue, mi, stride, w, grid, s); }
-    else if (format == 1) { if (wide) launch_sp_mi<1, 2>(a, epilogue, mi, stride, w, grid, s); else launch_sp_mi<2, 2>(a, epilogue, mi, stride, w, grid, s); }
-    else { if (wide) launch_sp_mi<1, 3>(a, epilogue, mi, stride, w, grid, s); else launch_sp_mi<2, 3>(a, epilogue, mi, stride, w, grid, s); }
-    return true;
+    else if (p.fmt == 2) { if (p.ph == 1) launch_sp_mi<1, 4>(p, s); else launch_sp_mi<2, 4>(p, s); }
+    else if (p.fmt == 1) { if (p.ph == 1) launch_sp_mi<1, 2>(p, s); else launch_sp_mi<2, 2>(p, s); }
+    else { if (p.ph == 1) launch_sp_mi<1, 3>(p, s); else launch_sp_mi<2, 3>(p, s); }
 }
 
 }  // namespace himo

@@ -118,6 +118,30 @@ def _f32x(values):
     return (ctypes.c_float * len(values))(*[float(v) for v in values])
 
 
+def fastest_tile_hint(lib, d: "ConvDesc", hints, warmup: int) -> int:
+    """The fastest admitted ``tile_hint`` of one convolution descriptor (every variant gives the same bits; ``d.tile_hint`` is
+    left at the last one tried).  Two interleaved rounds, best time of each hint: the chip's clock drifts with load, and a
+    one-shot ranking of near-equal tiles flips.  Per round and hint ``warmup`` >= 1 untimed launches -- the first one's status
+    decides whether the shape admits the hint at all -- then three timed ones.  0 when every hint is refused."""
+    stream = _lib.stream_handle()
+    times = {}
+    for _round in range(2):
+        for hint in hints:
+            d.tile_hint = hint
+            if lib.himo_conv2d(ctypes.byref(d), stream) != 0:
+                continue                              # a variant this shape does not admit
+            for _ in range(warmup - 1):
+                lib.himo_conv2d(ctypes.byref(d), stream)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(3):
+                lib.himo_conv2d(ctypes.byref(d), stream)
+            e1.record()
+            e1.synchronize()
+            times[hint] = min(times.get(hint, float("inf")), e0.elapsed_time(e1))
+    return min(times, key=times.get) if times else 0
+
+
 class SeFlowNet:
     """``forward(pch1, pc0, pc1, pose_h1, pose0, pose1)`` -> (N0,3) float32 device tensor: the flow of every
     pc0 row INCLUDING ego motion (the h5 ``<res_name>`` dataset that save_zip.py:117 reads)."""
@@ -386,7 +410,6 @@ class SeFlowNet:
         GRU ones update state in place, so they keep the library heuristic) and remember the fastest."""
         if d.epilogue in (EPI_GRU_ZR, EPI_GRU_Q):
             return 0
-        stream = _lib.stream_handle()
         cands = [(bn << 4) | mi for bn in (128, 64) if not (bn == 128 and d.cout % 128) for mi in (2, 1)]
         if d.act_layout:                                  # split activation format: only the weights-from-L2 structures
             if d.stride == 2 and (d.act_layout & ACT_SPLIT_IN):
@@ -400,21 +423,7 @@ class SeFlowNet:
                 cands.append(0x1000 | (8 if d.cout <= 64 else 12))
         if len(cands) < 2:
             return cands[0] if cands else 0
-        times = {hint: float("inf") for hint in cands}
-        for _round in range(2):                           # two interleaved rounds, best of each candidate: the chip's clock
-            for hint in cands:                            # drifts with load, and a one-shot ranking of near-equal tiles flips
-                d.tile_hint = hint
-                for _ in range(2):
-                    self.lib.himo_conv2d(ctypes.byref(d), stream)
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                for _ in range(3):
-                    self.lib.himo_conv2d(ctypes.byref(d), stream)
-                e1.record()
-                e1.synchronize()
-                times[hint] = min(times[hint], e0.elapsed_time(e1))
-        best = min(cands, key=lambda hint: times[hint])
-        return best
+        return fastest_tile_hint(self.lib, d, cands, warmup=2)
 
     def _up(self, x, x_pitch, h, w, c, y, y_pitch, out_split=False):
         nb = self._nb

@@ -23,7 +23,7 @@ import torch
 
 from .. import _lib
 from . import spec
-from .model import ConvDesc, EPI_BIAS
+from .model import ConvDesc, EPI_BIAS, fastest_tile_hint
 
 c_p, c_i, c_l, c_f = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
 _lib.register({
@@ -817,23 +817,7 @@ class SeFlowTrainer:
                 return 0
             t.act_layout &= ~8
             t.y, t.y_batch_stride, t.y_pitch = self.TMP.data_ptr(), ho * wo * t.cout, t.cout
-        stream = _lib.stream_handle()
-        best, best_ms = 0, float("inf")
-        for _round in range(2):                       # two interleaved rounds (the clock drifts with load), best time of each variant
-            for hint in self.TILE_HINTS:
-                t.tile_hint = hint
-                if self.lib.himo_conv2d(ctypes.byref(t), stream) != 0:
-                    continue                          # a variant this shape does not admit
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                for _ in range(3):
-                    self.lib.himo_conv2d(ctypes.byref(t), stream)
-                e1.record()
-                e1.synchronize()
-                ms = e0.elapsed_time(e1)
-                if ms < best_ms:
-                    best, best_ms = hint, ms
-        return best
+        return fastest_tile_hint(self.lib, t, self.TILE_HINTS, warmup=1)
 
     def _wgrad3_batch(self, n, x, x_bs, x_pitch, h, w, cin, dy, dy_bs, dy_pitch, cout, gname, stride=1, ws=None):
         """weight gradient over n images in one launch (LDS-tiled kernel)"""

@@ -268,11 +268,31 @@ typedef struct himo_conv_desc {
     const void* w_packed;                                  /* optional: himo_conv_pack_weights[_ex] output; when set the
                                                               split-precision kernels run (stride 1, and 3x3 stride 2):
                                                               float32-class accuracy at a multiple of the float32-MFMA rate */
-    int tile_hint;                                         /* 0 = library heuristic; else (channel tile 64|128) << 4 | (1|2):
-                                                              pixel tile 64|128 of the LDS-staged-weights kernel, or
-                                                              0x1000 | (4|2): image rows per wave of the weights-from-L2
-                                                              kernel (3x3, split precision) -- for callers that time
-                                                              the variants */
+    int tile_hint;                                         /* 0 = library heuristic.  Every variant of a layer returns the same
+                                                              bits; hints exist for callers that time them.  The full table
+                                                              (csrc/conv_plan.h decides; `rows` = tile_hint & 15):
+      value                 kernel family                     meaning                                 ignored / refused
+      (64|128) << 4 | (1|2) LDS-staged weights: float32       channel tile 64|128, pixel tile         ignored (heuristic) when malformed or 128 with
+                            (no w_packed; 3x3 stride 2), or   64|128                                  cout not a multiple of 128; 3x3 stride 1 packed
+                            split precision on float32 maps                                           with packed_format 2 or a non-zero act_layout:
+                            (1x1; pins it for 3x3 stride 1)                                           HIMO_ERR_UNSUPPORTED; on 3x3 stride 2 it selects
+                                                                                                      the float32 kernel although w_packed is set
+      0x1000 | 4|2|1        weights from L2 (3x3, packed,     image rows per wave (stride 2: 2|1,     a layer this family declines (GRU epilogues, an
+                            float32 input map)                4 = heuristic)                          image of 2 GB or more): the LDS-staged kernel
+                                                                                                      with its heuristic at stride 1, else refused
+      0x1000 | 5|6          same, stride 1, packed_format     64-channel blocks forced (wide layers   packed_format 0, stride 2 or a declined layer:
+                            1|2                               too), 1|2 rows per wave                 HIMO_ERR_UNSUPPORTED
+      0x1000 | 9|10         same                              32-channel blocks, four pixel groups,   as 5|6
+                                                              1|2 rows per wave
+      0x1000 | other rows   same                              0, 3: heuristic                         rows > 4 otherwise: HIMO_ERR_UNSUPPORTED
+      rows 4|2|1            split-format input                image rows (3x3 stride 1) / 32-pixel    4 on layers of <= 64 channels becomes 2; stride 2
+      (any upper bits)      (HIMO_ACT_SPLIT_IN; 3x3 and 1x1)  segments (1x1) per wave                 has one variant per width class: ignored
+      rows 8                same, 3x3 stride 1, cout <= 64    two 32-channel column tiles per wave,   ignored (heuristic) on wider layers or when the
+                                                              8-row tiles                             output does not admit 16-byte stores
+      rows 12               same, 3x3 stride 1, cout > 64     4 rows x 64 channels per wave           ignored (heuristic) likewise
+      anything else         --                                --                                      the tile is the heuristic's, but a non-zero value
+                                                                                                      without 0x1000 still selects the family as the
+                                                                                                      first row does (packed 3x3 layers) */
     int packed_format;                                     /* format of w_packed: 0 = three bf16 planes (float32 range,
                                                               6 matrix instructions per product block), 1 = two fp16
                                                               planes, x = h + l with weights packed x 2^6 (|values| < 65504,
