@@ -30,6 +30,11 @@ SIGNATURES = {
     "himo_compdis_batch": (c_int, [c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                                    c_double, c_uint, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                    ctypes.POINTER(c_float), c_float, c_void_p, c_size_t, c_void_p]),
+    "himo_gt_body_bytes": (c_size_t, [c_int64, c_uint]),
+    "himo_gt_column_starts": (c_size_t, [c_int64, c_uint, ctypes.POINTER(c_int64)]),
+    "himo_compdis_gt_batch": (c_int, [c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                      c_double, c_uint, c_void_p, c_void_p, c_void_p, c_void_p, c_uint,
+                                      ctypes.POINTER(c_float), c_float, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "himo_compdis_frame": (c_int, [c_int64, ctypes.POINTER(c_double), ctypes.POINTER(c_double), c_void_p, c_int,
                                    c_void_p, c_void_p, c_double, c_uint, c_void_p, c_void_p, c_void_p, c_size_t,
                                    c_void_p]),
@@ -51,6 +56,7 @@ FLAG_F32_CHAIN = 0x1
 FLAG_RAW = 0x2
 FLAG_SCANIA = 0x4
 FLAG_POSE_IS_EGO = 0x8
+GT_HAS_CATEGORY, GT_HAS_INSTANCE, GT_MAX_COLUMNS = 0x1, 0x2, 10
 
 OK, ERR_INVALID_ARGUMENT, ERR_EMPTY_FRAME, ERR_WORKSPACE, ERR_SINGULAR_POSE, ERR_HIP, ERR_UNSUPPORTED = range(7)
 

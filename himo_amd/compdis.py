@@ -54,7 +54,12 @@ class FrameBatch:
     flow: torch.Tensor | None = None         # float32 [T,3]  (None => "raw")
     gm0: torch.Tensor | None = None          # uint8 [T]
     flow_is_valid: torch.Tensor | None = None
+    category: torch.Tensor | None = None     # uint8 [T]   flow_category_indices (``with_labels``)
+    instance: torch.Tensor | None = None     # int32 [T] holding the uint32 bits of flow_instance_id (``with_labels``)
+    gt_offsets_host: np.ndarray | None = None  # int64 [F+1] byte offset of every sweep's record-batch body (``with_labels``)
+    gt_offsets: torch.Tensor | None = None     # ... on the device, uploaded with the rest of the batch
     f32_chain: bool = False                  # numpy would have computed in float32 (float32 poses)
+    pose_is_ego: bool = False                # pose0 holds ego_pose = inv(pose1) @ pose0 computed by numpy (``host_ego``)
     meta: list = field(default_factory=list)  # (scene_id, timestamp) per frame
 
     @property
@@ -71,11 +76,17 @@ class FrameBatch:
         return [t[int(o[i]):int(o[i + 1])] for i in range(self.n_frames)]
 
     @classmethod
-    def from_frames(cls, frames, res_name: str | None = "seflowpp_best", device=None, with_masks: bool = False, upload=None):
+    def from_frames(cls, frames, res_name: str | None = "seflowpp_best", device=None, with_masks: bool = False, upload=None,
+                    with_labels: bool = False, host_ego: bool = False):
         """Pack reference-style frame dicts.  ``res_name`` "raw"/None => no flow (save_zip.py:117).
         A missing result key raises ``KeyError`` exactly where the reference's ``data[res_name]`` does.
         ``upload(parts, dtype) -> device tensor`` of the row-wise concatenation of ``parts`` converted to ``dtype``: optional
-        staging hook (feeder.EvalFeeder concatenates straight into pinned memory and copies on its own stream)."""
+        staging hook (feeder.EvalFeeder concatenates straight into pinned memory and copies on its own stream).
+        ``with_labels``: also ``flow_category_indices`` / ``flow_instance_id``, each when EVERY frame of the batch carries it (the
+        ground-truth writer decides per sweep whether a column exists, tools/test/save_zip_gt.py:172-173: it packs one batch per schema).
+        ``host_ego``: ``ego_pose = inv(pose1) @ pose0`` of every frame comes from numpy in the poses' own dtype -- the very expression of
+        save_zip.py:115, so the 4x4 bits are the reference's and a singular pose raises numpy's ``LinAlgError`` -- instead of the library's
+        float64 LU (within 1 ulp of it in the results; ``run_frame`` has the same switch)."""
         dev = device if device is not None else _lib.require_gpu()
         to_dev = upload if upload is not None else host_upload(dev)
         frames = list(frames)
@@ -96,10 +107,15 @@ class FrameBatch:
                 parts.append(a)
             return to_dev(parts, dtype)
 
-        pose_dtypes = {np.asarray(f[k]).dtype for f in frames for k in ("pose0", "pose1")}
-        f32_chain = all(dt == np.float32 for dt in pose_dtypes)
-        pose0 = to_dev([np.stack([np.asarray(f["pose0"], dtype=np.float64) for f in frames])], np.float64)
-        pose1 = to_dev([np.stack([np.asarray(f["pose1"], dtype=np.float64) for f in frames])], np.float64)
+        if host_ego:
+            egos = [np.linalg.inv(np.asarray(f["pose1"])) @ np.asarray(f["pose0"]) for f in frames]      # save_zip.py:115
+            f32_chain = all(e.dtype == np.float32 for e in egos)
+            pose0 = pose1 = to_dev([np.stack([e.astype(np.float64) for e in egos])], np.float64)
+        else:
+            pose_dtypes = {np.asarray(f[k]).dtype for f in frames for k in ("pose0", "pose1")}
+            f32_chain = all(dt == np.float32 for dt in pose_dtypes)
+            pose0 = to_dev([np.stack([np.asarray(f["pose0"], dtype=np.float64) for f in frames])], np.float64)
+            pose1 = to_dev([np.stack([np.asarray(f["pose1"], dtype=np.float64) for f in frames])], np.float64)
         b = cls(
             offsets_host=offsets,
             offsets=to_dev([offsets], np.int64),
@@ -107,14 +123,31 @@ class FrameBatch:
             pc0=cat("pc0", np.float32, stride),
             lidar_dt=cat("lidar_dt", np.float32),
             flow=None if raw else cat(res_name, np.float32, 3),
-            f32_chain=f32_chain,
+            f32_chain=f32_chain, pose_is_ego=host_ego,
             meta=[(f.get("scene_id"), f.get("timestamp")) for f in frames],
         )
         if with_masks:
             b.gm0 = cat("gm0", np.uint8)
             if all("flow_is_valid" in f for f in frames):
                 b.flow_is_valid = cat("flow_is_valid", np.uint8)
+        if with_labels:
+            if all("flow_category_indices" in f for f in frames):
+                b.category = cat("flow_category_indices", np.uint8)
+            if all("flow_instance_id" in f for f in frames):
+                b.instance = cat("flow_instance_id", np.int32)             # (the uint32 column's bits: ``astype(np.uint32)`` wraps alike)
+            from . import feather
+            b.gt_offsets_host = gt_body_offsets(offsets, feather.gt_schema(b.category is not None, b.instance is not None)[1])
+            b.gt_offsets = to_dev([b.gt_offsets_host], np.int64)            # rides in the batch's one upload: no copy at launch time
         return b
+
+
+def gt_body_offsets(offsets_host, dtypes) -> np.ndarray:
+    """int64 [F+1]: where each sweep's record batch body starts in a batch's body buffer (bytes; bodies are multiples of 8)"""
+    from . import feather
+    out = np.zeros(len(offsets_host), dtype=np.int64)
+    for k in range(len(offsets_host) - 1):
+        out[k + 1] = out[k] + feather.body_layout(dtypes, int(offsets_host[k + 1] - offsets_host[k]))[0]
+    return out
 
 
 class CompDisEngine:
@@ -149,6 +182,7 @@ class CompDisEngine:
             if rf is None:
                 rf = out["refined"] = torch.empty((T, 3), dtype=torch.float32, device=self.device)
         flags = (_lib.FLAG_F32_CHAIN if b.f32_chain else 0) | (_lib.FLAG_RAW if b.flow is None else 0)
+        flags |= _lib.FLAG_POSE_IS_EGO if b.pose_is_ego else 0
         mask = valid = bounds = None
         if data_name is not None:
             if b.gm0 is None:
@@ -170,6 +204,42 @@ class CompDisEngine:
             self._ws.numel(), _lib.stream_handle())
         _lib.check(st, "himo_compdis_batch")
         return out
+
+    def run_gt(self, batch: FrameBatch, data_name: str, sensor_dt: float = 0.1):
+        """The batch's ground-truth sweeps (tools/test/save_zip_gt.py:143-178; ``batch.flow`` is the frames' ``flow``) as Arrow record
+        batch BODIES: ``(body, body_offsets, (names, dtypes))`` -- ``body`` a uint8 device tensor, sweep ``k``'s bytes at
+        ``body_offsets[k]:body_offsets[k + 1]`` (host int64), laid out as ``feather.framing(names, dtypes, rows)`` says, so that its file
+        is ``head + body + tail``.  The label columns exist when the batch carries them.  Asynchronous on the current stream."""
+        from . import feather
+        b = batch
+        if b.flow is None:
+            raise KeyError("flow")                                     # save_zip_gt.py:167
+        if b.gm0 is None:
+            raise KeyError("gm0")                                      # save_zip_gt.py:148
+        self._reserve(b.n_frames)
+        names, dtypes = feather.gt_schema(b.category is not None, b.instance is not None)
+        columns = (_lib.GT_HAS_CATEGORY if b.category is not None else 0) | (_lib.GT_HAS_INSTANCE if b.instance is not None else 0)
+        if b.gt_offsets is None:                                       # a batch packed without ``with_labels``
+            b.gt_offsets_host = gt_body_offsets(b.offsets_host, dtypes)
+            b.gt_offsets = torch.from_numpy(b.gt_offsets_host).to(self.device)
+        body_offsets, d_body_offsets = b.gt_offsets_host, b.gt_offsets
+        body = torch.empty(max(int(body_offsets[-1]), 8), dtype=torch.uint8, device=self.device)
+        flags = (_lib.FLAG_F32_CHAIN if b.f32_chain else 0) | (_lib.FLAG_POSE_IS_EGO if b.pose_is_ego else 0)
+        valid = None
+        lo, hi = EGO_BOX["scania" if data_name == "scania" else "av2"]
+        bounds = (ctypes.c_float * 6)(*[float(v) for v in lo + hi])
+        if data_name == "scania":
+            if b.flow_is_valid is None:
+                raise KeyError("flow_is_valid")                        # save_zip_gt.py:152
+            flags |= _lib.FLAG_SCANIA
+            valid = b.flow_is_valid
+        st = self.lib.himo_compdis_gt_batch(
+            b.n_frames, b.total_points, _lib.ptr(b.offsets), _lib.ptr(b.pose0), _lib.ptr(b.pose1), _lib.ptr(b.pc0), b.pc0.shape[1],
+            _lib.ptr(b.flow), _lib.ptr(b.lidar_dt), float(sensor_dt), flags, _lib.ptr(b.gm0), _lib.ptr(valid), _lib.ptr(b.category),
+            _lib.ptr(b.instance), columns, bounds, float(CLOSE_DISTANCE_THRESHOLD), _lib.ptr(d_body_offsets), _lib.ptr(body),
+            _lib.ptr(self._ws), self._ws.numel(), _lib.stream_handle())
+        _lib.check(st, "himo_compdis_gt_batch")
+        return body[:int(body_offsets[-1])], body_offsets, (names, dtypes)
 
     def run_frame(self, pc0: torch.Tensor, flow: torch.Tensor | None, lidar_dt: torch.Tensor, pose0, pose1,
                   sensor_dt: float = 0.1, refined: bool = False, host_ego: bool = True):

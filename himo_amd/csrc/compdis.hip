@@ -195,10 +195,7 @@ struct CompdisArgs {
 };
 
 __device__ inline uint8_t mask_math(const CompdisArgs& a, float px, float py, float pz, uint8_t gm, uint8_t valid) {
-    const float d = sqrtf(px * px + py * py);                        // eval.py:288 (float32 norm)
-    const bool inside = (px > a.bmin[0]) & (px < a.bmax[0]) & (py > a.bmin[1]) & (py < a.bmax[1]) &
-                        (pz > a.bmin[2]) & (pz < a.bmax[2]);         // utils/__init__.py:31-33
-    return (uint8_t)((d <= a.close_distance) & (gm == 0) & (!inside) & (valid != 0));   // eval.py:289-296
+    return eval_mask_point(a.bmin, a.bmax, a.close_distance, px, py, pz, gm, valid);
 }
 
 template <bool F32>

@@ -56,15 +56,19 @@ __device__ inline XfRegs load_xf(const FrameXf* __restrict__ xf, const unsigned*
     return x;
 }
 
-template <bool F32>
+// NORM: also the per-point norm of the ego-compensated flow, tools/test/save_zip_gt.py:169 --
+// np.linalg.norm(axis=1) is sqrt((x*x + y*y) + z*z) in the chain's dtype, then astype(float32)
+template <bool F32, bool NORM = false>
 __device__ inline void point_math(const XfRegs& x, float px, float py, float pz, float fx, float fy, float fz,
-                                  float dt, double sensor_dt, bool raw, float* cd, float* rf) {
+                                  float dt, double sensor_dt, bool raw, float* cd, float* rf, float* nrm = nullptr,
+                                  bool single_row = false) {
     const float dt0 = x.fmax - dt;                                   // save_zip.py:120 (float32)
     if (F32) {
         const float r[9] = {(float)x.R[0], (float)x.R[1], (float)x.R[2], (float)x.R[3], (float)x.R[4],
                             (float)x.R[5], (float)x.R[6], (float)x.R[7], (float)x.R[8]};
         const float sdt = (float)sensor_dt;
         const float p[3] = {px, py, pz}, fl[3] = {fx, fy, fz};
+        float e[3];
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             const float pf = (fmaf(pz, r[c * 3 + 2], fmaf(py, r[c * 3 + 1], px * r[c * 3])) + (float)x.t[c]) - p[c];
@@ -72,19 +76,39 @@ __device__ inline void point_math(const XfRegs& x, float px, float py, float pz,
             const float v = est / sdt * dt0;                         // utils/__init__.py:43
             cd[c] = v;
             rf[c] = p[c] + v;                                        // utils/__init__.py:46
+            e[c] = est;
         }
+        if (NORM) *nrm = sqrtf((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
     } else {
         const double p[3] = {(double)px, (double)py, (double)pz}, fl[3] = {(double)fx, (double)fy, (double)fz};
+        double e[3];
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            // save_zip.py:116 -- dgemm accumulates k-ordered fused multiply-adds
-            const double pf = (fma(p[2], x.R[c * 3 + 2], fma(p[1], x.R[c * 3 + 1], p[0] * x.R[c * 3])) + x.t[c]) - p[c];
+            // save_zip.py:116 -- dgemm accumulates k-ordered fused multiply-adds.  A sweep of ONE row is a vector-matrix product, which
+            // numpy hands to dgemv: the OpenBLAS build numpy 2.2 ships takes k = 1 first, then 0, then 2 (``single_row``; measured
+            // against numpy, no reference-written sweep has one row).  LIMITS: only compdis_gt_kernel passes it (compdis_kernel keeps
+            // the k-ordered chain for every sweep, as pinned by its tests), and the float32 chain above has no counterpart -- sgemv's
+            // accumulation for one row was not identified, so a one-row sweep with float32 poses may differ from numpy in the last bit.
+            const double dot = single_row ? fma(p[2], x.R[c * 3 + 2], fma(p[0], x.R[c * 3], p[1] * x.R[c * 3 + 1]))
+                                          : fma(p[2], x.R[c * 3 + 2], fma(p[1], x.R[c * 3 + 1], p[0] * x.R[c * 3]));
+            const double pf = (dot + x.t[c]) - p[c];
             const double est = raw ? 0.0 : fl[c] - pf;               // save_zip.py:117
             const double v = est / sensor_dt * (double)dt0;          // utils/__init__.py:43
             cd[c] = (float)v;                                        // save_zip.py:70-72
             rf[c] = (float)(p[c] + v);                               // utils/__init__.py:46
+            e[c] = est;
         }
+        if (NORM) *nrm = (float)sqrt((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
     }
+}
+
+// evaluation mask of one point (eval.py:288-296): bmin / bmax = the open ego box, valid = flow_is_valid (1 where not used)
+__device__ inline uint8_t eval_mask_point(const float* bmin, const float* bmax, float close_distance, float px, float py,
+                                          float pz, uint8_t gm, uint8_t valid) {
+    const float d = sqrtf(px * px + py * py);                        // eval.py:288 (float32 norm)
+    const bool inside = (px > bmin[0]) & (px < bmax[0]) & (py > bmin[1]) & (py < bmax[1]) &
+                        (pz > bmin[2]) & (pz < bmax[2]);             // utils/__init__.py:31-33
+    return (uint8_t)((d <= close_distance) & (gm == 0) & (!inside) & (valid != 0));   // eval.py:289-296
 }
 
 

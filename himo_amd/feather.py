@@ -293,6 +293,40 @@ def _message(header_type: int, build_header, body_len: int) -> bytes:
 
 _FRAMING_CACHE: dict = {}
 
+# the columns of a ground-truth sweep file in file order (tools/test/save_zip_gt.py:89-105); the two label columns are written
+# only for sweeps that carry them.  The ONE place the schema lives: the kernel launcher (compdis.CompDisEngine.run_gt) places
+# the sweeps' bodies with it, save_zip_gt frames and encodes the files with it.
+GT_COLUMNS = (("comp_dis_x_m", np.float32), ("comp_dis_y_m", np.float32), ("comp_dis_z_m", np.float32), ("eval_mask", np.uint8),
+              ("flow_category_indices", np.uint8), ("flow_instance_id", np.uint32), ("gt_flow_norm", np.float32),
+              ("pc0_x", np.float32), ("pc0_y", np.float32), ("pc0_z", np.float32))
+
+
+def gt_schema(category: bool = True, instance: bool = True):
+    """(names, dtypes) of a ground-truth sweep file with / without its label columns"""
+    cols = [(n, np.dtype(d)) for n, d in GT_COLUMNS
+            if (category or n != "flow_category_indices") and (instance or n != "flow_instance_id")]
+    return tuple(n for n, _ in cols), tuple(d for _, d in cols)
+
+
+def body_layout(dtypes, length: int):
+    """(body length, [(offset, nbytes) of each column's data]) of a record batch of ``length`` rows of fixed-width columns:
+    the columns one after the other, each padded to a multiple of 8 bytes, no validity buffers"""
+    spans, at = [], 0
+    for dt in dtypes:
+        dt = np.dtype(dt)
+        nbytes = (length + 7) // 8 if dt == np.dtype(bool) else length * dt.itemsize
+        spans.append((at, nbytes))
+        at += nbytes + (-nbytes) % 8
+    return at, spans
+
+
+def framing(names, dtypes, length: int):
+    """``(head, tail, body length, spans)``: a Feather file of ``length`` rows of the fixed-width columns ``names`` / ``dtypes`` is
+    ``head + body + tail`` where ``body`` holds column ``k`` at ``spans[k] = (offset, nbytes)``, zero bytes between the columns
+    (``body_layout``).  ``head`` and ``tail`` depend on the schema and the row count alone and are cached, so a producer that
+    lays a body out itself (the ground-truth kernel does, on the device) writes a file without touching the values."""
+    return _framing(tuple(names), tuple(np.dtype(d) for d in dtypes), int(length))
+
 
 def _framing(names: tuple, dtypes: tuple, length: int):
     """(bytes before the record batch body, bytes after it, body length, [(offset, nbytes) of each column's data in the body]) of
@@ -302,16 +336,12 @@ def _framing(names: tuple, dtypes: tuple, length: int):
     got = _FRAMING_CACHE.get(key)
     if got is not None:
         return got
-    buffers, nodes, spans, at = [], [], [], 0
-    for dt in dtypes:
-        dt = np.dtype(dt)
+    body_len, spans = body_layout(dtypes, length)
+    buffers, nodes = [], []
+    for at, nbytes in spans:
         nodes.append((length, 0))
         buffers.append((at, 0))                               # validity bitmap: absent (no nulls)
-        nbytes = (length + 7) // 8 if dt == np.dtype(bool) else length * dt.itemsize
         buffers.append((at, nbytes))
-        spans.append((at, nbytes))
-        at += nbytes + (-nbytes) % 8
-    body_len = at
     head = bytearray(MAGIC + b"\x00\x00")
     head += _message(1, lambda b: _schema(b, names, dtypes), 0)
 

@@ -121,6 +121,44 @@ int himo_compdis_frame(int64_t n_points, const double* h_pose0, const double* h_
                        void* d_workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Ground-truth sweeps (tools/test/save_zip_gt.py:141-178): the same chain with est_flow = `flow` - pose_flow, written as
+ * the BODY of one Arrow record batch per sweep -- the sweep's Feather file is head + body + tail with the framing a function
+ * of the schema and the row count alone.  Columns, in file order, each starting at a multiple of 8 bytes with zero pad bytes
+ * and no validity buffers:
+ *     comp_dis_x_m, comp_dis_y_m, comp_dis_z_m  float32     gt_flow / sensor_dt * dt0
+ *     eval_mask                                 uint8       as himo_compdis_batch
+ *     flow_category_indices                     uint8       copied   (HIMO_GT_HAS_CATEGORY)
+ *     flow_instance_id                          uint32      copied   (HIMO_GT_HAS_INSTANCE)
+ *     gt_flow_norm                              float32     ||gt_flow||_2 in the chain's dtype, rounded once
+ *     pc0_x, pc0_y, pc0_z                       float32     copied
+ * `columns` = HIMO_GT_HAS_* bits: a column without its bit is absent from the layout (its pointer may be NULL).
+ */
+#define HIMO_GT_HAS_CATEGORY 0x1u
+#define HIMO_GT_HAS_INSTANCE 0x2u
+#define HIMO_GT_MAX_COLUMNS 10
+
+/* bytes of one sweep's body (a multiple of 8; 0 for an empty sweep) */
+size_t himo_gt_body_bytes(int64_t n_points, unsigned columns);
+/* h_starts[HIMO_GT_MAX_COLUMNS]: byte offset of every column inside the body in the order above, -1 for an absent one
+ * (host arithmetic only: the function the kernel places its stores with); returns the body's bytes */
+size_t himo_gt_column_starts(int64_t n_points, unsigned columns, int64_t* h_starts);
+
+/* d_body_offsets int64[n_frames+1]: byte offset of every sweep's body in d_body, each a multiple of 8, with
+ * offsets[f+1] - offsets[f] >= himo_gt_body_bytes(points of f, columns); d_body 8-byte aligned.  Every byte of a sweep's
+ * body is written.  d_category uint8[T] / d_instance uint32[T] are read when their HIMO_GT_HAS_* bit is set.  flags:
+ * F32_CHAIN, SCANIA, POSE_IS_EGO as in himo_compdis_batch (RAW is refused: the ground truth needs `flow`).  Workspace as
+ * himo_compdis_workspace_bytes(n_frames). */
+int himo_compdis_gt_batch(int n_frames, int64_t total_points,
+                          const int64_t* d_offsets, const double* d_pose0, const double* d_pose1,
+                          const float* d_pc0, int pc_stride, const float* d_flow, const float* d_lidar_dt,
+                          double sensor_dt, unsigned flags,
+                          const uint8_t* d_gm0, const uint8_t* d_flow_is_valid,
+                          const uint8_t* d_category, const uint32_t* d_instance, unsigned columns,
+                          const float* h_mask_bounds, float close_distance,
+                          const int64_t* d_body_offsets, uint8_t* d_body,
+                          void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The three functions of utils/__init__.py as stand-alone element-wise operators.
  * `dtype_is_f64` selects float64 flow/out arrays (numpy's result for float64 poses).
  */
