@@ -221,13 +221,14 @@ def rms(a):
     return float(a.pow(2).mean().sqrt()) if a.numel() else 0.0
 
 
-def check(got, ref, bnd, ref32=None, arith="f32", case="", floor=None):
+def check(got, ref, bnd, ref32=None, arith="f32", case="", floor=None, limit=None):
     """Worst err / bound and a readable report.
 
     got, ref, bnd: [..., H, W, C] (NHWC; ref float64).  ref32: the same operation in float32 (CPU torch) or None.
     Returns (worst, rms_ratio, report); the caller asserts worst <= 1 and rms_ratio <= R[arith]
     (``ok(...)`` does both).  rms_ratio = rms(got - ref) / (rms(ref32 - ref) + floor), floor = 2^-24 rms(ref) unless
-    given (a case whose float32 reference happens to be exact must not divide by zero)."""
+    given (a case whose float32 reference happens to be exact must not divide by zero).  ``limit``: the aggregate limit of
+    an arithmetic R does not list (oracle/grad_oracle.py)."""
     got = torch.as_tensor(got).double()
     ref = torch.as_tensor(ref).double()
     bnd = torch.as_tensor(bnd).double()
@@ -241,7 +242,7 @@ def check(got, ref, bnd, ref32=None, arith="f32", case="", floor=None):
         fl = U * rms(ref) if floor is None else floor
         denom = rms(torch.as_tensor(ref32).double() - ref) + fl
         rr = rms(torch.where(torch.isinf(err), torch.full_like(err, 1e30), err)) / denom if denom > 0 else 0.0
-    report = f"{case} [{arith}]: worst err/bound {worst:.3g}, rms ratio {rr:.3g} (R {R[arith]:g})"
+    report = f"{case} [{arith}]: worst err/bound {worst:.3g}, rms ratio {rr:.3g} (R {R[arith] if limit is None else limit:g})"
     if ratio.numel() and worst > 0:
         idx = np.unravel_index(int(torch.argmax(ratio)), tuple(ratio.shape))
         where = []
@@ -259,9 +260,9 @@ def check(got, ref, bnd, ref32=None, arith="f32", case="", floor=None):
     return worst, rr, report
 
 
-def ok(got, ref, bnd, ref32=None, arith="f32", case="", floor=None):
+def ok(got, ref, bnd, ref32=None, arith="f32", case="", floor=None, limit=None):
     """check(...) and assert both levels; returns (worst, rms_ratio) for the caller's record."""
-    worst, rr, report = check(got, ref, bnd, ref32, arith, case, floor)
+    worst, rr, report = check(got, ref, bnd, ref32, arith, case, floor, limit)
     assert worst <= 1.0, report
-    assert rr <= R[arith], report
+    assert rr <= (R[arith] if limit is None else limit), report
     return worst, rr

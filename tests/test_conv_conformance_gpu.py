@@ -16,11 +16,11 @@ import torch
 import torch.nn.functional as F
 
 import conv_oracle as co
+import grad_oracle as go
+from guarded import GUARD, NAN_BITS, Guarded, layout
 
 pytestmark = pytest.mark.gpu
 
-NAN_BITS = 0x7FC0BEEF                 # a quiet NaN with a payload no kernel produces
-GUARD = 1 << 16                       # floats of guard on each side of an operand
 HINTS = (0, 0x41, 0x42, 0x81, 0x82, 0x1001, 0x1002, 0x1004, 0x1005, 0x1006, 0x1008, 0x1009, 0x100A, 0x100C)
 PACK = {"bf16x3": 0, "f16x2": 1, "bf16x2": 2}
 
@@ -64,47 +64,6 @@ def _note(arith, worst, rr, case=""):
     s[2] += 1
 
 
-def layout(n_img, n_inner, bs, outer, pixels, pitch, c):
-    """Flat float offsets [n_img, pixels, c] of image i at (i % n_inner) * bs + (i // n_inner) * outer."""
-    i = torch.arange(n_img, dtype=torch.int64)
-    base = (i % n_inner) * bs + (i // n_inner) * outer
-    return base[:, None, None] + torch.arange(pixels, dtype=torch.int64)[None, :, None] * pitch + torch.arange(c)[None, None, :]
-
-
-class Guarded:
-    """An operand at flat offsets ``idx`` (+ ``off`` floats) inside a NaN-filled buffer with guards on both sides."""
-
-    def __init__(self, idx, device, off=0):
-        self.shape = idx.shape
-        span = int(idx.max()) + 1 if idx.numel() else 1
-        self.base = GUARD + off
-        self.buf = torch.full((self.base + span + GUARD,), NAN_BITS, dtype=torch.int32, device=device)
-        self.idx = (idx.reshape(-1) + self.base).to(device)
-        self.outside = torch.ones(self.buf.numel(), dtype=torch.bool, device=device)
-        self.outside[self.idx] = False
-
-    @property
-    def ptr(self):
-        return self.buf.data_ptr() + 4 * self.base
-
-    def put(self, values):
-        """float32 values, or int32 words (the split activation format)"""
-        v = values.reshape(-1).to(self.buf.device)
-        self.buf[self.idx] = v.view(torch.int32) if v.dtype == torch.float32 else v
-
-    def words(self):
-        return self.buf[self.idx].reshape(self.shape).cpu()
-
-    def get(self):
-        return self.words().view(torch.float32)
-
-    def untouched_outside(self):
-        return bool(torch.all(self.buf[self.outside] == NAN_BITS))
-
-    def reset(self):
-        self.buf.fill_(NAN_BITS)
-
-
 def split_encode(x):
     """float32 [..., C] (C % 16 == 0) -> (int32 words of the split activation format, float64 value h + l)"""
     h = x.half()
@@ -126,7 +85,10 @@ def conv_case(lib, gpu, arith, n, H, W, cin, cout, k=3, stride=1, epi=0, *, x_pi
 
     groups: the "frames as channel groups" layout -- image i of a sample at channel offset i * cin of an (n * cin)-wide
     pixel, samples one map apart (n_outer of them).  Otherwise images are x_gap / y_gap floats apart beyond their map, and
-    samples (n_outer > 1) outer_gap floats beyond n images."""
+    samples (n_outer > 1) outer_gap floats beyond n images.
+    act & 8 (HIMO_ACT_ACCUMULATE): y holds a non-zero map before the call and must hold map + result after it.
+    act & 16 (HIMO_ACT_STUFFED_2X): the operand is a compact [H / 2][W / 2] map (pitches, gaps and strides describe it) and the
+    result is checked against the float64 adjoint of the stride-2 convolution (grad_oracle.conv3x3_dx)."""
     case = f"{arith} n={n} H={H} W={W} cin={cin} cout={cout} k={k} s={stride} epi={epi} xp={x_pitch} yp={y_pitch} " \
            f"gap={x_gap},{y_gap} off={y_off} outer={n_outer},{outer_gap} groups={groups} act={act}"
     g = torch.Generator().manual_seed(seed)
@@ -142,11 +104,22 @@ def conv_case(lib, gpu, arith, n, H, W, cin, cout, k=3, stride=1, epi=0, *, x_pi
         x_os, y_os = n * x_bs + outer_gap, n * y_bs + outer_gap
     y_cols = cout // 2 if epi == 3 else cout
     x = torch.randn(N, H, W, cin, generator=g) * x_scale
+    accumulate, stuffed = bool(act & 8), bool(act & 16)
+    x_pixels = H * W
+    if stuffed:
+        xc = torch.randn(N, H // 2, W // 2, cin, generator=g) * x_scale
+        x = go.zero_stuff2x(xc)
+        x_pixels = (H // 2) * (W // 2)
+        if not groups:
+            x_bs = x_pixels * x_pitch + x_gap
+            x_os = n * x_bs + outer_gap
     w = torch.randn(k, k, cin, cout, generator=g) / np.sqrt(k * k * cin)
     b = torch.randn(cout, generator=g) * 0.1 if (bias and epi != 6) else None
     sc, sh = torch.rand(cout, generator=g) + 0.5, torch.randn(cout, generator=g) * 0.1
-    xg = Guarded(layout(N, n, x_bs, x_os, H * W, x_pitch, cin), gpu)
-    if act & 1:
+    xg = Guarded(layout(N, n, x_bs, x_os, x_pixels, x_pitch, cin), gpu)
+    if stuffed:
+        xg.put(xc)
+    elif act & 1:
         words, x64 = split_encode(x)
         xg.put(words)
         x = x64.float()              # exact: the value the kernel reads
@@ -188,10 +161,23 @@ def conv_case(lib, gpu, arith, n, H, W, cin, cout, k=3, stride=1, epi=0, *, x_pi
     ref = co.conv_ref(x, w, b, stride, epi, sc, sh, aux_in, aux_out)
     ref32 = co.conv_ref(x, w, b, stride, epi, sc, sh, aux_in, aux_out, dtype=torch.float32)
     bnd = co.bound(arith, x, w, b, stride, epi, sc, sh, aux_in, aux_out, ref=ref, split_out=bool(act & 2))
+    if stuffed and k == 3 and stride == 1 and epi == 0 and not (H & 1 or W & 1):
+        # the same thing said independently: dX of a stride-2 convolution whose weights are these with taps and channels swapped back
+        adj = go.conv3x3_dx(xc, w.flip(0, 1).permute(0, 1, 3, 2), 2, H, W) + (0 if b is None else b.double())
+        assert torch.allclose(adj, ref["y"], rtol=1e-12, atol=1e-12), f"{case}: the two float64 references disagree"
+    y0 = None
+    if accumulate and ref["y"] is not None:
+        y0 = torch.randn(N, Ho, Wo, y_cols, generator=g)
+        ref["y"] = ref["y"] + y0.double()
+        ref32["y"] = ref32["y"] + y0
+        bnd["y"] = bnd["y"] + co.U * (y0.double().abs() + ref["y"].abs())       # one more rounding, of old + new
     x_before = xg.buf.clone()
     results = []
     for hint in hints:
         yg.reset()
+        if y0 is not None:
+            yg.put(y0)
+        y_before = yg.buf.clone()
         if ag_out is not None:
             ag_out.reset()
             if epi == 4:
@@ -202,7 +188,7 @@ def conv_case(lib, gpu, arith, n, H, W, cin, cout, k=3, stride=1, epi=0, *, x_pi
         if st != 0:
             assert not expect_ok or hint != 0, f"{case}: refused (status {st})"
             FALLBACKS.append((case, hint, st))
-            assert yg.untouched_outside() and bool(torch.all(yg.buf == NAN_BITS)), f"{case} hint {hint:#x}: refused but wrote"
+            assert yg.untouched_outside() and torch.equal(yg.buf, y_before), f"{case} hint {hint:#x}: refused but wrote"
             continue
         assert expect_ok, f"{case}: accepted a descriptor it should refuse"
         tag = f"{case} hint={hint:#x}"
@@ -329,6 +315,37 @@ def test_conv2d_nhwc_caller(gpu, arith):
         worst, rr = co.ok(got, ref["y"], bnd["y"], co.conv_ref(x, w, b, s, dtype=torch.float32)["y"], arith,
                           f"conv2d_nhwc {arith} {(n, H, W, ci, co_, k, s)}")
         _note(arith, worst, rr, f"conv2d_nhwc {(n, H, W, ci, co_, k, s)}")
+
+
+def test_data_gradient_forms(lib, gpu):
+    """HIMO_ACT_ACCUMULATE (3x3 stride 1 in the two-term bf16 split; row GEMMs of either bf16 split) onto a non-zero map, and
+    HIMO_ACT_STUFFED_2X alone and with accumulate against the float64 adjoint of the stride-2 convolution: ragged shapes,
+    compact maps with h or w = 1, pitches and gaps, every hint; the combinations the header rules out are refused."""
+    for i, (n, H, W, ci, co_) in enumerate(S1_SHAPES):
+        kw = dict(x_pitch=ci + 12, y_pitch=co_ + 8, x_gap=20, y_gap=12) if i % 2 else {}
+        conv_case(lib, gpu, "bf16x2", n, H, W, ci, co_, act=8, seed=700 + i, **kw)
+    i = 0
+    for arith in ("bf16x3", "bf16x2"):
+        for rows in (1, 33, 4097):
+            for ci, co_ in GEMM_CH:
+                kw = dict(x_pitch=ci + 4, y_pitch=co_ + 12) if i % 2 else {}
+                conv_case(lib, gpu, arith, 1, 1, rows, ci, co_, k=1, act=8, seed=720 + i, **kw)
+                i += 1
+    for i, (n, hc, wc, ci, co_) in enumerate([(1, 1, 1, 16, 32), (2, 1, 19, 32, 64), (1, 17, 1, 16, 32), (2, 5, 7, 20, 36),
+                                              (1, 9, 33, 64, 100), (1, 16, 16, 132, 36)]):
+        for act in (16, 24):
+            kw = dict(x_pitch=ci + 8, y_pitch=co_ + 4, x_gap=12, y_gap=20) if i % 2 else {}
+            assert conv_case(lib, gpu, "bf16x2", n, 2 * hc, 2 * wc, ci, co_, act=act, hints=HINTS, seed=760 + 2 * i + act // 16, **kw)
+    for act in (8, 16, 24):                                   # what the header rules out
+        conv_case(lib, gpu, "f16x2", 1, 6, 8, 16, 32, act=act, expect_ok=False)
+        conv_case(lib, gpu, "f32", 1, 6, 8, 16, 32, act=act, expect_ok=False)
+        conv_case(lib, gpu, "bf16x2", 1, 6, 8, 16, 32, act=act, stride=2, expect_ok=False)
+        conv_case(lib, gpu, "bf16x2", 1, 6, 8, 16, 32, act=act, epi=5, expect_ok=False)
+    conv_case(lib, gpu, "bf16x3", 1, 6, 8, 16, 32, act=8, expect_ok=False)              # 3x3 accumulate: the two-term split only
+    conv_case(lib, gpu, "bf16x3", 1, 6, 8, 16, 32, act=16, expect_ok=False)
+    conv_case(lib, gpu, "f16x2", 1, 1, 33, 16, 32, k=1, act=8, expect_ok=False)         # row GEMM accumulate: the bf16 splits only
+    conv_case(lib, gpu, "bf16x2", 1, 1, 33, 16, 32, k=1, act=8, epi=5, expect_ok=False)
+    conv_case(lib, gpu, "bf16x2", 1, 2, 34, 16, 32, k=1, act=16, expect_ok=False)       # stuffed: 3x3 only
 
 
 def test_split_activation_format(lib, gpu):
