@@ -121,6 +121,13 @@ def load_index(directory, eval: bool = False) -> list:  # noqa: A002
 SAVE_FIELDS = ("pc0", "pose0", "lidar_dt", "pose1", "pc1")
 
 
+# what the segmentation evaluator reads beside its result names (downstream/eval_seg.py:219): labels and the mask, no points, no poses
+SEG_FIELDS = ("flow_category_indices", "seg_valid")
+
+# frame keys the loader derives itself (renamed datasets, the successor sweep's): never looked up in a group under these names
+_LOADER_KEYS = frozenset(("scene_id", "timestamp", "pc0", "pose0", "pose1", "pc1", "gm0", "gm1", "lidar_dt", "flow_instance_id_next"))
+
+
 # ... and the ones the evaluator reads (eval.py:282-310: the sweep, its poses and time stamps, the ground truth, the masks and ids -- not
 # the next sweep's points); the estimate's key (``res_name``) joins them
 EVAL_FIELDS = ("pc0", "pose0", "pose1", "lidar_dt", "gm0", "flow", "flow_is_valid", "flow_category_indices", "flow_instance_id")
@@ -200,12 +207,17 @@ class HDF5Dataset:
     ground-truth flow are then not touched).  ``zero_copy``: arrays the file stores as one plain run come back as READ-ONLY
     views of the file mapping (``h5lite`` only; consumers that stage frames into their own buffers, like
     ``feeder.SampleFeeder``, then copy each sweep once instead of twice).
-    ``allow_dropped_eval`` (default: env ``HIMO_ALLOW_DROPPED_EVAL``, else False): see the KeyError below."""
+    A name in ``fields`` that is none of the loader's own keys is served from the dataset of that name in the sweep's group when
+    there is one, with its on-disk dtype (``seg_valid``, the segmentation results of downstream/eval_seg.py:219).
+    ``allow_dropped_eval`` (default: env ``HIMO_ALLOW_DROPPED_EVAL``, else False): see the KeyError below.
+    ``need_next=False``: for consumers that read a sweep alone (no ``pose1`` / ``pc1``): every index entry stays, the last sweep
+    of a scene included, and asking such an item for a successor's key is a KeyError."""
 
     carries_next = True        # every item holds its successor's ``pc1`` / ``pose1``: a walk never reads item i + 1 for them
 
     def __init__(self, directory, vis_name="", eval: bool = False, n_frames: int = 2, opener=None,  # noqa: A002
-                 allow_dropped_eval: bool | None = None, fields=None, zero_copy: bool = False, keep_open: int = 8):
+                 allow_dropped_eval: bool | None = None, fields=None, zero_copy: bool = False, keep_open: int = 8,
+                 need_next: bool = True):
         self._files = _OpenFiles(opener if opener is not None else _open_h5, keep=keep_open)
         # reader PROCESSES (feeder.ReaderPool) may inherit this object through fork(): h5lite holds a read-only file mapping and
         # nothing else; libhdf5's global state under h5py does not survive a fork with files open
@@ -223,6 +235,9 @@ class HDF5Dataset:
             if s0 == s1:
                 self._next[(s0, t0)] = t1
         wanted = load_index(self.directory, eval=eval)
+        if not need_next:
+            self.index, self.dropped = [[s, t] for s, t in wanted], []
+            return
         self.index = [[s, t] for s, t in wanted if (s, t) in self._next]
         # Entries without a successor sweep cannot be processed (no pose1: save_zip.py:115 / eval.py:284).  The last sweep
         # of every scene in index_total.pkl is such an entry and is dropped with a note; an entry of the EVAL list is a
@@ -327,6 +342,10 @@ class HDF5Dataset:
                         d[name] = self._array(r[ts][name])
                 if name not in d and name in g:
                     d[name] = self._array(g[name])
+        if want is not None:                                   # any other dataset of the sweep's group, asked for by its own name
+            for k in sorted(want - _LOADER_KEYS):
+                if k not in d and k in g:
+                    d[k] = self._array(g[k])
         if not any(need(k) for k in ("pose1", "pc1", "gm1", "flow_instance_id_next")):
             return d
         nxt = f[self._next[(scene_id, ts)]]

@@ -238,6 +238,19 @@ int himo_eval_instances(int n_frames, int64_t total_points,
                         void* d_workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Downstream segmentation evaluator: the confusion matrices of downstream/eval_seg.py (iouEval.addBatch, :113-134, fed
+ * by the loop at :248-265) for a packed batch of sweeps, one launch, one pass over the bytes.
+ * d_gt: uint8[T] flow_category_indices; h_pred: HOST array of n_results (1..HIMO_SEG_MAX_RESULTS) DEVICE pointers, each
+ * uint8[T] predicted category indices; d_seg_valid: uint8[T] (non-zero = set) or NULL; h_class_lut: HOST uint8[256],
+ * values 0..2 (eval_seg.py:255-257 as one table).
+ * d_conf: int64[n_results][2][3][3], ADDED to (zero it first): [r][0] counts every point, [r][1] the points with
+ * seg_valid set (nothing when d_seg_valid is NULL); rows = predicted class, columns = ground-truth class.
+ * total_points < 2^31.  16-byte aligned base pointers take the vectorised path. */
+#define HIMO_SEG_MAX_RESULTS 8
+int himo_seg_confusion(int64_t total_points, const uint8_t* d_gt, const uint8_t* const* h_pred, int n_results,
+                       const uint8_t* d_seg_valid, const uint8_t* h_class_lut, int64_t* d_conf, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * a10: scene-flow network (voxelise -> encoder/decoder -> per-point flow).
  * The reference's implementation is in the absent OpenSceneFlow submodule: these
  * entry points have NO reference lines to cite beyond the call sites README.md:50 (`save.py`) and the
