@@ -56,6 +56,19 @@ __device__ inline XfRegs load_xf(const FrameXf* __restrict__ xf, const unsigned*
     return x;
 }
 
+// one component of the float64 pose flow R p + t - p (save_zip.py:116, dataprocess/extract_sca.py:97)
+__device__ inline double pose_flow_f64(const XfRegs& x, const double* p, int c, bool single_row) {
+    // save_zip.py:116 -- dgemm accumulates k-ordered fused multiply-adds.  A sweep of ONE row is a vector-matrix product, which
+    // numpy hands to dgemv: the OpenBLAS build numpy 2.2 ships takes k = 1 first, then 0, then 2 (``single_row``; measured
+    // against numpy, no reference-written sweep has one row).  LIMITS: only compdis_gt_kernel and box_label_kernel pass it
+    // (compdis_kernel keeps the k-ordered chain for every sweep, as pinned by its tests), and the float32 chain has no
+    // counterpart -- sgemv's accumulation for one row was not identified, so a one-row sweep with float32 poses may differ from
+    // numpy in the last bit.
+    const double dot = single_row ? fma(p[2], x.R[c * 3 + 2], fma(p[0], x.R[c * 3], p[1] * x.R[c * 3 + 1]))
+                                  : fma(p[2], x.R[c * 3 + 2], fma(p[1], x.R[c * 3 + 1], p[0] * x.R[c * 3]));
+    return (dot + x.t[c]) - p[c];
+}
+
 // NORM: also the per-point norm of the ego-compensated flow, tools/test/save_zip_gt.py:169 --
 // np.linalg.norm(axis=1) is sqrt((x*x + y*y) + z*z) in the chain's dtype, then astype(float32)
 template <bool F32, bool NORM = false>
@@ -84,14 +97,7 @@ __device__ inline void point_math(const XfRegs& x, float px, float py, float pz,
         double e[3];
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            // save_zip.py:116 -- dgemm accumulates k-ordered fused multiply-adds.  A sweep of ONE row is a vector-matrix product, which
-            // numpy hands to dgemv: the OpenBLAS build numpy 2.2 ships takes k = 1 first, then 0, then 2 (``single_row``; measured
-            // against numpy, no reference-written sweep has one row).  LIMITS: only compdis_gt_kernel passes it (compdis_kernel keeps
-            // the k-ordered chain for every sweep, as pinned by its tests), and the float32 chain above has no counterpart -- sgemv's
-            // accumulation for one row was not identified, so a one-row sweep with float32 poses may differ from numpy in the last bit.
-            const double dot = single_row ? fma(p[2], x.R[c * 3 + 2], fma(p[0], x.R[c * 3], p[1] * x.R[c * 3 + 1]))
-                                          : fma(p[2], x.R[c * 3 + 2], fma(p[1], x.R[c * 3 + 1], p[0] * x.R[c * 3]));
-            const double pf = (dot + x.t[c]) - p[c];
+            const double pf = pose_flow_f64(x, p, c, single_row);
             const double est = raw ? 0.0 : fl[c] - pf;               // save_zip.py:117
             const double v = est / sensor_dt * (double)dt0;          // utils/__init__.py:43
             cd[c] = (float)v;                                        // save_zip.py:70-72

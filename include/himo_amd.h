@@ -251,6 +251,26 @@ int himo_seg_confusion(int64_t total_points, const uint8_t* d_gt, const uint8_t*
                        const uint8_t* d_seg_valid, const uint8_t* h_class_lut, int64_t* d_conf, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Scania extractor: the labelling of dataprocess/extract_sca.py:95-145 (compute_flow) for a packed batch of sweeps, one
+ * launch.  Replaces the pose flow of extract_sca.py:97, the `mmcv.ops.points_in_boxes_part` call of extract_sca.py:117 on double
+ * tensors, the object flow and validity of :120-134 and the class / instance columns of :137-140.
+ * h_offsets / d_offsets: int64[F+1], the same values on the host (validated here) and on the device (read by the kernel);
+ * d_ego1_SE3_ego0: double[F][3][4], the top rows of inv(pose1) @ pose0 computed by the caller; d_pc: float[T][4].
+ * h_box_offsets / d_box_offsets: int32[F+1] into the box table, whose rows the caller prepares (:104-114 and the op's own
+ * constants): d_box_geom double[B][8] = cx, cy, cz_centre, dx/2, dy/2, dz/2, cos(-rz), sin(-rz); d_box_flow float[B][3] =
+ * (hstack(vel, 0) * 0.1).astype(float32), zero where the velocity is infinite; d_box_class uint8[B]; d_box_vel_finite uint8[B].
+ * background_class: the byte of 'none'.  Outputs: d_flow float[T][3], d_flow_is_valid uint8[T], d_category uint8[T],
+ * d_instance uint32[T] (box index within the sweep + 1; 0 = background; the first containing box in list order wins).
+ * Refuses (HIMO_ERR_INVALID_ARGUMENT, outputs untouched) negative or decreasing offsets, offsets that do not start at 0 and
+ * end at total_points / n_boxes, and NULL where data is required.  16-byte aligned d_pc / d_flow / d_instance and 4-byte
+ * aligned byte columns take the vectorised path.  Asynchronous on `stream`. */
+int himo_box_label_batch(int n_frames, int64_t total_points, const int64_t* h_offsets, const int64_t* d_offsets,
+                         const double* d_ego1_SE3_ego0, const float* d_pc, int n_boxes, const int* h_box_offsets,
+                         const int* d_box_offsets, const double* d_box_geom, const float* d_box_flow,
+                         const uint8_t* d_box_class, const uint8_t* d_box_vel_finite, int background_class,
+                         float* d_flow, uint8_t* d_flow_is_valid, uint8_t* d_category, uint32_t* d_instance, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * a10: scene-flow network (voxelise -> encoder/decoder -> per-point flow).
  * The reference's implementation is in the absent OpenSceneFlow submodule: these
  * entry points have NO reference lines to cite beyond the call sites README.md:50 (`save.py`) and the
