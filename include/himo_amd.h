@@ -508,8 +508,9 @@ int himo_gru_head_backward(int64_t n, int iters, const float* d_dhx_last, const 
                            float* d_dazr, float* d_dhx0, void* stream);
 int himo_clear_u32(uint32_t* d_words, int n, void* stream);
 
-/* per-point head glue: hx[i] = [img0[cell], img1[cell], dec[cell], Linear(3,64)(offset)] (192 floats; zeros for
- * dropped points), rhx[i][128:192] = the same Linear output */
+/* per-point head glue: hx[i] = [img0[cell], img1[cell], dec[cell], Linear(3,64)(offset)] (192 floats; the 128 gathered
+ * columns are zeros for dropped points, the 64 Linear columns are computed from the offset for every point, dropped or
+ * not -- as himo_gru_head_train saves them), rhx[i][128:192] = the same Linear output */
 int himo_head_gather(int64_t n, const int32_t* d_pid, const float* d_offsets, const float* d_img0,
                      const float* d_img1, int img_pitch, const float* d_dec, int dec_pitch,
                      const float* d_w_off, const float* d_b_off, float* d_hx, float* d_rhx, int pitch, void* stream);
