@@ -54,6 +54,9 @@ SIGNATURES = {
                                    c_void_p, c_void_p]),
     "himo_box_label_batch": (c_int, [c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "himo_ground_seg_workspace_bytes": (c_size_t, [c_int, c_void_p]),
+    "himo_ground_seg_batch": (c_int, [c_int, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_size_t, c_void_p]),
 }
 
 FLAG_F32_CHAIN = 0x1

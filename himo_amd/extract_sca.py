@@ -251,6 +251,32 @@ def split_outputs(host: np.ndarray, offsets_host: np.ndarray) -> list:
     return out
 
 
+class GroundBatch:
+    """Every sweep of a batch -- also the ones without labels -- packed for the ground segmenter (``himo_amd/ground_seg.py``;
+    parity with the reference's own segmenter unpinned), uploaded with the batch that labels the boxes."""
+
+    def __init__(self, pcs, params, device=None, upload=None):
+        from . import _lib
+        from .compdis import host_upload
+        dev = device if device is not None else _lib.require_gpu()
+        up = upload if upload is not None else host_upload(dev)
+        self.params = params
+        self.offsets_host = np.zeros(len(pcs) + 1, dtype=np.int64)
+        self.offsets_host[1:] = np.cumsum([len(pc) for pc in pcs])
+        self.offsets = up([self.offsets_host], np.int64)
+        self.pc = up(pcs, np.float32)
+
+    @property
+    def total_points(self) -> int:
+        return int(self.offsets_host[-1])
+
+
+def ground_batch(gb: GroundBatch, mask=None):
+    """Launch ``himo_ground_seg_batch`` on the current stream: the uint8 device mask of every point of ``gb``.  Asynchronous."""
+    from .ground_seg import segment_batch
+    return segment_batch(gb.pc, gb.offsets_host, gb.offsets, gb.params, mask=mask)
+
+
 def label_sweeps(sweeps, background: int, device=None) -> list:
     """``compute_flow`` of extract_sca.py:95-145 for a list of sweeps, synchronously: per sweep (flow, valid, category, instance)"""
     import torch
@@ -340,7 +366,7 @@ def read_sweep(job, sequence_meta, extrinsics, name_mapping) -> dict:
     return rec
 
 
-def write_group(f, rec, labels=None) -> None:
+def write_group(f, rec, labels=None, ground=None) -> None:
     """one superframe's group with the dataset names, dtypes and conditions of extract_sca.py:76-93, :200-235"""
     g = f.create_group(rec["group"])
     g.create_dataset("lidar", data=rec["pc"].astype(np.float32))
@@ -357,10 +383,13 @@ def write_group(f, rec, labels=None) -> None:
         g.create_dataset("flow_category_indices", data=np.asarray(cat).astype(np.uint8))
         g.create_dataset("flow_instance_id", data=np.asarray(inst).astype(np.uint32))
         g.create_dataset("ego_motion", data=rec["label"][0].astype(np.float32))  # :234
+    if ground is not None:                                             # (--ground_mask: not one of the reference extractor's datasets)
+        g.create_dataset("ground_mask", data=np.asarray(ground).astype(bool))
 
 
-def process_one(origin_data, output_dir: Path, scene_id, scene_meta, lidar_ext_dir=None, name_mapping=None):
-    """One scene, serially: plan, read every superframe, label the annotated ones in ONE launch, write ``<scene_id>.h5``."""
+def process_one(origin_data, output_dir: Path, scene_id, scene_meta, lidar_ext_dir=None, name_mapping=None, ground_params=None):
+    """One scene, serially: plan, read every superframe, label the annotated ones in ONE launch, write ``<scene_id>.h5``.
+    ``ground_params`` (a ``ground_seg.GroundParams``): also write every sweep's ``ground_mask``."""
     plan = scene_plan(origin_data, output_dir, scene_id, scene_meta, lidar_ext_dir)
     if plan is None:
         return
@@ -371,9 +400,13 @@ def process_one(origin_data, output_dir: Path, scene_id, scene_meta, lidar_ext_d
     todo = [r for r in recs if r["label"] is not None]
     background = CATEGORY_TO_INDEX[name_mapping["none"]]
     labels = iter(label_sweeps([(r["pc"], r["label"][0], r["label"][1]) for r in todo], background))
+    ground = [None] * len(recs)
+    if ground_params is not None and recs:
+        from .ground_seg import ground_masks
+        ground = ground_masks([r["pc"] for r in recs], ground_params)
     with _h5().File(Path(output_dir) / f"{scene_id}.h5", "a") as f:
-        for r in recs:
-            write_group(f, r, next(labels) if r["label"] is not None else None)
+        for r, gm in zip(recs, ground):
+            write_group(f, r, next(labels) if r["label"] is not None else None, gm)
 
 
 def create_reading_index(output_dir) -> list:
@@ -403,11 +436,15 @@ def select_scenes(origin_data, metadata) -> list:
     return out
 
 
-def run_scenes(scenes, origin_data, output_dir, lidar_ext_dir, name_mapping: dict, nproc: int = 4, batch_sweeps: int = 32) -> int:
+def run_scenes(scenes, origin_data, output_dir, lidar_ext_dir, name_mapping: dict, nproc: int = 4, batch_sweeps: int = 32,
+               ground_params=None) -> int:
     """The program's loop: ``nproc`` reader threads read superframes ahead (``np.fromfile`` releases the interpreter lock), sweeps
     of consecutive scenes are packed ``batch_sweeps`` at a time (``feeder.BatchFeeder`` stages and uploads two batches ahead), each
     batch is ONE launch, and its four columns come back as one copy through ``feeder.ResultDrain`` to a writer thread that appends
-    the groups in order (one writer: the HDF5 library serialises its calls anyway).  Returns the sweeps written."""
+    the groups in order (one writer: the HDF5 library serialises its calls anyway).  Returns the sweeps written.
+    ``ground_params``: the batch also carries ALL its sweeps packed for the ground segmenter (the labelled ones a second time: the
+    labelling kernel wants them contiguous), the masks are computed on the same stream right after the labels and come back in the
+    same copy, behind the four label columns."""
     from collections import deque
     from concurrent.futures import ThreadPoolExecutor
 
@@ -449,20 +486,25 @@ def run_scenes(scenes, origin_data, output_dir, lidar_ext_dir, name_mapping: dic
     def build(group, upload):
         todo = [r for _, _, r in group if r["label"] is not None]
         batch = LabelBatch([(r["pc"], r["label"][0], r["label"][1]) for r in todo], background, device=dev, upload=upload) if todo else None
-        return (group, batch), []
+        gb = GroundBatch([r["pc"] for _, _, r in group], ground_params, device=dev, upload=upload) if ground_params is not None else None
+        return (group, batch, gb), []
 
     files = {}
     written = [0]
 
     def sink(key, host):                                               # (the writer thread; ``host`` is a view of a pinned buffer)
-        group, offsets_host = key
+        group, offsets_host, ground_offsets = key
         labels = iter(split_outputs(host, offsets_host)) if offsets_host is not None else iter(())
-        for scene_id, last, rec in group:
+        at_ground = out_layout(int(offsets_host[-1]))[1] if offsets_host is not None else 0
+        for k, (scene_id, last, rec) in enumerate(group):
+            gm = None
+            if ground_offsets is not None:
+                gm = host[at_ground + int(ground_offsets[k]):at_ground + int(ground_offsets[k + 1])]
             with _H5_LOCK:
                 f = files.get(scene_id)
                 if f is None:
                     f = files[scene_id] = _h5().File(Path(output_dir) / f"{scene_id}.h5", "a")
-                write_group(f, rec, next(labels) if rec["label"] is not None else None)
+                write_group(f, rec, next(labels) if rec["label"] is not None else None, gm)
                 if last:
                     files.pop(scene_id).close()
             written[0] += 1
@@ -470,11 +512,15 @@ def run_scenes(scenes, origin_data, output_dir, lidar_ext_dir, name_mapping: dic
     drain = ResultDrain(sink, device=dev, threads=1, copy=False)
     feed = BatchFeeder(batches(), build, device=dev)
     try:
-        for group, batch in feed:
-            if batch is None:
-                drain.put((group, None), torch.zeros(16, dtype=torch.uint8, device=dev))
-            else:
-                drain.put((group, batch.offsets_host), label_batch(batch))
+        for group, batch, gb in feed:
+            size = out_layout(batch.total_points)[1] if batch is not None else 0
+            extra = gb.total_points if gb is not None else 0
+            out = torch.empty(max(size + extra, 16), dtype=torch.uint8, device=dev)
+            if batch is not None:
+                label_batch(batch, out)
+            if gb is not None and extra:
+                ground_batch(gb, out[size:size + extra])
+            drain.put((group, batch.offsets_host if batch is not None else None, gb.offsets_host if gb is not None else None), out)
     except BaseException:
         feed.close()
         try:
@@ -492,9 +538,11 @@ def run_scenes(scenes, origin_data, output_dir, lidar_ext_dir, name_mapping: dic
 
 def main(origin_data: str = "/home/kin/data/Scania/val", metadata_pkl: str = "/home/kin/data/Scania/scania_pseudo_infos.pkl",
          output_dir: str = "/home/kin/data/Scania/preprocess/val_debuging", nproc: int = 4, create_index_only: bool = False,
-         lidar_ext_dir: str | None = None, name_mapping: str | None = None, batch_sweeps: int = 32):
+         lidar_ext_dir: str | None = None, name_mapping: str | None = None, batch_sweeps: int = 32, ground_mask: bool = False,
+         sensor_height: float = 0.0):
     """extract_sca.py:240-284.  Under ``torchrun`` (one rank per GPU) the scenes are sharded i % world, every rank writes its own
-    scene files, and rank 0 writes the index once all of them are on disk."""
+    scene files, and rank 0 writes the index once all of them are on disk.  ``ground_mask``: also write every sweep's
+    ``ground_mask`` (``himo_amd/ground_seg.py``, with ``sensor_height``); off by default, so the output is the reference's."""
     from . import distenv
     if create_index_only:
         create_reading_index(Path(output_dir))
@@ -509,7 +557,12 @@ def main(origin_data: str = "/home/kin/data/Scania/val", metadata_pkl: str = "/h
         print(f"Using {nproc} readers for creating {len(mine)} of {len(scenes)} scene.")
         err = None
         try:
-            run_scenes(mine, origin_data, output_dir, lidar_ext_dir, mapping, nproc=nproc, batch_sweeps=batch_sweeps)
+            ground_params = None
+            if ground_mask:
+                from .ground_seg import GroundParams
+                ground_params = GroundParams(sensor_height=sensor_height)
+            run_scenes(mine, origin_data, output_dir, lidar_ext_dir, mapping, nproc=nproc, batch_sweeps=batch_sweeps,
+                       ground_params=ground_params)
         except Exception as e:                                         # (an interrupt leaves at once; the launcher ends the job)
             err = e
         distenv.rendezvous(err, "its scene files, but no index was written")
@@ -530,12 +583,19 @@ def _parser():
     ap.add_argument("--lidar_ext_dir", default=None, help="directory of the <vehicle>-generated.yml extrinsics files")
     ap.add_argument("--name_mapping", default=None, help="JSON / YAML file: annotation name -> AV2 category, 'none' included (required)")
     ap.add_argument("--batch_sweeps", type=int, default=32, help="sweeps per launch")
+    ap.add_argument("--ground_mask", action="store_true",
+                    help="also write <timestamp>/ground_mask for every sweep (himo_amd.ground_seg's rule; parity with the reference's "
+                         "segmenter unpinned); off by default: the output is then the reference extractor's")
+    ap.add_argument("--sensor_height", type=float, default=0.0,
+                    help="with --ground_mask: the ground is expected at z = -sensor_height; the default 0.0 is an UNVERIFIED assumption "
+                         "about the Scania vehicle frame")
     return ap
 
 
 def _cli(argv=None):
     a = _parser().parse_args(argv)
-    main(a.origin_data, a.metadata_pkl, a.output_dir, a.nproc, a.create_index_only, a.lidar_ext_dir, a.name_mapping, a.batch_sweeps)
+    main(a.origin_data, a.metadata_pkl, a.output_dir, a.nproc, a.create_index_only, a.lidar_ext_dir, a.name_mapping, a.batch_sweeps, a.ground_mask,
+         a.sensor_height)
 
 
 if __name__ == "__main__":

@@ -85,15 +85,18 @@ def host_sample(dataset, trip, label_key: str = "flow_instance_id") -> dict:
         pc1, lab1, gm1 = f1["pc0"], f1.get(label_key), f1.get("gm0")
         if lab1 is None and not auto:
             raise KeyError(f"{label_key}: the next frame does not hold the labels ssl_label={label_key!r} names "
-                           f"(ssl_label='seflow_auto' generates them from the sweeps and their ground masks gm0 / gm1)")
+                           f"(ssl_label='seflow_auto' generates them from the sweeps and their ground masks gm0 / gm1; "
+                           f"`python -m himo_amd.ground_seg` writes them)")
     if not auto and f0.get(label_key) is None:
         raise KeyError(f"{label_key}: the frame does not hold the labels ssl_label={label_key!r} names "
-                       f"(ssl_label='seflow_auto' generates them from the sweeps and their ground masks gm0 / gm1)")
+                       f"(ssl_label='seflow_auto' generates them from the sweeps and their ground masks gm0 / gm1; "
+                       f"`python -m himo_amd.ground_seg` writes them)")
     out = {"pch1": fh["pc0"], "pc0": f0["pc0"], "pc1": pc1, "pose_h1": np.asarray(fh["pose0"], np.float64),
            "pose0": np.asarray(f0["pose0"], np.float64), "pose1": np.asarray(f0["pose1"], np.float64)}
     if auto:
         if f0.get("gm0") is None or gm1 is None:
-            raise KeyError("gm0 / gm1: ssl_label=seflow_auto needs the ground masks of both sweeps")
+            raise KeyError("gm0 / gm1: ssl_label=seflow_auto needs the ground masks of both sweeps "
+                           "(`python -m himo_amd.ground_seg` writes them)")
         out["gm0"], out["gm1"] = f0["gm0"], gm1
     else:
         out["lab0"], out["lab1"] = f0[label_key], lab1

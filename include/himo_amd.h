@@ -271,6 +271,41 @@ int himo_box_label_batch(int n_frames, int64_t total_points, const int64_t* h_of
                          float* d_flow, uint8_t* d_flow_is_valid, uint8_t* d_category, uint32_t* d_instance, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Ground segmenter: the per-point `ground_mask` every program of the package consumes, for a packed batch of sweeps.
+ * The reference takes the mask from a ground-segmentation pass in its absent submodule, so this stage follows the build's own
+ * written rule, "ray ground filter, v1" (the module docstring of himo_amd/ground_seg.py is normative): PARITY UNPINNED.
+ *   bin      a point's cell = (range bin, one of 8K segments equal in tangent), float32, no transcendental; the cell's
+ *            prototype = its point of lowest z (ties: lowest index), one 64-bit atomicMin per (wave, cell)
+ *   walk     per (sweep, segment) over the bins in ascending order, float64 on float32 inputs: a prototype (r, z) is accepted
+ *            iff fabs(z - g_prev) <= max_slope * (r - r_prev) + step_tol; the cell's ground height G is z if accepted, else
+ *            the height carried so far (also for a cell without points)
+ *   classify a binned point is ground iff z - G[cell] <= ground_thresh (float32)
+ * h_offsets / d_offsets: int64[F+1], the same values on the host (validated here) and on the device (read by the kernels);
+ * d_xyz: float[T][pitch], pitch 3 or 4 (x, y, z first); d_mask: uint8[T], 1 = ground; d_cell_ground: float[F][n_bins][8K] or
+ * NULL -- the rows of a sweep WITHOUT points are left as the caller had them (nothing is launched for such a sweep, nor for
+ * total_points == 0, which returns HIMO_OK).  d_workspace: 16-byte aligned, himo_ground_seg_workspace_bytes() bytes
+ * (HIMO_ERR_WORKSPACE when shorter; the function returns 0 for parameters the batch call refuses).
+ * Refuses (HIMO_ERR_INVALID_ARGUMENT, nothing launched) a pitch other than 3 or 4, offsets that are negative, decreasing, do
+ * not start at 0 or end at total_points, NULL where data is required, and parameters outside: r_min > 0, bin_size > 0,
+ * 1 <= n_bins <= 4096, 1 <= K <= 512, every float finite.  total_points > 0x7fffffff: HIMO_ERR_UNSUPPORTED (the prototype key
+ * holds a 32-bit point index).  Asynchronous on `stream`; the same inputs give the same bytes on every run. */
+typedef struct himo_ground_params {
+    float sensor_height;   /* the ground is expected at z = -sensor_height under the vehicle */
+    float r_min;           /* points nearer than this (in the x-y plane) are never ground */
+    float bin_size;        /* radial size of a cell */
+    int32_t n_bins;
+    int32_t K;             /* segments per octant: 8K segments */
+    float max_slope;
+    float step_tol;
+    float ground_thresh;
+} himo_ground_params;
+
+size_t himo_ground_seg_workspace_bytes(int n_frames, const himo_ground_params* params);
+int himo_ground_seg_batch(int n_frames, int64_t total_points, const int64_t* h_offsets, const int64_t* d_offsets,
+                          const float* d_xyz, int pitch, const himo_ground_params* params, uint8_t* d_mask,
+                          float* d_cell_ground, void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * a10: scene-flow network (voxelise -> encoder/decoder -> per-point flow).
  * The reference's implementation is in the absent OpenSceneFlow submodule: these
  * entry points have NO reference lines to cite beyond the call sites README.md:50 (`save.py`) and the
