@@ -57,6 +57,13 @@ SIGNATURES = {
     "himo_ground_seg_workspace_bytes": (c_size_t, [c_int, c_void_p]),
     "himo_ground_seg_batch": (c_int, [c_int, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_size_t, c_void_p]),
+    "himo_icp_workspace_bytes": (c_size_t, [c_int64, c_int]),
+    "himo_icp_vote": (c_int, [c_int64, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                              c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "himo_icp_step": (c_int, [c_int64, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                              c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "himo_icp_apply": (c_int, [c_int64, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                               c_void_p]),
 }
 
 FLAG_F32_CHAIN = 0x1

@@ -84,6 +84,7 @@ extern "C" size_t himo_abi_sizeof(const char* struct_name) {
     if (!strcmp(struct_name, "himo_sweep")) return sizeof(himo_sweep);
     if (!strcmp(struct_name, "himo_instance_record")) return sizeof(himo_instance_record);
     if (!strcmp(struct_name, "himo_ground_params")) return sizeof(himo_ground_params);
+    if (!strcmp(struct_name, "himo_icp_params")) return sizeof(himo_icp_params);
     return 0;
 }
 

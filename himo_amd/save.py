@@ -354,29 +354,70 @@ def run_fastnsf(dataset, res_name: str = "fastnsf", sink=None, by_scene: bool = 
     return results if sink is None else done
 
 
+def run_icpflow(dataset, res_name: str = "icpflow", sink=None, by_scene: bool = False, params=None):
+    """``--model icpflow``: the clustering + rigid-ICP baseline instead of the network (``himo_amd/icpflow.py``, "cluster-rigid ICP,
+    v1"; PARITY UNPINNED like the network) -- no checkpoint, no fit: DBSCAN clusters of the non-ground points of pc0, one yaw +
+    translation per cluster against pc1, the flow of every pc0 row including ego motion stored under ``res_name`` exactly like the
+    network's.  Needs both sweeps' ground masks (``gm0`` / ``gm1``).  Results leave through the same pinned-buffer writer thread as
+    ``run``'s."""
+    import torch.distributed as dist
+    rank, world = (dist.get_rank(), dist.get_world_size()) if dist.is_available() and dist.is_initialized() else (0, 1)
+    results = {} if sink is None else None
+
+    def deliver(key, flow):
+        i, f0 = key
+        if sink is None:
+            results[i] = flow
+        else:
+            sink(i, f0, flow)
+
+    icp, drain, done = None, None, 0
+    try:
+        for i, _, f0, f1 in frame_source(dataset, rank, world, by_scene=by_scene):
+            pc1, gm1 = (f0["pc1"], f0.get("gm1")) if "pc1" in f0 else (f1["pc0"], f1.get("gm0"))
+            if f0.get("gm0") is None or gm1 is None:
+                raise KeyError("gm0 / gm1: model=icpflow needs the ground masks of both sweeps "
+                               "(`python -m himo_amd.ground_seg` writes them)")
+            if icp is None:
+                from .feeder import ResultDrain
+                from .icpflow import IcpFlow
+                icp = IcpFlow(params=params)
+                drain = ResultDrain(deliver, device=icp.device)
+            drain.put((i, f0), icp.fit(np.asarray(f0["pc0"]), np.asarray(pc1), np.asarray(f0["gm0"]), np.asarray(gm1), f0["pose0"], f0["pose1"]))
+            done += 1
+    finally:
+        if drain is not None:
+            drain.close()
+        if hasattr(sink, "close"):
+            sink.close()
+    return results if sink is None else done
+
+
 def main(checkpoint: str = "", dataset_path: str = "", res_name: str = "", model: str = "", iters: int = 100):
     """``python -m himo_amd.save --checkpoint <weights.npz> --dataset_path <dir>`` (the feed-forward network), or
-    ``--model fastnsf --dataset_path <dir>`` (the optimisation-based baseline, README.md:50-53); under ``torchrun`` one rank per GPU."""
+    ``--model fastnsf --dataset_path <dir>`` (the optimisation-based baseline, README.md:50-53), or ``--model icpflow`` (clustering +
+    rigid ICP per cluster; needs the scenes' ground masks); under ``torchrun`` one rank per GPU."""
     from . import distenv
     from .dataset import SAVE_FIELDS, NpzDataset, open_dataset
-    if model not in ("", "seflowpp", "deflowpp", "fastnsf"):
-        raise ValueError(f"model={model!r}: this build runs the SeFlow++-style network (default) and 'fastnsf'")
-    fastnsf = model == "fastnsf"
-    name = res_name or ("fastnsf" if fastnsf else (Path(checkpoint).stem if checkpoint else "seflowpp_best"))
+    if model not in ("", "seflowpp", "deflowpp", "fastnsf", "icpflow"):
+        raise ValueError(f"model={model!r}: this build runs the SeFlow++-style network (default), 'fastnsf' and 'icpflow'")
+    fastnsf, icpflow = model == "fastnsf", model == "icpflow"
+    name = res_name or ("fastnsf" if fastnsf else "icpflow" if icpflow else (Path(checkpoint).stem if checkpoint else "seflowpp_best"))
     params = None
-    if checkpoint and not fastnsf:
+    if checkpoint and not fastnsf and not icpflow:
         from .seflow.checkpoint import load_params
         params = load_params(checkpoint)
     root = Path(dataset_path)
     with distenv.process_group():
         # inference reads the sweeps, poses and time stamps only (no labels, masks, ground-truth flow, earlier results), as views
         # of the file mappings where the files allow: the feeder stages them straight into its pinned buffers
-        ds = open_dataset(root, vis_name=name, eval=False, fields=SAVE_FIELDS, zero_copy=True)
+        ds = open_dataset(root, vis_name=name, eval=False, fields=SAVE_FIELDS + (("gm0", "gm1") if icpflow else ()), zero_copy=True)
         npz = isinstance(ds, NpzDataset)
         sink = NpzResultSink(root, name) if npz else H5ResultSink(root, name, before_write=ds.forget)
         done, err = 0, None
         try:
             done = (run_fastnsf(ds, name, sink=sink, by_scene=not npz, iters=iters) if fastnsf else
+                    run_icpflow(ds, name, sink=sink, by_scene=not npz) if icpflow else
                     run(ds, name, params, sink=sink, by_scene=not npz))
         except Exception as e:                                  # arrive at the rendezvous anyway, then re-raise
             err = e
@@ -390,7 +431,8 @@ if __name__ == "__main__":
     ap.add_argument("--checkpoint", default="")
     ap.add_argument("--dataset_path", required=True)
     ap.add_argument("--res_name", default="")
-    ap.add_argument("--model", default="", help="'fastnsf': fit the optimisation-based baseline per sweep pair instead of running the network")
+    ap.add_argument("--model", default="", help="'fastnsf': fit the optimisation-based baseline per sweep pair instead of running the network; "
+                                                "'icpflow': clustering + rigid ICP per cluster (needs ground masks: python -m himo_amd.ground_seg)")
     ap.add_argument("--iters", type=int, default=100, help="optimiser iterations per sweep pair (--model fastnsf)")
     import sys
     # the reference's program takes hydra-style overrides (`save.py checkpoint=... dataset_path=...`, `model=fastnsf`: README.md:46-53)

@@ -306,6 +306,62 @@ int himo_ground_seg_batch(int n_frames, int64_t total_points, const int64_t* h_o
                           float* d_cell_ground, void* d_workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * ICP-Flow baseline (`save --model icpflow`, result key `icpflow`): clusters of the non-ground points of pc0, one rigid fit
+ * (yaw + 3-D translation) per cluster against pc1, flow = fitted motion.  The reference's ICP-Flow code is in its absent
+ * submodule (only the key name is in its tree, tools/view_instance.py:155-156), so this stage follows the build's own written
+ * rule, "cluster-rigid ICP, v1" (the module docstring of himo_amd/icpflow.py is normative): PARITY UNPINNED.
+ *
+ * The clustered points are passed SORTED BY LABEL: cluster k (label k + 1) owns the rows offsets[k] .. offsets[k + 1] of
+ * d_pts / d_moved; h_offsets / d_offsets: int64[n_clusters + 1], the same values on the host (validated here) and on the device
+ * (read by the kernels).  A cluster may be empty (a label without points).  A label >= n_clusters + 1 among the sorted rows is
+ * rows beyond offsets[n_clusters]: offsets that do not end at n are refused.
+ * State per cluster: d_transform double[C][5] = c, s, tx, ty, tz (R = [[c, -s], [s, c]] about z); d_status int32[C][4] =
+ * HIMO_ICP_ACCEPTED / FAILED / REJECTED, the inlier count of the cluster's last pass, the vote peak kx, ky.
+ *   himo_icp_vote   rule 2: the target sweep (d_target float[n_target][3]) is binned on the BEV cell grid of himo_nn_grid
+ *                   (1 m cells from (-52, -52), 104 x 104; points outside go to the border cells); every clustered point votes with
+ *                   the target points near it.  d_counts int32[C][(2 half + 1)^2] (bin (ky + half) * (2 half + 1) + kx + half),
+ *                   d_peak int32[C][2] = kx, ky; starts d_transform at (1, 0, kx bin, ky bin, 0) and d_status at ACCEPTED.
+ *   himo_icp_step   one iteration of rule 3 given the search result of the moved points (d_moved float[n][3]; d_nn_idx /
+ *                   d_nn_dist2 from himo_nn_grid(n, d_moved, n_target, d_target)): inliers, float64 sums in a fixed reduction
+ *                   shape (no floating-point atomics), closed form, composition; a cluster with fewer than min_inliers stops as
+ *                   FAILED.  final_pass != 0 is rule 4 instead: count the inliers, ACCEPTED iff inliers / size >= min_ratio, else
+ *                   REJECTED (FAILED stays).  d_inlier: uint8[n] or NULL.
+ *   himo_icp_apply  rows in ANY order with their labels (d_labels int32[n]; 0 and any value outside 1 .. n_clusters: identity).
+ *                   HIMO_ICP_MOVED: d_out float[n][3] = float32(R a + t), evaluated in float64; HIMO_ICP_FLOW: the same for the
+ *                   ACCEPTED clusters only (every other row keeps a), minus d_base (float[n][base_pitch], float32 subtraction).
+ * Refuse (HIMO_ERR_INVALID_ARGUMENT, nothing launched): a pitch other than 3 or 4, a negative count, offsets that are negative,
+ * decreasing, do not start at 0 or end at n, NULL or misaligned where data is required, and parameters that are not finite and
+ * positive or have half > 64.  A short, NULL or misaligned (16 bytes) workspace: HIMO_ERR_WORKSPACE (himo_icp_workspace_bytes
+ * returns 0 for counts it refuses).  n == 0 or n_clusters == 0: HIMO_OK, nothing launched.  Asynchronous on `stream`; the same
+ * inputs give the same bytes on every run. */
+typedef struct himo_icp_params {
+    float bin;             /* metres per vote bin */
+    int32_t half;          /* the vote covers |kx|, |ky| <= half */
+    float z_gate;          /* a pair votes iff |dz| <= z_gate */
+    float max_dist;        /* inlier iff squared distance <= max_dist^2 */
+    int32_t min_inliers;
+    float min_ratio;       /* accepted iff inliers / cluster size >= min_ratio */
+    int32_t iters;         /* read by the host: the kernels run one pass per call */
+} himo_icp_params;
+
+#define HIMO_ICP_ACCEPTED 0
+#define HIMO_ICP_FAILED 1
+#define HIMO_ICP_REJECTED 2
+#define HIMO_ICP_MOVED 0
+#define HIMO_ICP_FLOW 1
+
+size_t himo_icp_workspace_bytes(int64_t n_target, int n_clusters);
+int himo_icp_vote(int64_t n, const float* d_pts, int pitch, int n_clusters, const int64_t* h_offsets, const int64_t* d_offsets,
+                  int64_t n_target, const float* d_target, const himo_icp_params* params, int32_t* d_counts, int32_t* d_peak,
+                  double* d_transform, int32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream);
+int himo_icp_step(int64_t n, const float* d_moved, int n_clusters, const int64_t* h_offsets, const int64_t* d_offsets,
+                  int64_t n_target, const float* d_target, const int32_t* d_nn_idx, const float* d_nn_dist2,
+                  const himo_icp_params* params, int final_pass, double* d_transform, int32_t* d_status, uint8_t* d_inlier,
+                  void* d_workspace, size_t workspace_bytes, void* stream);
+int himo_icp_apply(int64_t n, const float* d_pts, int pitch, const int32_t* d_labels, int n_clusters, const double* d_transform,
+                   const int32_t* d_status, int mode, const float* d_base, int base_pitch, float* d_out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * a10: scene-flow network (voxelise -> encoder/decoder -> per-point flow).
  * The reference's implementation is in the absent OpenSceneFlow submodule: these
  * entry points have NO reference lines to cite beyond the call sites README.md:50 (`save.py`) and the

@@ -1,0 +1,411 @@
+"""The checker of the ICP-Flow baseline: a numpy restatement of rules 0-5 of "cluster-rigid ICP, v1" (the module docstring of
+``himo_amd/icpflow.py`` is the text).  Votes are all-pairs, the nearest neighbour is brute force in float32 with the lowest-row
+tie, the sums are float64.  Nothing under ``himo_amd/`` imports it; it imports nothing from there either.
+
+The transforms of ``himo_icp_step`` are compared within ``16 * s`` (floor 1e-12), ``s`` = the largest difference between the
+transforms this restatement gets with its sums taken in forward, reversed and pairwise order on the same inputs (``step_spread``;
+measured on the CPU from this file alone).  The device's reduction shape (strided partials, then a tree) is one more order of the
+same sums, not mirrored here bit for bit.  Per case of tests/test_icpflow_gpu.py::test_step_equals_the_restatement
+(``step_case(size)``), the spread and the bar:
+
+    cluster size      s            bar = max(16 s, 1e-12)
+    8                 8.9e-16      1.0e-12
+    63                1.7e-15      1.0e-12
+    64                4.2e-17      1.0e-12
+    65                8.9e-16      1.0e-12
+    2049              1.8e-15      1.0e-12
+
+(``python tests/icpflow_ref.py`` prints the table.)
+"""
+import numpy as np
+
+DEFAULTS = dict(bin=0.25, half=16, z_gate=1.0, max_dist=1.0, min_inliers=8, min_ratio=0.5, iters=10)
+ACCEPTED, FAILED, REJECTED = 0, 1, 2
+EPS, MIN_PTS, RANGE_NET = 0.5, 8, 51.2
+
+f32, f64 = np.float32, np.float64
+
+
+def params(**kw):
+    p = dict(DEFAULTS)
+    p.update(kw)
+    return p
+
+
+# ---- rule 0 -------------------------------------------------------------------------------------------------------------------------
+def moved(pc0, pose0, pose1):
+    """pc0 in pc1's frame: inv(pose1) @ pose0 rounded to float32, then ((x T0 + y T1) + z T2) + T3 in float32"""
+    T = (np.linalg.inv(np.asarray(pose1, f64)) @ np.asarray(pose0, f64)).astype(f32)
+    p = np.asarray(pc0, f32).reshape(-1, np.asarray(pc0).shape[-1] if np.asarray(pc0).ndim == 2 else 3)[:, :3]
+    x, y, z = p[:, 0], p[:, 1], p[:, 2]
+    return np.stack([((x * T[r, 0] + y * T[r, 1]) + z * T[r, 2]) + T[r, 3] for r in range(3)], axis=1).astype(f32)
+
+
+def participates(pts, ground):
+    pts = np.asarray(pts, f32).reshape(-1, 3)
+    return ~(np.asarray(ground, bool) | (np.abs(pts[:, :2]).max(axis=1, initial=0.0) > f32(RANGE_NET)))
+
+
+# ---- rule 1 -------------------------------------------------------------------------------------------------------------------------
+def dbscan(pts, eps=EPS, min_pts=MIN_PTS, skip=None):
+    """brute-force DBSCAN by the package's rule (csrc/dbscan.hip): float32 distances dx*dx + dy*dy + dz*dz <= eps*eps, min_pts counts
+    the point itself, clusters numbered by their lowest point index, a border point joins the neighbouring cluster of lowest such index"""
+    pts = np.asarray(pts, f32).reshape(-1, 3)
+    n = len(pts)
+    labels = np.zeros(n, np.int32)
+    take = np.ones(n, bool) if skip is None else ~np.asarray(skip, bool)
+    idx = np.flatnonzero(take)
+    if len(idx) == 0:
+        return labels
+    sub = pts[idx]
+    d = sub[:, None, :] - sub[None, :, :]
+    near = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1] + d[..., 2] * d[..., 2]) <= f32(eps) * f32(eps)
+    core = near.sum(1) >= min_pts
+    root = np.where(core, np.arange(len(sub)), len(sub))            # (rows of sub are in ascending original index)
+    link = near & core[None, :] & core[:, None]
+    while True:                                                     # the lowest index of a component, by propagation
+        new = np.where(core, np.where(link, root[None, :], len(sub)).min(1, initial=len(sub)), len(sub))
+        new = np.minimum(new, root)
+        if np.array_equal(new, root):
+            break
+        root = new
+    border = ~core & (near & core[None, :]).any(1)
+    root[border] = np.where(near[border] & core[None, :], root[None, :], len(sub)).min(1)
+    roots = np.unique(root[root < len(sub)])
+    rank = np.zeros(len(sub) + 1, np.int32)
+    rank[roots] = np.arange(1, len(roots) + 1)
+    labels[idx] = rank[root]
+    return labels
+
+
+# ---- rule 2 -------------------------------------------------------------------------------------------------------------------------
+def vote(pts, labels, n_clusters, target, **kw):
+    """all-pairs counters int32 [C, W, W] (indexed [ky + half, kx + half]) and peaks int32 [C, 2] = kx, ky; ``unique`` [C]: the peak's
+    count is strictly above every other bin's (or the cluster has no votes at all)"""
+    p = params(**kw)
+    half, W = int(p["half"]), 2 * int(p["half"]) + 1
+    pts, target = np.asarray(pts, f32).reshape(-1, 3), np.asarray(target, f32).reshape(-1, 3)
+    labels = np.asarray(labels)
+    counts = np.zeros((n_clusters, W, W), np.int32)
+    for i in np.flatnonzero(labels > 0):
+        with np.errstate(all="ignore"):
+            dz = target[:, 2] - pts[i, 2]
+            kx = np.rint((target[:, 0] - pts[i, 0]) / f32(p["bin"]))
+            ky = np.rint((target[:, 1] - pts[i, 1]) / f32(p["bin"]))
+            ok = (np.abs(dz) <= f32(p["z_gate"])) & (np.abs(kx) <= half) & (np.abs(ky) <= half)
+        np.add.at(counts[labels[i] - 1], (ky[ok].astype(np.int64) + half, kx[ok].astype(np.int64) + half), 1)
+    peaks = np.zeros((n_clusters, 2), np.int32)
+    unique = np.ones(n_clusters, bool)
+    ky_g, kx_g = np.meshgrid(np.arange(-half, half + 1), np.arange(-half, half + 1), indexing="ij")
+    for k in range(n_clusters):
+        c = counts[k]
+        order = np.lexsort((kx_g.ravel(), ky_g.ravel(), (kx_g ** 2 + ky_g ** 2).ravel(), -c.ravel().astype(np.int64)))
+        best = order[0]
+        peaks[k] = (kx_g.ravel()[best], ky_g.ravel()[best])
+        unique[k] = c.max() == 0 or (c == c.max()).sum() == 1
+    return counts, peaks, unique
+
+
+# ---- rule 3 -------------------------------------------------------------------------------------------------------------------------
+def nearest(m, target):
+    """(squared distance float32 [n], row int32 [n]) brute force in float32, ties to the lowest row; (+inf, -1) without targets; also
+    the second-smallest squared distance (+inf when there is none)"""
+    m, target = np.asarray(m, f32).reshape(-1, 3), np.asarray(target, f32).reshape(-1, 3)
+    if len(target) == 0:
+        return np.full(len(m), np.inf, f32), np.full(len(m), -1, np.int32), np.full(len(m), np.inf, f32)
+    d2 = np.empty(len(m), f32)
+    idx = np.empty(len(m), np.int32)
+    second = np.full(len(m), np.inf, f32)
+    for lo in range(0, len(m), 512):
+        d = m[lo:lo + 512, None, :] - target[None, :, :]
+        dd = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+        j = dd.argmin(1)                                            # (the first of equals)
+        idx[lo:lo + 512], d2[lo:lo + 512] = j, dd[np.arange(len(j)), j]
+        if len(target) > 1:
+            dd[np.arange(len(j)), j] = np.inf
+            second[lo:lo + 512] = dd.min(1)
+    return d2, idx, second
+
+
+def apply(pts, T):
+    """m = float32(R a + t) evaluated in float64: ((c x - s y) + tx, (s x + c y) + ty, z + tz)"""
+    p = np.asarray(pts, f32).reshape(-1, 3).astype(f64)
+    c, s, tx, ty, tz = (f64(v) for v in T)
+    return np.stack([(c * p[:, 0] - s * p[:, 1]) + tx, (s * p[:, 0] + c * p[:, 1]) + ty, p[:, 2] + tz], axis=1).astype(f32)
+
+
+def _sum(v, order):
+    v = np.asarray(v, f64)
+    if order == "reversed":
+        v = v[::-1]
+    if order == "pairwise":
+        v = v.copy()
+        while len(v) > 1:
+            if len(v) & 1:
+                v = np.append(v, 0.0)
+            v = v[0::2] + v[1::2]
+        return f64(v[0]) if len(v) else f64(0.0)
+    t = f64(0.0)
+    for x in v:
+        t = t + x
+    return t
+
+
+def solve(m, q, T, order="forward"):
+    """one closed-form update of T = (c, s, tx, ty, tz) from the inlier pairs m (float32 [n, 3]) -> q (float32 [n, 3])"""
+    m, q = np.asarray(m, f32).astype(f64), np.asarray(q, f32).astype(f64)
+    n = f64(len(m))
+    mb = np.array([_sum(m[:, c], order) / n for c in range(3)])
+    qb = np.array([_sum(q[:, c], order) / n for c in range(3)])
+    mx, my, qx, qy = m[:, 0] - mb[0], m[:, 1] - mb[1], q[:, 0] - qb[0], q[:, 1] - qb[1]
+    A, B = _sum(mx * qx + my * qy, order), _sum(mx * qy - my * qx, order)
+    h = np.sqrt(A * A + B * B)
+    dc, ds = (f64(1.0), f64(0.0)) if h == 0 else (A / h, B / h)
+    dt = np.array([qb[0] - (dc * mb[0] - ds * mb[1]), qb[1] - (ds * mb[0] + dc * mb[1]), qb[2] - mb[2]])
+    c, s, tx, ty, tz = (f64(v) for v in T)
+    return np.array([dc * c - ds * s, ds * c + dc * s, (dc * tx - ds * ty) + dt[0], (ds * tx + dc * ty) + dt[1], tz + dt[2]], f64)
+
+
+def step(m, labels, n_clusters, target, d2, idx, T, status, final=False, order="forward", **kw):
+    """rule 3 (or, ``final``, rule 4) for every cluster given the search result of the moved points.  ``T`` [C, 5] float64 and
+    ``status`` [C, 4] int32 (state, inliers, kx, ky) are updated in place; returns the inlier mask of every row."""
+    p = params(**kw)
+    m, target, labels = np.asarray(m, f32).reshape(-1, 3), np.asarray(target, f32).reshape(-1, 3), np.asarray(labels)
+    inlier = (np.asarray(d2, f32) <= f32(p["max_dist"]) * f32(p["max_dist"])) & (np.asarray(idx) >= 0)
+    for k in range(n_clusters):
+        rows = np.flatnonzero(labels == k + 1)
+        if status[k, 0] == FAILED:
+            continue
+        use = rows[inlier[rows]]
+        status[k, 1] = len(use)
+        if final:
+            ok = len(rows) > 0 and f64(len(use)) / f64(len(rows)) >= f64(f32(p["min_ratio"]))
+            status[k, 0] = ACCEPTED if ok else REJECTED
+        elif len(use) < int(p["min_inliers"]):
+            status[k, 0] = FAILED
+        else:
+            T[k] = solve(m[use], target[np.asarray(idx)[use]], T[k], order)
+    return inlier
+
+
+class Margins:
+    """the smallest margins of a run's discrete decisions"""
+
+    def __init__(self):
+        self.nn_gap = np.inf        # relative gap between the nearest and the second-nearest squared distance
+        self.dist = np.inf          # |d2 - max_dist^2| / max_dist^2
+        self.count = np.inf         # |n - min_inliers|
+        self.ratio = np.inf         # |inliers / size - min_ratio|
+        self.peaks_unique = True
+
+    def ok(self, rel=1e-4):
+        return self.nn_gap >= rel and self.dist >= rel and self.count >= 1 and self.ratio >= rel and self.peaks_unique
+
+    def __repr__(self):
+        return (f"Margins(nn_gap={self.nn_gap:.3g}, dist={self.dist:.3g}, count={self.count}, ratio={self.ratio:.3g}, "
+                f"peaks_unique={self.peaks_unique})")
+
+
+def fit_clusters(a, labels, n_clusters, B, order="forward", margins=None, **kw):
+    """rules 2-4 on the common-frame points ``a`` with their labels against the target set ``B``: (T [C, 5], status [C, 4])"""
+    p = params(**kw)
+    mg = margins if margins is not None else Margins()
+    a, B, labels = np.asarray(a, f32).reshape(-1, 3), np.asarray(B, f32).reshape(-1, 3), np.asarray(labels)
+    counts, peaks, unique = vote(a, labels, n_clusters, B, **kw)
+    mg.peaks_unique = mg.peaks_unique and bool(unique.all())
+    T = np.zeros((n_clusters, 5), f64)
+    T[:, 0] = 1.0
+    T[:, 2:4] = peaks.astype(f64) * f64(f32(p["bin"]))
+    status = np.zeros((n_clusters, 4), np.int32)
+    status[:, 2:4] = peaks
+    rows = np.flatnonzero(labels > 0)
+    max_d2 = f32(p["max_dist"]) * f32(p["max_dist"])
+
+    def search():
+        m = a.copy()
+        for k in range(n_clusters):
+            sel = labels == k + 1
+            m[sel] = apply(a[sel], T[k])
+        d2, idx, second = nearest(m[rows], B)
+        live = status[labels[rows] - 1, 0] != FAILED
+        with np.errstate(all="ignore"):
+            if live.any() and len(B):
+                gap = (second[live] - d2[live]) / np.maximum(second[live], f32(1e-30))
+                mg.nn_gap = min(mg.nn_gap, float(np.min(np.where(np.isfinite(second[live]), gap, np.inf), initial=np.inf)))
+                mg.dist = min(mg.dist, float(np.min(np.abs(d2[live].astype(f64) - f64(max_d2)) / f64(max_d2), initial=np.inf)))
+        full_d2, full_idx = np.full(len(a), np.inf, f32), np.full(len(a), -1, np.int32)
+        full_d2[rows], full_idx[rows] = d2, idx
+        return m, full_d2, full_idx
+
+    for _ in range(int(p["iters"])):
+        m, d2, idx = search()
+        before = status[:, 0].copy()
+        step(m, labels, n_clusters, B, d2, idx, T, status, False, order, **kw)
+        for k in np.flatnonzero(before != FAILED):
+            n = int(status[k, 1])
+            mg.count = min(mg.count, abs(n - int(p["min_inliers"])))
+    m, d2, idx = search()
+    before = status[:, 0].copy()
+    step(m, labels, n_clusters, B, d2, idx, T, status, True, order, **kw)
+    for k in np.flatnonzero(before != FAILED):
+        size = int((labels == k + 1).sum())
+        if size:
+            mg.ratio = min(mg.ratio, abs(float(status[k, 1]) / size - float(f64(f32(p["min_ratio"])))))
+    return T, status
+
+
+# ---- rules 0-5 ----------------------------------------------------------------------------------------------------------------------
+def fit(pc0, pc1, gm0, gm1, pose0, pose1, a=None, order="forward", eps=EPS, min_pts=MIN_PTS, **kw):
+    """the whole rule for one pair: {"flow" float32 [N0, 3], "labels", "T", "status", "a", "margins"}.  ``a``: the common-frame
+    points when the caller already holds them (the GPU tests pass the device's own ``himo_rigid_transform`` result, which rule 0
+    names as the definition), else ``moved(pc0, pose0, pose1)``"""
+    pc0 = np.asarray(pc0, f32).reshape(-1, np.asarray(pc0).shape[-1])
+    pc1 = np.asarray(pc1, f32).reshape(-1, np.asarray(pc1).shape[-1])
+    a = moved(pc0, pose0, pose1) if a is None else np.asarray(a, f32).reshape(-1, 3)
+    b = pc1[:, :3]
+    use_a, use_b = participates(a, gm0), participates(b, gm1)
+    B = b[use_b]
+    labels = dbscan(a, eps, min_pts, ~use_a)
+    C = int(labels.max(initial=0))
+    mg = Margins()
+    T, status = fit_clusters(a, labels, C, B, order, mg, **kw)
+    m = a.copy()
+    for k in range(C):
+        if status[k, 0] == ACCEPTED:
+            sel = labels == k + 1
+            m[sel] = apply(a[sel], T[k])
+    return {"flow": (m - pc0[:, :3]).astype(f32), "ego_flow": (a - pc0[:, :3]).astype(f32), "labels": labels, "T": T, "status": status,
+            "a": a, "margins": mg}
+
+
+# ---- seeded inputs shared by the CPU and the GPU tests ----------------------------------------------------------------------------------
+def yaw_pose(deg, t):
+    c, s = np.cos(np.deg2rad(deg)), np.sin(np.deg2rad(deg))
+    T = np.eye(4)
+    T[:2, :2] = [[c, -s], [s, c]]
+    T[:3, 3] = t
+    return T
+
+
+def lattice_cluster(centre=(-1.5, -0.9, 0.5)):
+    """the hand-derived cluster: a 6 x 4 lattice at 0.6 m spacing plus a 5-point mast (29 points); by default centred on the origin, so
+    that a yaw about the origin moves no point by more than a bin and the vote peak is the translation's bin"""
+    gx, gy = np.meshgrid(np.arange(6) * 0.6, np.arange(4) * 0.6, indexing="ij")
+    flat = np.stack([gx.ravel(), gy.ravel(), np.zeros(24)], axis=1)
+    mast = np.stack([np.full(5, 1.2), np.full(5, 0.6), 0.4 + 0.4 * np.arange(5)], axis=1)
+    return np.concatenate([flat, mast]) + np.asarray(centre)
+
+
+HAND_EPS, HAND_MIN_PTS = 0.7, 3            # the lattice's 0.6 m spacing is wider than ssl_label.EPS: the hand scenes cluster with these
+
+
+def hand_scene(yaw_deg=5.0, t=(2.0, 0.5, 0.1)):
+    """(pc0, pc1, gm0, gm1, pose0, pose1, true displacement of the moving cluster's rows [29, 3] float64): the lattice cluster under
+    yaw about z and a translation, computed in float64 and rounded to float32, plus a far static cluster copied unchanged"""
+    cl = lattice_cluster()
+    far = lattice_cluster((-20.0, -15.0, 0.5))
+    c, s = np.cos(np.deg2rad(yaw_deg)), np.sin(np.deg2rad(yaw_deg))
+    R = np.array([[c, -s, 0], [s, c, 0], [0, 0, 1.0]])
+    tgt = cl @ R.T + np.asarray(t, f64)
+    pc0 = np.concatenate([cl, far]).astype(f32)
+    pc1 = np.concatenate([tgt, far]).astype(f32)
+    disp = pc1[:29].astype(f64) - pc0[:29].astype(f64)
+    return pc0, pc1, np.zeros(len(pc0), bool), np.zeros(len(pc1), bool), np.eye(4), np.eye(4), disp
+
+
+def seeded_pair(seed=7, n=3000, boxes=12, pose1=None):
+    """a pair of sweeps in pc0's frame world: ``boxes`` moving boxes (surface points), two walls, clutter and ground; pc1 = the same
+    surfaces resampled with noise, the boxes moved by their own yaw and translation, everything seen from ``pose1``"""
+    rng = np.random.default_rng(seed)
+    per = n // (boxes + 6)
+    parts0, parts1 = [], []
+    for k in range(boxes):
+        ang = 2 * np.pi * k / boxes + 0.2
+        centre = np.array([(14 + 2.5 * (k % 4)) * np.cos(ang), (14 + 2.5 * (k % 4)) * np.sin(ang), 0.9])
+        dims = np.array([4.2, 1.9, 1.6])
+        u = rng.uniform(-0.5, 0.5, (per, 3)) * dims                 # the two faces a sensor sees: one side, one end
+        side = rng.random(per) < 0.7
+        u[side, 1] = -dims[1] / 2
+        u[~side, 0] = -dims[0] / 2
+        yaw = np.deg2rad(rng.uniform(-4, 4))
+        tr = np.array([rng.uniform(-2.5, 2.5), rng.uniform(-2.5, 2.5), 0.0]) if k % 3 else np.zeros(3)
+        c, s = np.cos(yaw), np.sin(yaw)
+        R = np.array([[c, -s, 0], [s, c, 0], [0, 0, 1.0]])
+        parts0.append(u + centre)
+        parts1.append((u + rng.normal(0, 0.01, u.shape)) @ R.T + centre + tr)
+    for k in range(2):
+        w = np.stack([rng.uniform(-6, 6, 2 * per), np.full(2 * per, -34.0 if k else 36.0) + rng.normal(0, 0.01, 2 * per),
+                      rng.uniform(0.2, 2.2, 2 * per)], axis=1)
+        parts0.append(w)
+        parts1.append(w + rng.normal(0, 0.01, w.shape))
+    clutter = np.stack([rng.uniform(-60, 60, per), rng.uniform(-60, 60, per), rng.uniform(0.3, 2.0, per)], axis=1)
+    parts0.append(clutter)
+    parts1.append(clutter[: per // 2])
+    n_obj = sum(len(q) for q in parts0)
+    g0 = np.stack([rng.uniform(-55, 55, n - n_obj), rng.uniform(-55, 55, n - n_obj), rng.normal(0, 0.02, n - n_obj)], axis=1)
+    g1 = np.stack([rng.uniform(-55, 55, n - n_obj), rng.uniform(-55, 55, n - n_obj), rng.normal(0, 0.02, n - n_obj)], axis=1)
+    w0, w1 = np.concatenate(parts0 + [g0]), np.concatenate(parts1 + [g1])
+    gm0 = np.arange(len(w0)) >= n_obj
+    gm1 = np.arange(len(w1)) >= len(w1) - len(g1)
+    pose0 = np.eye(4)
+    pose1 = np.eye(4) if pose1 is None else np.asarray(pose1, f64)
+    inv1 = np.linalg.inv(pose1)
+    pc1 = w1 @ inv1[:3, :3].T + inv1[:3, 3]
+    p0, p1 = rng.permutation(len(w0)), rng.permutation(len(w1))
+    pc0 = np.concatenate([w0, rng.uniform(0, 1, (len(w0), 1))], axis=1).astype(f32)[p0]
+    return pc0, pc1.astype(f32)[p1], gm0[p0], gm1[p1], pose0, pose1
+
+
+def vote_case(seed, n, n_clusters, n_target=400, gaps=False):
+    """``n`` clustered points in ``n_clusters`` clusters (labels sorted; with ``gaps`` every third label has no points) and a target set:
+    clusters are blobs, the targets the blobs shifted by a per-cluster offset plus scatter, all inside +-45 m"""
+    rng = np.random.default_rng(seed)
+    used = [k for k in range(n_clusters) if not (gaps and k % 3 == 1)] or [0]
+    labels = np.sort(np.asarray(used)[rng.integers(0, len(used), n)] + 1).astype(np.int32) if n else np.zeros(0, np.int32)
+    centres = rng.uniform(-40, 40, (n_clusters, 3)) * np.array([1, 1, 0.02])
+    shift = rng.uniform(-3.0, 3.0, (n_clusters, 3)) * np.array([1, 1, 0.05])
+    pts = centres[labels - 1] + rng.normal(0, 0.4, (n, 3)) * np.array([1, 1, 0.3]) if n else np.zeros((0, 3))
+    tl = rng.integers(0, n_clusters, n_target)
+    tgt = centres[tl] + shift[tl] + rng.normal(0, 0.5, (n_target, 3)) * np.array([1, 1, 0.4])
+    tgt[: n_target // 10] = rng.uniform(-51, 51, (n_target // 10, 3)) * np.array([1, 1, 0.02])
+    return pts.astype(f32), labels, tgt.astype(f32)
+
+
+def step_case(size, seed=None):
+    """one cluster of ``size`` points plus a 40-point bystander cluster, moved points m, a target set and its search result: a
+    noisy rigid motion (yaw 3 degrees) so that the closed form has work to do; a tenth of the points are outliers beyond max_dist"""
+    rng = np.random.default_rng(1000 + size if seed is None else seed)
+    sizes = [size, 40]
+    labels = np.repeat(np.arange(1, 3), sizes).astype(np.int32)
+    n = len(labels)
+    m = (np.array([12.0, -7.0, 0.8]) + rng.uniform(-2.5, 2.5, (n, 3)) * np.array([1, 0.5, 0.3])).astype(f32)
+    c, s = np.cos(np.deg2rad(3.0)), np.sin(np.deg2rad(3.0))
+    R = np.array([[c, -s, 0], [s, c, 0], [0, 0, 1.0]])
+    tgt = (m.astype(f64) - m.astype(f64).mean(0)) @ R.T + m.astype(f64).mean(0) + np.array([0.2, -0.1, 0.05]) + rng.normal(0, 0.02, (n, 3))
+    out = rng.random(n) < 0.1
+    out[:8] = False                                                 # (a cluster of 8 keeps min_inliers)
+    tgt[out] += np.array([3.0, 3.0, 0.0])
+    tgt = np.concatenate([tgt, rng.uniform(-50, 50, (30, 3)) * np.array([1, 1, 0.02])]).astype(f32)
+    d2, idx, _ = nearest(m, tgt)
+    return m, labels, tgt, d2, idx
+
+
+def step_spread(m, labels, n_clusters, tgt, d2, idx, **kw):
+    """``s``: the largest difference among the transforms of one step with the sums in forward, reversed and pairwise order"""
+    out = []
+    for order in ("forward", "reversed", "pairwise"):
+        T = np.zeros((n_clusters, 5), f64)
+        T[:, 0] = 1.0
+        T[:, 2:] = [0.05, -0.02, 0.01]
+        status = np.zeros((n_clusters, 4), np.int32)
+        step(m, labels, n_clusters, tgt, d2, idx, T, status, False, order, **kw)
+        out.append(T)
+    return max(float(np.abs(out[i] - out[j]).max()) for i in range(3) for j in range(i))
+
+
+STEP_SIZES = (8, 63, 64, 65, 2049)
+
+if __name__ == "__main__":
+    for size in STEP_SIZES:
+        s = step_spread(*(lambda c: (c[0], c[1], 2, c[2], c[3], c[4]))(step_case(size)))
+        print(f"    {size:<17d} {s:<12.1e} {max(16 * s, 1e-12):.1e}")
