@@ -24,6 +24,7 @@
 #include "bf16x3.h"
 #include <math.h>
 #include <algorithm>
+#include <vector>
 
 namespace himo {
 
@@ -610,13 +611,27 @@ static size_t pillar_ws(int64_t n, int cells) { return 2 * ws_cells(cells) + ws_
 // (a position that does not depend on the sweep's point count, unlike the lists in front of it)
 static size_t ws_occ(int cells) { return round_up(((size_t)cells + 63) / 64 * 8, 16); }
 
+// The cell count of a grid in 64 bits (grid_w * grid_h in int wraps: 65536 x 65536 is 0 cells), and the one refusal every entry point
+// of this file makes for it before anything else looks at the count: more than kMaxCells cells need a third scan level.
+constexpr int64_t kMaxCells = (int64_t)kScanBlock * 1024;
+static int64_t grid_cells(int grid_w, int grid_h) { return (int64_t)grid_w * (int64_t)grid_h; }
+static int grid_status(int grid_w, int grid_h) {
+    if (grid_w < 1 || grid_h < 1) return HIMO_ERR_INVALID_ARGUMENT;
+    return grid_cells(grid_w, grid_h) > kMaxCells ? HIMO_ERR_UNSUPPORTED : HIMO_OK;
+}
+
 extern "C" size_t himo_pillar_workspace_bytes(int64_t max_points, int grid_w, int grid_h) {
-    return pillar_ws(max_points, grid_w * grid_h) + 64 + ws_occ(grid_w * grid_h);
+    if (max_points < 0 || max_points > 0x7fffffff || grid_status(grid_w, grid_h) != HIMO_OK) return 0;   // what himo_pillarize refuses
+    const int cells = (int)grid_cells(grid_w, grid_h);
+    return pillar_ws(max_points, cells) + 64 + ws_occ(cells);
 }
 
 extern "C" int himo_pillar_occupancy_reset(void* d_workspace, size_t workspace_bytes, int grid_w, int grid_h, void* stream) {
-    if (!d_workspace || grid_w < 1 || grid_h < 1 || workspace_bytes < ws_occ(grid_w * grid_h)) return HIMO_ERR_INVALID_ARGUMENT;
-    const size_t nb = ws_occ(grid_w * grid_h);
+    if (!d_workspace || grid_w < 1 || grid_h < 1) return HIMO_ERR_INVALID_ARGUMENT;
+    if (grid_status(grid_w, grid_h) != HIMO_OK) return HIMO_ERR_UNSUPPORTED;
+    const int cells = (int)grid_cells(grid_w, grid_h);
+    if (workspace_bytes < ws_occ(cells)) return HIMO_ERR_INVALID_ARGUMENT;
+    const size_t nb = ws_occ(cells);
     HIMO_HIP(hipMemsetAsync(reinterpret_cast<char*>(d_workspace) + (workspace_bytes - nb), 0xFF, nb, (hipStream_t)stream));
     return HIMO_OK;
 }
@@ -625,16 +640,18 @@ extern "C" int himo_pillar_occupancy_reset(void* d_workspace, size_t workspace_b
 static int pillar_args(PillarArgs& a, int64_t n, const float* d_pts, int pc_stride, const float* h_transform, const float* h_range,
                        const float* h_voxel, const float* h_centre_offset, int grid_w, int grid_h, const float* d_pfn_weight,
                        const float* d_pfn_scale, const float* d_pfn_shift, float* d_xyz_t, int32_t* d_pid, float* d_offsets,
-                       float* d_image, int image_pitch, void* d_workspace, size_t workspace_bytes) {
+                       float* d_image, int image_pitch, void* d_workspace, size_t workspace_bytes, bool incremental = false) {
+    // the order of the refusals is the one include/himo_amd.h states: INVALID_ARGUMENT, UNSUPPORTED, WORKSPACE
     if (n < 0 || pc_stride < 3 || grid_w < 1 || grid_h < 1 || !h_transform || !h_range || !h_voxel || !h_centre_offset)
         return HIMO_ERR_INVALID_ARGUMENT;
     if (!d_pfn_weight || !d_pfn_scale || !d_pfn_shift || !d_image || !d_workspace) return HIMO_ERR_INVALID_ARGUMENT;
     if (n > 0 && (!d_pts || !d_xyz_t || !d_pid || !d_offsets)) return HIMO_ERR_INVALID_ARGUMENT;
     if (n > 0x7fffffff || image_pitch < 32) return HIMO_ERR_UNSUPPORTED;
     if ((image_pitch & 3) || (reinterpret_cast<uintptr_t>(d_image) & 15)) return HIMO_ERR_UNSUPPORTED;     // 16-byte row stores
-    const int cells = grid_w * grid_h;
+    if (grid_cells(grid_w, grid_h) > kMaxCells) return HIMO_ERR_UNSUPPORTED;         // grids beyond 1M cells need a third scan level
+    const int cells = (int)grid_cells(grid_w, grid_h);
     if (workspace_bytes < pillar_ws(n, cells) || !aligned16(d_workspace)) return HIMO_ERR_WORKSPACE;
-    if ((cells + kScanBlock - 1) / kScanBlock > 1024) return HIMO_ERR_UNSUPPORTED;   // grids beyond 1M cells need a third scan level
+    if (incremental && ((workspace_bytes & 15) || workspace_bytes < pillar_ws(n, cells) + ws_occ(cells))) return HIMO_ERR_WORKSPACE;
     a = PillarArgs{};
     a.n = n; a.pts = d_pts; a.stride = pc_stride;
     for (int i = 0; i < 9; ++i) a.R[i] = h_transform[(i / 3) * 4 + (i % 3)];
@@ -651,6 +668,19 @@ static int pillar_args(PillarArgs& a, int64_t n, const float* d_pts, int pc_stri
     a.block_sum = reinterpret_cast<int*>(ws + 2 * ws_cells(cells));
     a.cell_rec = reinterpret_cast<float4*>(ws + 2 * ws_cells(cells) + ws_blocks(cells));
     a.order2 = reinterpret_cast<int*>(ws + 2 * ws_cells(cells) + ws_blocks(cells) + 4 * ws_points(n));
+    if (incremental) a.occ = reinterpret_cast<unsigned long long*>(ws + (workspace_bytes - ws_occ(cells)));
+    return HIMO_OK;
+}
+
+// what the multi-sweep forms refuse before any sweep's own arguments are looked at
+static int sweeps_status(int n_sweeps, const himo_sweep* h_sweeps, int image_pitch, int image_split, bool check_shared) {
+    if (n_sweeps < 1 || n_sweeps > kMaxSweeps || !h_sweeps) return HIMO_ERR_INVALID_ARGUMENT;
+    if (image_split && (image_pitch & 15)) return HIMO_ERR_INVALID_ARGUMENT;
+    for (int i = 0; i < n_sweeps; ++i) {
+        if (image_split && (reinterpret_cast<uintptr_t>(h_sweeps[i].d_image) & 63)) return HIMO_ERR_INVALID_ARGUMENT;
+        for (int j = 0; check_shared && j < i; ++j)
+            if (h_sweeps[j].d_workspace == h_sweeps[i].d_workspace) return HIMO_ERR_INVALID_ARGUMENT;     // one workspace per sweep
+    }
     return HIMO_OK;
 }
 
@@ -720,25 +750,16 @@ extern "C" int himo_pillarize_multi_ex(int n_sweeps, const himo_sweep* h_sweeps,
                                        int image_split, void* stream) {
     const bool incremental = (image_split & 2) != 0;                  // HIMO_IMAGE_INCREMENTAL
     image_split &= 1;
-    if (image_split && (image_pitch & 15)) return HIMO_ERR_INVALID_ARGUMENT;
-    if (n_sweeps < 1 || n_sweeps > kMaxSweeps || !h_sweeps) return HIMO_ERR_INVALID_ARGUMENT;
-    if (incremental && ((workspace_bytes & 15) || workspace_bytes < ws_occ(grid_w * grid_h))) return HIMO_ERR_WORKSPACE;
+    const int st0 = sweeps_status(n_sweeps, h_sweeps, image_pitch, image_split, true);
+    if (st0 != HIMO_OK) return st0;
     PillarBatch m{};
     for (int i = 0; i < n_sweeps; ++i) {
         const himo_sweep& w = h_sweeps[i];
         const int st = pillar_args(m.s[i], w.n, w.d_pts, w.pc_stride, w.transform, h_range, h_voxel, h_centre_offset, grid_w, grid_h,
                                    d_pfn_weight, d_pfn_scale, d_pfn_shift, w.d_xyz_t, w.d_pid, w.d_offsets, w.d_image, image_pitch,
-                                   w.d_workspace, workspace_bytes);
+                                   w.d_workspace, workspace_bytes, incremental);
         if (st != HIMO_OK) return st;
-        if (image_split && (reinterpret_cast<uintptr_t>(w.d_image) & 63)) return HIMO_ERR_INVALID_ARGUMENT;
         m.s[i].image_split = image_split ? 1 : 0;
-        if (incremental) {
-            const size_t nb = ws_occ(grid_w * grid_h);
-            if (workspace_bytes < pillar_ws(w.n, grid_w * grid_h) + nb) return HIMO_ERR_WORKSPACE;
-            m.s[i].occ = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(w.d_workspace) + (workspace_bytes - nb));
-        }
-        for (int j = 0; j < i; ++j)
-            if (h_sweeps[j].d_workspace == w.d_workspace) return HIMO_ERR_INVALID_ARGUMENT;     // one workspace per sweep
     }
     return pillar_launch(m, n_sweeps, (hipStream_t)stream);
 }
@@ -764,6 +785,7 @@ extern "C" int himo_pfn_backward(int64_t n, const float* h_voxel, const float* h
         !d_pillar_workspace || !d_dimage || !d_dweight || !d_workspace || image_pitch < 32)
         return HIMO_ERR_INVALID_ARGUMENT;
     if (n > 0 && !d_xyz_t) return HIMO_ERR_INVALID_ARGUMENT;
+    if (n > 0x7fffffff || grid_status(grid_w, grid_h) != HIMO_OK) return HIMO_ERR_UNSUPPORTED;
     if (workspace_bytes < himo_pfn_backward_workspace_bytes()) return HIMO_ERR_WORKSPACE;
     PillarBwdArgs a{};
     a.g.vx = h_voxel[0]; a.g.vy = h_voxel[1]; a.g.vz = h_voxel[2];
@@ -797,6 +819,7 @@ static int pfn_bn_args(PfnBnArgs& p, int64_t n, const float* h_voxel, const floa
     if (n < 0 || !h_voxel || !h_centre_offset || grid_w < 1 || grid_h < 1 || !d_pfn_weight || !d_pillar_workspace || !d_workspace)
         return HIMO_ERR_INVALID_ARGUMENT;
     if (n > 0 && !d_xyz_t) return HIMO_ERR_INVALID_ARGUMENT;
+    if (n > 0x7fffffff || grid_status(grid_w, grid_h) != HIMO_OK) return HIMO_ERR_UNSUPPORTED;
     if (workspace_bytes < himo_pfn_bn_workspace_bytes() || !aligned16(d_workspace)) return HIMO_ERR_WORKSPACE;
     p = PfnBnArgs{};
     PillarBwdArgs& a = p.b;
@@ -826,24 +849,26 @@ extern "C" int himo_pfn_bn_stats_groups(int n_sweeps, int n_groups, const int64_
         return HIMO_ERR_INVALID_ARGUMENT;
     if (!d_gamma || !d_beta || !d_scale || !d_shift || !d_mean || !d_invstd || (d_running_mean == nullptr) != (d_running_var == nullptr))
         return HIMO_ERR_INVALID_ARGUMENT;
+    if (grid_w < 1 || grid_h < 1) return HIMO_ERR_INVALID_ARGUMENT;
+    if (n_groups > kMaxSweeps * kMaxGroup || grid_status(grid_w, grid_h) != HIMO_OK) return HIMO_ERR_UNSUPPORTED;
     const size_t one = himo_pfn_bn_workspace_bytes();
     if (workspace_bytes < one * n_sweeps) return HIMO_ERR_WORKSPACE;
+    std::vector<PfnBnArgs> args((size_t)n_sweeps);   // every sweep's arguments BEFORE the first launch: a refusal launches nothing
+    PfnGroup groups[kMaxSweeps * kMaxGroup];
+    for (int g = 0; g < n_groups; ++g) groups[g].n = 0;
+    for (int i = 0; i < n_sweeps; ++i) {
+        const int st = pfn_bn_args(args[i], h_n[i], h_voxel, h_centre_offset, grid_w, grid_h, d_pfn_weight, h_xyz_t[i], h_pillar_workspace[i],
+                                   reinterpret_cast<char*>(d_workspace) + one * i, one);
+        if (st != HIMO_OK) return st;
+        PfnGroup& G = groups[i % n_groups];
+        G.partial[G.n] = args[i].partial; G.block_sum[G.n] = args[i].b.block_sum; ++G.n;
+    }
     hipStream_t s = (hipStream_t)stream;
     ProfScope ps("pfn_bn_stats_kernel", s);
-    PfnGroup groups[kMaxSweeps * kMaxGroup];
-    if (n_groups > kMaxSweeps * kMaxGroup) return HIMO_ERR_UNSUPPORTED;
-    for (int g = 0; g < n_groups; ++g) groups[g].n = 0;
     for (int lo = 0; lo < n_sweeps; lo += kMaxSweeps) {
         const int cnt = n_sweeps - lo < kMaxSweeps ? n_sweeps - lo : kMaxSweeps;
         PfnBnBatch m{};
-        for (int j = 0; j < cnt; ++j) {
-            const int i = lo + j;
-            const int st = pfn_bn_args(m.s[j], h_n[i], h_voxel, h_centre_offset, grid_w, grid_h, d_pfn_weight, h_xyz_t[i], h_pillar_workspace[i],
-                                       reinterpret_cast<char*>(d_workspace) + one * i, one);
-            if (st != HIMO_OK) return st;
-            PfnGroup& G = groups[i % n_groups];
-            G.partial[G.n] = m.s[j].partial; G.block_sum[G.n] = m.s[j].b.block_sum; ++G.n;
-        }
+        for (int j = 0; j < cnt; ++j) m.s[j] = args[lo + j];
         hipLaunchKernelGGL(pfn_walk_kernel<0>, dim3(kPfnBwdBlocks, cnt), dim3(256), 0, s, m);
     }
     for (int g = 0; g < n_groups; ++g)
@@ -884,23 +909,17 @@ extern "C" int himo_pillar_features_multi(int n_sweeps, const himo_sweep* h_swee
                                           int image_split, void* stream) {
     const bool incremental = (image_split & 2) != 0;
     image_split &= 1;
-    if (image_split && (image_pitch & 15)) return HIMO_ERR_INVALID_ARGUMENT;
-    if (n_sweeps < 1 || n_sweeps > kMaxSweeps || !h_sweeps || !d_scale || !d_shift) return HIMO_ERR_INVALID_ARGUMENT;
-    if (incremental && ((workspace_bytes & 15) || workspace_bytes < ws_occ(grid_w * grid_h))) return HIMO_ERR_WORKSPACE;
+    if (!d_scale || !d_shift) return HIMO_ERR_INVALID_ARGUMENT;
+    const int st0 = sweeps_status(n_sweeps, h_sweeps, image_pitch, image_split, false);
+    if (st0 != HIMO_OK) return st0;
     PillarBatch m{};
     for (int i = 0; i < n_sweeps; ++i) {
         const himo_sweep& w = h_sweeps[i];
         const int st = pillar_args(m.s[i], w.n, w.d_pts, w.pc_stride, w.transform, h_range, h_voxel, h_centre_offset, grid_w, grid_h,
                                    d_pfn_weight, d_scale + 32 * i, d_shift + 32 * i, w.d_xyz_t, w.d_pid, w.d_offsets, w.d_image, image_pitch,
-                                   w.d_workspace, workspace_bytes);
+                                   w.d_workspace, workspace_bytes, incremental);
         if (st != HIMO_OK) return st;
-        if (image_split && (reinterpret_cast<uintptr_t>(w.d_image) & 63)) return HIMO_ERR_INVALID_ARGUMENT;
         m.s[i].image_split = image_split ? 1 : 0;
-        if (incremental) {
-            const size_t nb = ws_occ(grid_w * grid_h);
-            if (workspace_bytes < pillar_ws(w.n, grid_w * grid_h) + nb) return HIMO_ERR_WORKSPACE;
-            m.s[i].occ = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(w.d_workspace) + (workspace_bytes - nb));
-        }
     }
     hipStream_t s = (hipStream_t)stream;
     const int cells = grid_w * grid_h;
@@ -927,6 +946,8 @@ extern "C" int himo_pfn_backward_bn_groups(int n_sweeps, int n_groups, const int
         n_sweeps > kMaxSweeps * kMaxGroup || !h_n || !h_xyz_t || !h_pillar_workspace || !h_dimage)
         return HIMO_ERR_INVALID_ARGUMENT;
     if (!d_scale || !d_shift || !d_mean || !d_invstd || !d_dweight || !d_dgamma || !d_dbeta || image_pitch < 32) return HIMO_ERR_INVALID_ARGUMENT;
+    if (grid_w < 1 || grid_h < 1) return HIMO_ERR_INVALID_ARGUMENT;
+    if (grid_status(grid_w, grid_h) != HIMO_OK) return HIMO_ERR_UNSUPPORTED;
     const size_t one = himo_pfn_bn_workspace_bytes();
     if (workspace_bytes < one * n_sweeps) return HIMO_ERR_WORKSPACE;
     static thread_local PfnBnArgs args[kMaxSweeps * kMaxGroup];
@@ -998,6 +1019,9 @@ extern "C" int himo_head_scatter(int64_t n, int grid_w, int grid_h, const void* 
     if (n < 0 || grid_w < 1 || grid_h < 1 || !d_pillar_workspace || !d_db0 || !d_ddec || dhx_pitch < 128 || n_groups < 1 ||
         b0_pitch < 32 * n_groups || dec_pitch < 64 || (n > 0 && !d_dhx))
         return HIMO_ERR_INVALID_ARGUMENT;
+    // a group index outside [0, n_groups) would drop that sum without a word, and group1 == group0 the second one
+    if (group0 < 0 || group0 >= n_groups || group1 < 0 || group1 >= n_groups || group0 == group1) return HIMO_ERR_INVALID_ARGUMENT;
+    if (n > 0x7fffffff || grid_status(grid_w, grid_h) != HIMO_OK) return HIMO_ERR_UNSUPPORTED;
     PillarBwdArgs a{};
     a.g.W = grid_w; a.g.H = grid_h;
     carve_bwd(a, n, grid_w * grid_h, const_cast<void*>(d_pillar_workspace));

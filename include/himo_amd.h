@@ -373,7 +373,16 @@ int himo_icp_apply(int64_t n, const float* d_pts, int pitch, const int32_t* d_la
  * float32), pillar feature net Linear(9,32)+BN+ReLU+mean -> 32 floats at d_image[cell * image_pitch] (every cell written;
  * d_image 16-byte aligned, image_pitch a multiple of 4 floats).
  * Also returns the transformed points, each point's cell (-1 = out of range) and its offset to the cell
- * centre. */
+ * centre.
+ * The cell count grid_w * grid_h is taken in 64 bits (65536 x 65536 is 2^32 cells, not 0).  Refusals, in the order they are
+ * checked, every one before anything is launched and with no output written:
+ *   1. HIMO_ERR_INVALID_ARGUMENT  n < 0, pc_stride < 3, grid_w < 1 or grid_h < 1, a NULL host array, weight, image or
+ *                                 workspace, a NULL point array or per-point output with n > 0;
+ *   2. HIMO_ERR_UNSUPPORTED       n > 2^31 - 1, image_pitch < 32 or not a multiple of 4, d_image not 16-byte aligned, more
+ *                                 than 1024 x 1024 = 1,048,576 cells (whatever workspace was passed);
+ *   3. HIMO_ERR_WORKSPACE         a workspace that is not 16-byte aligned or shorter than the call needs
+ *                                 (himo_pillar_workspace_bytes(n, ...) always suffices).
+ * himo_pillar_workspace_bytes returns 0 for a point count or a grid that steps 1-2 refuse. */
 size_t himo_pillar_workspace_bytes(int64_t max_points, int grid_w, int grid_h);
 int himo_pillarize(int64_t n, const float* d_pts, int pc_stride, const float* h_transform,
                    const float* h_range, const float* h_voxel, const float* h_centre_offset,
@@ -401,7 +410,15 @@ int himo_pillarize_multi(int n_sweeps, const himo_sweep* h_sweeps, const float* 
  * sweep's workspace (workspace_bytes a multiple of 16, constant per buffer) hold one bit per cell = "non-empty after the
  * previous call"; an empty cell that was empty then is already zero and is skipped -- two thirds of the zero rows of a
  * 120k-point sweep.  Contract: himo_pillar_occupancy_reset() once after allocating the workspace / image (marks every cell
- * dirty), and nobody else writes this sweep's image channels in between. */
+ * dirty), and nobody else writes this sweep's image channels in between.
+ * Refusals of the multi-sweep forms (himo_pillar_features_multi included), in the order they are checked, nothing launched:
+ *   1. HIMO_ERR_INVALID_ARGUMENT  n_sweeps outside [1, 12], h_sweeps NULL (himo_pillar_features_multi: d_scale / d_shift NULL);
+ *                                 HIMO_IMAGE_SPLIT with image_pitch not a multiple of 16 or a sweep's d_image not 64-byte
+ *                                 aligned; two sweeps naming the same workspace (himo_pillarize_multi*);
+ *   2. then sweep by sweep, steps 1-3 of himo_pillarize; with HIMO_IMAGE_INCREMENTAL step 3 (HIMO_ERR_WORKSPACE) also refuses a
+ *      workspace_bytes that is not a multiple of 16 or leaves no room for the occupancy words behind the sweep's lists.
+ * himo_pillar_occupancy_reset: HIMO_ERR_INVALID_ARGUMENT for a NULL workspace or a grid side < 1, HIMO_ERR_UNSUPPORTED beyond
+ * 1,048,576 cells, HIMO_ERR_INVALID_ARGUMENT for a workspace shorter than the occupancy words; in that order. */
 #define HIMO_IMAGE_SPLIT 1
 #define HIMO_IMAGE_INCREMENTAL 2
 int himo_pillar_occupancy_reset(void* d_workspace, size_t workspace_bytes, int grid_w, int grid_h, void* stream);
@@ -720,7 +737,20 @@ int himo_colsum(int64_t n, const float* d_z, int z_pitch, int cout, float* d_out
 /* backward of the pillar stage; d_pillar_workspace = the workspace himo_pillarize(n, ...) of the same sweep left behind.
  * himo_pfn_backward: d loss / d pfn.weight [9][32] from the gradient of the sweep's 32 image channels (flags bit 0:
  * accumulate).  himo_head_scatter: adjoint of himo_head_gather -- per-point rows [d img0 | d img1 | d dec] (128 columns)
- * summed per pillar into channel groups group0 / group1 of d_db0 (other groups and empty cells zeroed) and d_ddec. */
+ * summed per pillar into channel groups group0 / group1 of d_db0 (other groups and empty cells zeroed) and d_ddec.
+ * `n` MUST be the n of the forward call that filled d_pillar_workspace: the cell lists are located inside the workspace from
+ * n (and the grid), so another n reads them from the wrong place.  The same holds for every h_n[i] of the himo_pfn_bn_stats* and
+ * himo_pfn_backward_bn* forms below.  Nothing can check this; it is the caller's contract.
+ * Refusals, in the order they are checked, nothing launched and no output written:
+ *   himo_pfn_backward  1. HIMO_ERR_INVALID_ARGUMENT  n < 0, a grid side < 1, image_pitch < 32, a NULL argument (d_xyz_t may be
+ *                                                    NULL when n == 0);
+ *                      2. HIMO_ERR_UNSUPPORTED       n > 2^31 - 1, more than 1,048,576 cells (grid_w * grid_h in 64 bits);
+ *                      3. HIMO_ERR_WORKSPACE         workspace_bytes < himo_pfn_backward_workspace_bytes().
+ *   himo_head_scatter  1. HIMO_ERR_INVALID_ARGUMENT  n < 0, a grid side < 1, NULL d_pillar_workspace / d_db0 / d_ddec (d_dhx with
+ *                                                    n > 0), dhx_pitch < 128, n_groups < 1, b0_pitch < 32 n_groups,
+ *                                                    dec_pitch < 64; then group0 or group1 outside [0, n_groups), or
+ *                                                    group0 == group1 (either would drop a sum silently; hence n_groups >= 2);
+ *                      2. HIMO_ERR_UNSUPPORTED       n > 2^31 - 1, more than 1,048,576 cells. */
 size_t himo_pfn_backward_workspace_bytes(void);
 int himo_pfn_backward(int64_t n, const float* h_voxel, const float* h_centre_offset, int grid_w, int grid_h,
                       const float* d_pfn_weight, const float* d_pfn_scale, const float* d_pfn_shift,
@@ -866,7 +896,18 @@ size_t himo_pfn_bn_workspace_bytes(void);
  * sweep i belongs to GROUP i % n_groups, and a group shares ONE set of statistics -- with the sweeps ordered sample-major, frame-minor
  * and n_groups = the frames per sample, group f is frame slot f of every sample: what one call of the pillar net on a batch of sweeps
  * normalises over (torch.nn.BatchNorm1d on the concatenated points).  d_scale / d_shift / d_mean / d_invstd are [n_groups][32]; up to 16
- * sweeps per group; the _multi forms are these with every sweep its own group.  Workspace: n_sweeps * himo_pfn_bn_workspace_bytes(). */
+ * sweeps per group; the _multi forms are these with every sweep its own group.  Workspace: n_sweeps * himo_pfn_bn_workspace_bytes().
+ * An empty group (no in-range point in any member): constants from the running statistics (mean 0, variance 1 when not tracked),
+ * d_mean = d_invstd = 0, running statistics untouched.  h_n[i] is the n of sweep i's forward call (see himo_pfn_backward).
+ * Refusals, in the order they are checked, nothing launched and no output written:
+ *   1. HIMO_ERR_INVALID_ARGUMENT  n_sweeps < 1, n_groups < 1, n_sweeps % n_groups != 0, more than 16 sweeps per group (the _multi
+ *                                 forms: n_sweeps > 12; the backward form: n_sweeps > 192), a NULL host array or output, exactly one
+ *                                 of d_running_mean / d_running_var NULL, image_pitch < 32 (backward), a grid side < 1;
+ *   2. HIMO_ERR_UNSUPPORTED       more than 1,048,576 cells (grid_w * grid_h in 64 bits), more than 192 groups;
+ *   3. HIMO_ERR_WORKSPACE         workspace_bytes < n_sweeps * himo_pfn_bn_workspace_bytes();
+ *   4. then sweep by sweep: HIMO_ERR_INVALID_ARGUMENT for h_n[i] < 0, a NULL weight, pillar workspace, workspace (image gradient,
+ *      backward) or d_xyz_t with h_n[i] > 0; HIMO_ERR_UNSUPPORTED for h_n[i] > 2^31 - 1; HIMO_ERR_WORKSPACE for a d_workspace that
+ *      is not 16-byte aligned. */
 int himo_pfn_bn_stats_groups(int n_sweeps, int n_groups, const int64_t* h_n, const float* const* h_xyz_t,
                              const void* const* h_pillar_workspace, const float* h_voxel, const float* h_centre_offset, int grid_w,
                              int grid_h, const float* d_pfn_weight, const float* d_gamma, const float* d_beta, float eps, float momentum,
