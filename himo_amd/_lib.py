@@ -64,6 +64,16 @@ SIGNATURES = {
                               c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "himo_icp_apply": (c_int, [c_int64, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p,
                                c_void_p]),
+    "himo_nsf_forward_keep": (c_int, [c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_void_p]),
+    "himo_nsf_last_grad": (c_int, [c_int64, c_int, c_void_p, c_void_p, c_void_p]),
+    "himo_nsfp_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int, c_int]),
+    "himo_nsfp_partials": (c_int64, [c_int64, c_int64]),
+    "himo_nsfp_prepare": (c_int, [c_int64, c_int64, c_void_p, c_float, c_float, c_float, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "himo_nsfp_objective": (c_int, [c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_int, c_int, c_float,
+                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                    c_void_p]),
+    "himo_nsfp_keep_best": (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_void_p]),
 }
 
 FLAG_F32_CHAIN = 0x1

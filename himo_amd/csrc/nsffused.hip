@@ -157,6 +157,9 @@ __device__ inline void nsf_fwd_gemm(const unsigned char* A, const unsigned short
     }
 }
 
+// KEEP (himo_nsf_forward_keep: the objective runs OUTSIDE this kernel, csrc/nsfp.hip): H_{L-1} leaves as float32 rows in its --
+// otherwise unused -- slot of the spill, for nsf_last_grad_kernel; the instantiation without it is the kernel as it was
+template <bool KEEP>
 __global__ __launch_bounds__(256, 3) void nsf_forward_kernel(NsfFwdArgs a) {
     __shared__ __attribute__((aligned(16))) unsigned char A[2 * kNsfPlane + 64 * 4];      // (+ padding so that Y [64][129] fits)
     __shared__ float s_x[kNsfRows][4];
@@ -249,6 +252,11 @@ __global__ __launch_bounds__(256, 3) void nsf_forward_kernel(NsfFwdArgs a) {
         a.out[(r0 + row) * 4 + c] = s;
         s_o[row][c] = s;
     }
+    if (KEEP) {     // H_{L-1} [64][128] float32 = 32 KiB: exactly the tile's slot of layer L - 1
+        float* __restrict__ hk = reinterpret_cast<float*>(a.spill + ((int64_t)(L - 1) * a.tiles + blockIdx.x) * kNsfTileBytes);
+#pragma unroll 4
+        for (int i = threadIdx.x; i < kNsfRows * kNsfHidden; i += 256) hk[i] = Y[(i >> 7) * 129 + (i & 127)];
+    }
     if (!a.dout) return;
     __syncthreads();
     // the objective for this block's points: moved = x + f(x) -> distance-transform lookup -> d loss / d out (to be scaled by
@@ -294,6 +302,36 @@ __global__ __launch_bounds__(256, 3) void nsf_forward_kernel(NsfFwdArgs a) {
         __syncthreads();
     }
     if (threadIdx.x == 0) { a.loss_partial[blockIdx.x] = s_l[0]; a.count_partial[blockIdx.x] = s_c[0]; }
+}
+
+// the last layer's gradients of one tile from the H_{L-1} a KEEP forward left behind and a d_dout written by ANOTHER objective
+// (csrc/nsfp.hip): the arithmetic and the summation order of nsf_forward_kernel's own closing step, into the same place
+__global__ __launch_bounds__(256) void nsf_last_grad_kernel(const float* __restrict__ dout, const unsigned char* __restrict__ spill, int n_hidden,
+                                                            int tiles, float* __restrict__ last_partial) {
+    __shared__ float s_o[kNsfRows][4];
+    __shared__ float s_w[kNsfHidden][4];
+    const float* __restrict__ H = reinterpret_cast<const float*>(spill + ((int64_t)(n_hidden - 1) * tiles + blockIdx.x) * kNsfTileBytes);
+    (&s_o[0][0])[threadIdx.x] = dout[(int64_t)blockIdx.x * kNsfRows * 4 + threadIdx.x];
+    __syncthreads();
+    const int cc = threadIdx.x & 127, half = threadIdx.x >> 7;
+    float t4[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+    for (int row = half * 32; row < half * 32 + 32; ++row) {
+        const float hv = H[row * kNsfHidden + cc];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) t4[c] = fmaf(hv, s_o[row][c], t4[c]);
+    }
+    if (half == 1) { s_w[cc][0] = t4[0]; s_w[cc][1] = t4[1]; s_w[cc][2] = t4[2]; s_w[cc][3] = t4[3]; }
+    __syncthreads();
+    float* __restrict__ lp = last_partial + (int64_t)blockIdx.x * kNsfLastStride;
+    if (half == 0)
+        *reinterpret_cast<float4*>(lp + cc * 4) = float4{t4[0] + s_w[cc][0], t4[1] + s_w[cc][1], t4[2] + s_w[cc][2], t4[3] + s_w[cc][3]};
+    if (threadIdx.x >= 252) {
+        const int c = threadIdx.x - 252;
+        float sgm = 0.f;
+        for (int row = 0; row < kNsfRows; ++row) sgm += s_o[row][c];
+        lp[4 * kNsfHidden + c] = sgm;
+    }
 }
 
 // ---- backward + every weight gradient ----------------------------------------------------------------------------------------
@@ -707,8 +745,49 @@ extern "C" int himo_nsf_forward(int64_t n, const float* d_x0, int n_hidden, cons
     }
     hipStream_t s = (hipStream_t)stream;
     ProfScope ps("nsf_forward_kernel", s);
-    hipLaunchKernelGGL(nsf_forward_kernel, dim3((unsigned)a.tiles), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(nsf_forward_kernel<false>, dim3((unsigned)a.tiles), dim3(256), 0, s, a);
     HIMO_LAUNCH_CHECK("nsf_forward_kernel");
+    return HIMO_OK;
+}
+
+// himo_nsf_forward without an objective that ALSO keeps H_{L-1} (float32 [64][128] per tile, in layer L - 1's slot of d_spill): the
+// forward pass of an iteration whose objective is computed by other kernels (csrc/nsfp.hip).  himo_nsf_last_grad then turns their
+// d_dout [n][4] (padding rows zero) into the per-tile last-layer gradients himo_nsf_backward expects in d_spill's tail.
+extern "C" int himo_nsf_forward_keep(int64_t n, const float* d_x0, int n_hidden, const float* d_w_first, const float* d_b_first,
+                                     const void* const* h_w_hidden_packed, const float* const* h_b_hidden, const float* d_w_last,
+                                     const float* d_b_last, void* d_spill, float* d_out, void* stream) {
+    if (n < 0 || n_hidden < 1 || n_hidden > kNsfMaxHidden || !d_w_first || !d_b_first || !d_w_last || !d_b_last || !h_w_hidden_packed ||
+        !h_b_hidden || !d_spill || !d_out)
+        return HIMO_ERR_INVALID_ARGUMENT;
+    if (n == 0) return HIMO_OK;
+    if (!d_x0 || !aligned16(d_x0) || !aligned16(d_spill) || !aligned16(d_out)) return HIMO_ERR_INVALID_ARGUMENT;
+    NsfFwdArgs a{};
+    a.n = n; a.n_hidden = n_hidden; a.tiles = (int)nsf_tiles(n); a.x0 = d_x0; a.w_first = d_w_first; a.b_first = d_b_first;
+    a.w_last = d_w_last; a.b_last = d_b_last; a.spill = reinterpret_cast<unsigned char*>(d_spill); a.out = d_out;
+    a.maskbits = reinterpret_cast<unsigned*>(a.spill + nsf_mask_offset(a.tiles, n_hidden));
+    a.last_partial = reinterpret_cast<float*>(a.spill + nsf_last_offset(a.tiles, n_hidden));
+    for (int k = 1; k < n_hidden; ++k) {
+        if (!h_w_hidden_packed[k] || !h_b_hidden[k] || !aligned16(h_w_hidden_packed[k])) return HIMO_ERR_INVALID_ARGUMENT;
+        a.w_hidden[k] = (const unsigned short*)h_w_hidden_packed[k]; a.b_hidden[k] = h_b_hidden[k];
+    }
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps("nsf_forward_keep_kernel", s);
+    hipLaunchKernelGGL(nsf_forward_kernel<true>, dim3((unsigned)a.tiles), dim3(256), 0, s, a);
+    HIMO_LAUNCH_CHECK("nsf_forward_keep_kernel");
+    return HIMO_OK;
+}
+
+extern "C" int himo_nsf_last_grad(int64_t n, int n_hidden, const float* d_dout, void* d_spill, void* stream) {
+    if (n < 0 || n_hidden < 1 || n_hidden > kNsfMaxHidden || !d_spill) return HIMO_ERR_INVALID_ARGUMENT;
+    if (n == 0) return HIMO_OK;
+    if (!d_dout || !aligned16(d_dout) || !aligned16(d_spill)) return HIMO_ERR_INVALID_ARGUMENT;
+    const int tiles = (int)nsf_tiles(n);
+    unsigned char* spill = reinterpret_cast<unsigned char*>(d_spill);
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps("nsf_last_grad_kernel", s);
+    hipLaunchKernelGGL(nsf_last_grad_kernel, dim3((unsigned)tiles), dim3(256), 0, s, d_dout, spill, n_hidden, tiles,
+                       reinterpret_cast<float*>(spill + nsf_last_offset(tiles, n_hidden)));
+    HIMO_LAUNCH_CHECK("nsf_last_grad_kernel");
     return HIMO_OK;
 }
 

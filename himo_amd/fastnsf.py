@@ -114,34 +114,8 @@ def init_mlp(seed: int = 0) -> list:
     return out
 
 
-class FastNSF:
-    def __init__(self, device=None, lr: float = 1e-3, iters: int = 100, seed: int = 0, trunc: float = TRUNC,
-                 early_patience: int = 0, early_min_delta: float = 1e-4, objective: str = "dt", dt_cell: float = DT_CELL, dt_box=None,
-                 precision: str = "mixed", fused: bool = True, three_launch: bool = True):
-        """``fused`` (mixed precision only): the whole forward pass and the whole chain of input gradients as ONE kernel each
-        instead of a row GEMM per layer and direction; with ``three_launch`` (default; "dt" objective) also the objective, every
-        weight gradient and the optimiser step: three launches per iteration (csrc/nsffused.hip) -- ``three_launch=False`` keeps
-        round 3's kernels (csrc/mlpfused.hip + a split-K weight-gradient product per layer), which the tests compare with.
-        ``precision``: "mixed" (default) runs the MLP's products on the 16-bit matrix instructions with split operands -- forward
-        fp16 split (x = h + l: 22-bit products; activations are O(1) and coordinates < 64 m), input gradients and weight gradients
-        two-term bf16 (16 significant bits at float32's range: gradients sit far below fp16's subnormal floor), float32 sums
-        throughout -- as the training step does (seflow/train.py); "f32": float32 matrix instructions everywhere."""
-        if objective not in ("dt", "nn"):
-            raise ValueError(objective)
-        if precision not in ("mixed", "f32"):
-            raise ValueError(precision)
-        self.mixed = precision == "mixed"
-        self.fused = bool(fused) and self.mixed
-        self.three_launch = bool(three_launch)
-        self.lib = _lib.load()
-        self.device = device if device is not None else _lib.require_gpu()
-        self.lr, self.iters, self.seed, self.trunc = lr, iters, seed, trunc
-        self.objective, self.dt_cell, self.dt_box = objective, dt_cell, dt_box
-        self._dt_vol = None                                   # the volume buffer is kept between fits (0.45 GB at the default box)
-        self.early_patience, self.early_min_delta = early_patience, early_min_delta
-        self.loss_history = []
-        self._descs = {}
-        self._defer_finish, self._finish = False, None
+class _MlpParams:
+    """The coordinate MLP's parameters on the device (needs ``lib``, ``device`` and ``mixed``): shared by FastNSF and nsfp.NSFP."""
 
     # ---- parameters: stored padded to multiples of 4 channels (3 -> 4) -----------------------------------------------
     def _load(self, layers):
@@ -187,6 +161,41 @@ class FastNSF:
         """refresh the split copies of every layer's W (forward) and W^T (input gradient): one launch (csrc/convbf.hip)"""
         if self._repack_args is not None:
             _lib.check(self.lib.himo_mlp_repack(*self._repack_args, _lib.stream_handle()), "himo_mlp_repack")
+
+    def layers(self) -> list:
+        """Current parameters as [(W [in,out], b [out])] numpy with the padding removed."""
+        dims = [3] + [HIDDEN] * N_HIDDEN + [3]
+        return [(w.cpu().numpy()[:ci, :co].copy(), b.cpu().numpy()[:co].copy()) for w, b, ci, co in zip(self.W, self.b, dims[:-1], dims[1:])]
+
+
+class FastNSF(_MlpParams):
+    def __init__(self, device=None, lr: float = 1e-3, iters: int = 100, seed: int = 0, trunc: float = TRUNC,
+                 early_patience: int = 0, early_min_delta: float = 1e-4, objective: str = "dt", dt_cell: float = DT_CELL, dt_box=None,
+                 precision: str = "mixed", fused: bool = True, three_launch: bool = True):
+        """``fused`` (mixed precision only): the whole forward pass and the whole chain of input gradients as ONE kernel each
+        instead of a row GEMM per layer and direction; with ``three_launch`` (default; "dt" objective) also the objective, every
+        weight gradient and the optimiser step: three launches per iteration (csrc/nsffused.hip) -- ``three_launch=False`` keeps
+        round 3's kernels (csrc/mlpfused.hip + a split-K weight-gradient product per layer), which the tests compare with.
+        ``precision``: "mixed" (default) runs the MLP's products on the 16-bit matrix instructions with split operands -- forward
+        fp16 split (x = h + l: 22-bit products; activations are O(1) and coordinates < 64 m), input gradients and weight gradients
+        two-term bf16 (16 significant bits at float32's range: gradients sit far below fp16's subnormal floor), float32 sums
+        throughout -- as the training step does (seflow/train.py); "f32": float32 matrix instructions everywhere."""
+        if objective not in ("dt", "nn"):
+            raise ValueError(objective)
+        if precision not in ("mixed", "f32"):
+            raise ValueError(precision)
+        self.mixed = precision == "mixed"
+        self.fused = bool(fused) and self.mixed
+        self.three_launch = bool(three_launch)
+        self.lib = _lib.load()
+        self.device = device if device is not None else _lib.require_gpu()
+        self.lr, self.iters, self.seed, self.trunc = lr, iters, seed, trunc
+        self.objective, self.dt_cell, self.dt_box = objective, dt_cell, dt_box
+        self._dt_vol = None                                   # the volume buffer is kept between fits (0.45 GB at the default box)
+        self.early_patience, self.early_min_delta = early_patience, early_min_delta
+        self.loss_history = []
+        self._descs = {}
+        self._defer_finish, self._finish = False, None
 
     def _gemm(self, x, w, bias, y, n, cin, cout, epi, aux=None, packed=None, fmt=0):
         key = (x.data_ptr(), w.data_ptr(), y.data_ptr(), epi)          # descriptors are cached per call site
@@ -451,11 +460,6 @@ class FastNSF:
     def _gmoved(self, v):
         self._gm_lazy, self._gm_value = None, v
 
-    def layers(self) -> list:
-        """Current parameters as [(W [in,out], b [out])] numpy with the padding removed."""
-        dims = [3] + [HIDDEN] * N_HIDDEN + [3]
-        return [(w.cpu().numpy()[:ci, :co].copy(), b.cpu().numpy()[:co].copy()) for w, b, ci, co in zip(self.W, self.b, dims[:-1], dims[1:])]
-
 
 class OverlappedFastNSF:
     """Two FastNSF engines on two HIP streams: the fit of sweep pair k + 1 is queued while the fit of pair k runs, so one fit's
@@ -468,9 +472,10 @@ class OverlappedFastNSF:
             ...
     """
 
-    def __init__(self, device=None, engines: int = 2, **kw):
+    def __init__(self, device=None, engines: int = 2, engine=None, **kw):
+        """``engine``: the class of the fitting engines (default ``FastNSF``; ``nsfp.NSFP`` has the same ``fit_async`` / ``wait``)"""
         self.device = device if device is not None else _lib.require_gpu()
-        self.engines = [FastNSF(device=self.device, **kw) for _ in range(engines)]
+        self.engines = [(engine or FastNSF)(device=self.device, **kw) for _ in range(engines)]
         self.streams = _lib.shared_streams(self.device, "batch", engines)          # (the pipeline's list: one per process)
         self._turn = 0
         self._busy = [False] * engines

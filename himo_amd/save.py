@@ -316,7 +316,7 @@ def run(dataset, res_name: str = "seflowpp_best", params: dict | None = None, si
     return results if sink is None else done
 
 
-def run_fastnsf(dataset, res_name: str = "fastnsf", sink=None, by_scene: bool = False, iters: int = 100, **fit_options):
+def run_fastnsf(dataset, res_name: str = "fastnsf", sink=None, by_scene: bool = False, iters: int = 100, engine=None, **fit_options):
     """``python save.py model=fastnsf dataset_path=...`` (README.md:53): the optimisation-based baseline instead of the network --
     one coordinate MLP fitted per sweep pair (``himo_amd/fastnsf.py``; PARITY UNPINNED like the network), the flow of every pc0 row
     including ego motion stored under ``res_name`` exactly like the network's.  Two fits in flight on two HIP streams
@@ -325,7 +325,7 @@ def run_fastnsf(dataset, res_name: str = "fastnsf", sink=None, by_scene: bool = 
     from .fastnsf import OverlappedFastNSF
     from .feeder import ResultDrain
     rank, world = (dist.get_rank(), dist.get_world_size()) if dist.is_available() and dist.is_initialized() else (0, 1)
-    nsf = OverlappedFastNSF(iters=iters, **fit_options)
+    nsf = OverlappedFastNSF(iters=iters, engine=engine, **fit_options)
     results = {} if sink is None else None
 
     def deliver(key, flow):
@@ -352,6 +352,14 @@ def run_fastnsf(dataset, res_name: str = "fastnsf", sink=None, by_scene: bool = 
         if hasattr(sink, "close"):
             sink.close()
     return results if sink is None else done
+
+
+def run_nsfp(dataset, res_name: str = "nsfp", sink=None, by_scene: bool = False, iters: int = 5000, **fit_options):
+    """``--model fastnsf --objective nn``: the NSFP baseline (``himo_amd/nsfp.py``, "NSFP, v1"; PARITY UNPINNED) -- the same per-pair MLP fitted
+    on the truncated Chamfer distance with early stopping and its best iterate returned; ``iters`` is the cap.  The walk, the two
+    engines and the writer thread are ``run_fastnsf``'s."""
+    from .nsfp import NSFP
+    return run_fastnsf(dataset, res_name, sink=sink, by_scene=by_scene, iters=iters, engine=NSFP, **fit_options)
 
 
 def run_icpflow(dataset, res_name: str = "icpflow", sink=None, by_scene: bool = False, params=None):
@@ -393,16 +401,25 @@ def run_icpflow(dataset, res_name: str = "icpflow", sink=None, by_scene: bool = 
     return results if sink is None else done
 
 
-def main(checkpoint: str = "", dataset_path: str = "", res_name: str = "", model: str = "", iters: int = 100):
+def main(checkpoint: str = "", dataset_path: str = "", res_name: str = "", model: str = "", iters: int = 100, objective: str = "dt",
+         lr: float = 0.0, patience: int = -1):
     """``python -m himo_amd.save --checkpoint <weights.npz> --dataset_path <dir>`` (the feed-forward network), or
     ``--model fastnsf --dataset_path <dir>`` (the optimisation-based baseline, README.md:50-53), or ``--model icpflow`` (clustering +
-    rigid ICP per cluster; needs the scenes' ground masks); under ``torchrun`` one rank per GPU."""
+    rigid ICP per cluster; needs the scenes' ground masks); under ``torchrun`` one rank per GPU.  ``--model fastnsf --objective nn`` is
+    the NSFP baseline (result key ``nsfp``; ``iters`` is its cap; ``model="nsfp"`` itself is not a spelling this program takes).
+    ``lr=0.0`` / ``patience=-1`` mean the model's own defaults; ``patience=0`` never stops early (NSFP only)."""
     from . import distenv
     from .dataset import SAVE_FIELDS, NpzDataset, open_dataset
     if model not in ("", "seflowpp", "deflowpp", "fastnsf", "icpflow"):
         raise ValueError(f"model={model!r}: this build runs the SeFlow++-style network (default), 'fastnsf' and 'icpflow'")
+    if objective not in ("dt", "nn"):
+        raise ValueError(f"objective={objective!r}: 'dt' (FastNSF's distance transform) or 'nn' (NSFP's truncated Chamfer distance)")
     fastnsf, icpflow = model == "fastnsf", model == "icpflow"
-    name = res_name or ("fastnsf" if fastnsf else "icpflow" if icpflow else (Path(checkpoint).stem if checkpoint else "seflowpp_best"))
+    nsfp = fastnsf and objective == "nn"
+    fit_options = dict(lr=lr) if lr > 0.0 else {}
+    if nsfp and patience >= 0:
+        fit_options["patience"] = patience
+    name = res_name or ("nsfp" if nsfp else "fastnsf" if fastnsf else "icpflow" if icpflow else (Path(checkpoint).stem if checkpoint else "seflowpp_best"))
     params = None
     if checkpoint and not fastnsf and not icpflow:
         from .seflow.checkpoint import load_params
@@ -416,7 +433,8 @@ def main(checkpoint: str = "", dataset_path: str = "", res_name: str = "", model
         sink = NpzResultSink(root, name) if npz else H5ResultSink(root, name, before_write=ds.forget)
         done, err = 0, None
         try:
-            done = (run_fastnsf(ds, name, sink=sink, by_scene=not npz, iters=iters) if fastnsf else
+            done = (run_nsfp(ds, name, sink=sink, by_scene=not npz, iters=iters, **fit_options) if nsfp else
+                    run_fastnsf(ds, name, sink=sink, by_scene=not npz, iters=iters, **fit_options) if fastnsf else
                     run_icpflow(ds, name, sink=sink, by_scene=not npz) if icpflow else
                     run(ds, name, params, sink=sink, by_scene=not npz))
         except Exception as e:                                  # arrive at the rendezvous anyway, then re-raise
@@ -433,10 +451,15 @@ if __name__ == "__main__":
     ap.add_argument("--res_name", default="")
     ap.add_argument("--model", default="", help="'fastnsf': fit the optimisation-based baseline per sweep pair instead of running the network; "
                                                 "'icpflow': clustering + rigid ICP per cluster (needs ground masks: python -m himo_amd.ground_seg)")
-    ap.add_argument("--iters", type=int, default=100, help="optimiser iterations per sweep pair (--model fastnsf)")
+    ap.add_argument("--iters", type=int, default=100, help="optimiser iterations per sweep pair (--model fastnsf); with --objective nn the cap")
+    ap.add_argument("--objective", default="dt", help="--model fastnsf only.  'dt': FastNSF (result key 'fastnsf'); 'nn': the NSFP baseline -- truncated "
+                                                      "Chamfer distance, early stopping, best iterate -- under the result key 'nsfp'.  This is how NSFP "
+                                                      "is spelled: '--model nsfp' is refused")
+    ap.add_argument("--lr", type=float, default=0.0, help="learning rate of the fit (0: the model's own -- fastnsf 1e-3, NSFP 8e-3)")
+    ap.add_argument("--patience", type=int, default=-1, help="NSFP's early-stopping patience (-1: its own, 100; 0: never stop before --iters)")
     import sys
     # the reference's program takes hydra-style overrides (`save.py checkpoint=... dataset_path=...`, `model=fastnsf`: README.md:46-53)
-    argv = [("--" + x) if (not x.startswith("-") and "=" in x and x.split("=", 1)[0] in ("checkpoint", "dataset_path", "res_name", "model", "iters"))
+    argv = [("--" + x) if (not x.startswith("-") and "=" in x and x.split("=", 1)[0] in ("checkpoint", "dataset_path", "res_name", "model", "iters", "objective", "lr", "patience"))
             else x for x in sys.argv[1:]]
     a = ap.parse_args(argv)
-    main(a.checkpoint, a.dataset_path, a.res_name, a.model, a.iters)
+    main(a.checkpoint, a.dataset_path, a.res_name, a.model, a.iters, a.objective, a.lr, a.patience)

@@ -821,6 +821,39 @@ int himo_nsf_update(int total, int n_partials, int64_t partial_stride, const flo
                     float lr, float beta1, float beta2, float eps, int step, int n_hidden, const int* h_off_w, void* const* h_fwd_packed,
                     void* const* h_bwd_packed, double* d_loss, int* d_count, void* stream);
 
+/* ---- NSFP, v1 (result key `nsfp`, tools/view_instance.py:155; the reference's implementation is in the absent OpenSceneFlow
+ * submodule: PARITY UNPINNED, specification himo_amd/nsfp.py) -- the truncated-Chamfer objective on the fused MLP kernels above, and
+ * the early-stopping / keep-best rule on the device (csrc/nsfp.hip).  An iteration is
+ *   himo_nsf_forward_keep -> himo_nsfp_objective -> himo_nsf_last_grad -> himo_nsf_backward -> himo_nsf_update -> himo_nsfp_keep_best.
+ * himo_nsf_forward_keep   himo_nsf_forward without an objective, which also leaves H_{L-1} (float32) in d_spill.
+ * himo_nsf_last_grad      the per-tile last-layer gradients from that H_{L-1} and d_dout, where himo_nsf_backward reads them.
+ * himo_nsfp_prepare       ONCE per sweep pair: d_pc1 [n1][3] binned on the search grid (as himo_nn_grid's: x0, y0, cell, grid_w, grid_h)
+ *                         into d_workspace (himo_nsfp_workspace_bytes), which then belongs to the pair until its last objective step.
+ * himo_nsfp_objective     moved = d_x0 + d_out (both [himo_nsf_padded_rows(n0)][4]) -> d_moved [n0][3]; both exact nearest-neighbour
+ *                         searches (d_dist_a / d_idx_a [n0]: moved -> pc1, d_dist_b / d_idx_b [n1]: pc1 -> moved; squared distances,
+ *                         ties to the lowest row); d_dout [padded][4] = n0 * d L / d out (padding rows zero) and
+ *                         himo_nsfp_partials(n0, n1) loss / count entries whose sums himo_nsf_update divides: loss = L, gradient = dL.
+ *                         The pc1 -> moved half is summed in 2^-40 fixed point: the result does not depend on the order.
+ * himo_nsfp_keep_best     step >= 1 of the stop rule on d_state (8 float64: two slots of best, best_iter, stale, stopped_at; slot 0
+ *                         starts +inf, 0, 0, 0; the state after step t is slot t & 1) with the loss *d_loss; copies d_out to
+ *                         d_best_out (both [padded][4]) when the loss improved by more than min_delta.  patience <= 0 never stops.
+ * n0 == 0: nothing is launched.  n1 == 0: loss 0, zero gradient.  Misaligned (16 bytes) buffers: HIMO_ERR_INVALID_ARGUMENT; a short
+ * workspace: HIMO_ERR_WORKSPACE. */
+int himo_nsf_forward_keep(int64_t n, const float* d_x0, int n_hidden, const float* d_w_first, const float* d_b_first,
+                          const void* const* h_w_hidden_packed, const float* const* h_b_hidden, const float* d_w_last,
+                          const float* d_b_last, void* d_spill, float* d_out, void* stream);
+int himo_nsf_last_grad(int64_t n, int n_hidden, const float* d_dout, void* d_spill, void* stream);
+size_t himo_nsfp_workspace_bytes(int64_t n0, int64_t n1, int grid_w, int grid_h);
+int64_t himo_nsfp_partials(int64_t n0, int64_t n1);
+int himo_nsfp_prepare(int64_t n0, int64_t n1, const float* d_pc1, float x0, float y0, float cell, int grid_w, int grid_h,
+                      void* d_workspace, size_t workspace_bytes, void* stream);
+int himo_nsfp_objective(int64_t n0, int64_t n1, const float* d_x0, const float* d_out, const float* d_pc1, float x0, float y0,
+                        float cell, int grid_w, int grid_h, float trunc_dist, float* d_moved, float* d_dist_a, int32_t* d_idx_a,
+                        float* d_dist_b, int32_t* d_idx_b, float* d_dout, double* d_loss_partial, int* d_count_partial,
+                        void* d_workspace, size_t workspace_bytes, void* stream);
+int himo_nsfp_keep_best(int64_t n, const float* d_out, float* d_best_out, const double* d_loss, double* d_state, int step,
+                        int patience, double min_delta, void* stream);
+
 /* FastNSF's coordinate MLP (3 -> 128 x n_hidden, ReLU -> 3; himo_amd/fastnsf.py) over all n points as ONE kernel per direction
  * (csrc/mlpfused.hip): the forward pass writes the post-ReLU activations h_H[k] [n][128] and d_out [n][4]; the backward pass turns
  * d_dout [n][4] into the masked gradients h_dZ[k] [n][128] at every hidden layer's output.  Hidden layer k = 1 .. n_hidden - 1 is
