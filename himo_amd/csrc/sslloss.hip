@@ -15,6 +15,9 @@
 //                          to pc1 among members whose raw neighbour is itself dynamic (label1 > 0; ties: lowest
 //                          index) and t_c = pc1[NN_raw(a_c)] - pc0[a_c]; clusters without such a member are skipped
 //   total = sum of the four.  Correspondences are treated as constants in the gradient.
+//   Labels >= n_labels are dynamic for the Chamfer subsets, not part of the cluster term, and not static; negative labels take part in
+//   the full Chamfer only.  (oracle/sslloss_oracle.py: ssl_loss_f64 is the float64 statement of all of this with the tie rules made
+//   explicit; tests/test_sslloss_conformance_gpu.py holds every entry point below to it.)
 //
 // All nearest-neighbour searches run through nngrid.hip (exact): the full sweeps are binned once and searched in ONE launch
 // (moved -> pc1, pc1 -> moved, and pc0 -> pc1 unless the caller supplies it), the dynamic subsets in a second one.  Loss sums are fixed two-level trees
