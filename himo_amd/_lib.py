@@ -52,6 +52,10 @@ SIGNATURES = {
                                     c_int, c_uint, c_void_p, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
     "himo_seg_confusion": (c_int, [c_int64, c_void_p, ctypes.POINTER(c_void_p), c_int, c_void_p, ctypes.POINTER(ctypes.c_uint8),
                                    c_void_p, c_void_p]),
+    "himo_flow_metrics_workspace_bytes": (c_size_t, [c_int]),
+    "himo_flow_metrics_batch": (c_int, [c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                        ctypes.POINTER(c_void_p), c_int, c_void_p, c_void_p, c_void_p, ctypes.POINTER(ctypes.c_uint8),
+                                        c_double, c_uint, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "himo_box_label_batch": (c_int, [c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "himo_ground_seg_workspace_bytes": (c_size_t, [c_int, c_void_p]),

@@ -132,6 +132,9 @@ _LOADER_KEYS = frozenset(("scene_id", "timestamp", "pc0", "pose0", "pose1", "pc1
 # the next sweep's points); the estimate's key (``res_name``) joins them
 EVAL_FIELDS = ("pc0", "pose0", "pose1", "lidar_dt", "gm0", "flow", "flow_is_valid", "flow_category_indices", "flow_instance_id")
 
+# ... and the ones the scene-flow evaluator reads beside its result names (eval_flow.py): no time stamps, no instance ids
+FLOW_EVAL_FIELDS = ("pc0", "pose0", "pose1", "gm0", "flow", "flow_is_valid", "flow_category_indices")
+
 
 class _OpenFiles:
     """The most recently used scene files, kept OPEN (a walk reads every sweep of a scene in turn, and each sweep three times:

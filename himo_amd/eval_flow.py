@@ -1,0 +1,504 @@
+"""The scene-flow evaluator: three-way and bucketed end-point error of ``<res_name>`` against the ground-truth ``flow``.
+
+    python -m himo_amd.eval_flow --data_dir D --res_names seflowpp_best,fastnsf,nsfp,icpflow,raw
+
+PARITY UNPINNED.  The reference scores flow in its absent ``OpenSceneFlow`` submodule (``eval.py:21`` imports the tables of
+``src.utils.av2_eval``), so there is no source to hold this against.  What runs here is this package's own written rule,
+"flow metrics, v1", which follows the published three-way EPE and the Argoverse-2 bucketed normalised EPE; no claim is made about
+the numbers the reference's program would print.
+
+The rule.  All arithmetic is IEEE double on the float32 inputs, every operation rounded on its own.  For sweep f with
+``T = inv(pose1) @ pose0`` and point i:
+  1. counted: the package's evaluation mask (BEV range <= 35 m, not ground, outside the ego box; Scania: ``flow_is_valid`` too).
+  2. ``g = gt - pose_flow`` (``pose_flow = T p - p``), ``speed = sqrt((gx gx + gy gy) + gz gz)``.
+  3. result r: ``d = est_r - gt`` (``raw``: no estimate, ego motion only: ``d = -g``), ``epe = sqrt((dx dx + dy dy) + dz dz)``.
+  4. a counted point whose estimate has a non-finite component or whose ``epe >= 1024 m`` (or is NaN) is *rejected* for r:
+     counted in ``rejected[r]``, part of nothing else.
+  5. ``q(x) = llrint(x * 2^24)``; every sum is an int64 sum of ``q(epe)`` / ``q(speed)``: the unit is 2^-24 m, and block order,
+     batch size and rank count cannot change a digit.
+  6. classes 0..4 = BACKGROUND, CAR, OTHER_VEHICLES, PEDESTRIAN, WHEELED_VRU (``eval.BUCKETED_METACATAGORIES``); 5 = every other
+     category: foreground, in no bucket.
+  7. three-way, per sweep: dynamic = ``speed > 0.5 sensor_dt``; FD / FS = foreground dynamic / static, BS = background static.
+     A kind's value is the mean over the sweeps that have such points of the sweep's mean EPE; ``three_way`` the mean of the three.
+  8. buckets, over the run: bucket = #{k in 1..50: speed >= k * 0.4 sensor_dt}.  Static EPE of a class = mean EPE of bucket 0;
+     dynamic normalised EPE = mean over the occupied buckets b >= 1 of sum(epe) / sum(speed).
+
+What runs where: rules 1-6 and the sums run in one HIP kernel per packed batch of sweeps for up to 8 results at once
+(csrc/flowmetrics.hip, ``himo_flow_metrics_batch``); the means of rules 7-8 are pure numpy on the integer tables and work
+without a GPU (``FlowMetrics.from_counts``).  With ``torch.distributed`` initialised sweep i runs on rank i % world.
+"""
+from __future__ import annotations
+
+import ctypes
+import json
+import os
+import time
+
+import numpy as np
+
+from . import _lib
+from .eval import BUCKETED_METACATAGORIES, CATEGORY_TO_INDEX
+from .eval_seg import as_labels_u8, parse_res_names  # noqa: F401  (parse_res_names is part of this module's interface)
+
+CLASS_NAMES = ("BACKGROUND", "CAR", "OTHER_VEHICLES", "PEDESTRIAN", "WHEELED_VRU")
+KINDS = ("FD", "FS", "BS")
+MAX_RESULTS = 8                      # HIMO_FLOWM_MAX_RESULTS
+CLASSES = len(CLASS_NAMES)           # HIMO_FLOWM_CLASSES
+BUCKETS = 51                         # HIMO_FLOWM_BUCKETS
+OTHER_FOREGROUND = 5
+UNIT = float(2 ** 24)                # quantisation units per metre
+
+
+def class_lut() -> np.ndarray:
+    """uint8[256]: category index -> 0..4 (``CLASS_NAMES``) | 5 (any other category: foreground, in no bucket)"""
+    lut = np.full(256, OTHER_FOREGROUND, dtype=np.uint8)
+    seen = set()
+    for cid, name in enumerate(CLASS_NAMES):
+        idx = [CATEGORY_TO_INDEX[c] for c in BUCKETED_METACATAGORIES[name]]
+        if seen & set(idx):
+            raise ValueError("the meta-categories of eval.BUCKETED_METACATAGORIES overlap: no single class table stands for them")
+        seen |= set(idx)
+        lut[idx] = cid
+    return lut
+
+
+def data_name_of(data_dir: str) -> str:
+    """the package's substring sniff (``utils.check_valid``: a match at position 0 does not count)"""
+    hit = lambda s: str(data_dir).find(s) > 0      # noqa: E731
+    if hit("Scania") or hit("scania"):
+        return "scania"
+    if hit("av2") or hit("AV2"):
+        return "av2"
+    raise ValueError("Unknown dataset name in data_dir.")
+
+
+def flow_metrics(buckets, threeway, rejected, offsets, pose0, pose1, pc0, gt, ests, category, ground, valid=None, lut=None,
+                 sensor_dt: float = 0.1, scania: bool = False, pose_is_ego: bool = False, workspace=None) -> None:
+    """One launch on the current stream: the device int64 tables ``buckets`` [R][5][51][3], ``threeway`` [F][R][3][2] and
+    ``rejected`` [R] += the packed batch (``offsets`` int64 [F+1], poses float64 [F][4][4], ``pc0`` float32 [T][S] rows,
+    ``gt`` float32 [T][3], ``ests``: R float32 [T][3] tensors or None for ``raw``, ``category`` / ``ground`` / ``valid`` uint8 [T]).
+    Never synchronises."""
+    import torch
+    from .compdis import CLOSE_DISTANCE_DEFAULT, CLOSE_DISTANCE_THRESHOLD
+    if CLOSE_DISTANCE_THRESHOLD != CLOSE_DISTANCE_DEFAULT:
+        raise ValueError(f"flow metrics v1 count points within {CLOSE_DISTANCE_DEFAULT:g} m; HIMO_CLOSE_DISTANCE_THRESHOLD is set to another range")
+    lib = _lib.load()
+    lut = class_lut() if lut is None else np.ascontiguousarray(lut, dtype=np.uint8)
+    if lut.shape != (256,):
+        raise ValueError("the class table has 256 entries")
+    r, n_frames, total = len(ests), int(offsets.numel()) - 1, int(pc0.shape[0])
+    if not 1 <= r <= MAX_RESULTS:
+        raise ValueError(f"{r} results: himo_flow_metrics_batch takes 1..{MAX_RESULTS}")
+    if pc0.dim() != 2 or pc0.shape[1] < 3 or pc0.dtype != torch.float32 or (total and (pc0.stride(1) != 1 or pc0.stride(0) < 3)):
+        raise ValueError("pc0 must be float32 rows of at least 3 unit-stride columns")
+    pc_stride = int(pc0.stride(0)) if total else int(pc0.shape[1])        # (an empty tensor's strides say nothing)
+    for name, t, shape, dtype in ([("gt", gt, (total, 3), torch.float32), ("category", category, (total,), torch.uint8),
+                                   ("ground", ground, (total,), torch.uint8), ("buckets", buckets, (r, CLASSES, BUCKETS, 3), torch.int64),
+                                   ("threeway", threeway, (n_frames, r, 3, 2), torch.int64), ("rejected", rejected, (r,), torch.int64),
+                                   ("pose0", pose0, (n_frames, 4, 4), torch.float64)]
+                                  + ([("pose1", pose1, (n_frames, 4, 4), torch.float64)] if pose1 is not None else [])
+                                  + ([("valid", valid, (total,), torch.uint8)] if valid is not None else [])
+                                  + [(f"result {k}", e, (total, 3), torch.float32) for k, e in enumerate(ests) if e is not None]):
+        if tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape {shape}, not {t.dtype} {tuple(t.shape)}")
+    if scania and valid is None:
+        raise KeyError("flow_is_valid")
+    need = int(lib.himo_flow_metrics_workspace_bytes(n_frames))
+    if workspace is None:
+        workspace = torch.empty(need + 16, dtype=torch.uint8, device=pc0.device)
+    if workspace.numel() < need:
+        raise ValueError("workspace smaller than himo_flow_metrics_workspace_bytes")
+    flags = (_lib.FLAG_SCANIA if scania else 0) | (_lib.FLAG_POSE_IS_EGO if pose_is_ego else 0)
+    ptrs = (ctypes.c_void_p * r)(*[_lib.ptr(e) if total else None for e in ests])
+    _lib.check(lib.himo_flow_metrics_batch(
+        n_frames, total, _lib.ptr(offsets), _lib.ptr(pose0), _lib.ptr(pose1), _lib.ptr(pc0), pc_stride, _lib.ptr(gt), ptrs, r,
+        _lib.ptr(category), _lib.ptr(ground), _lib.ptr(valid), lut.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), float(sensor_dt), flags,
+        _lib.ptr(buckets), _lib.ptr(threeway), _lib.ptr(rejected), _lib.ptr(workspace), _lib.stream_handle()), "himo_flow_metrics_batch")
+
+
+class FlowBatch:
+    """A packed batch of sweeps on the device (sweep k owns rows ``offsets_host[k]:offsets_host[k + 1]``); ``ests[r]`` is None for
+    ``raw``; ``keys[k]`` is sweep k's dataset index."""
+
+    def __init__(self, offsets_host, offsets, pose0, pose1, pc0, gt, ests, category, ground, valid, keys, pose_is_ego=False):
+        self.offsets_host, self.offsets, self.pose0, self.pose1, self.pc0, self.gt = offsets_host, offsets, pose0, pose1, pc0, gt
+        self.ests, self.category, self.ground, self.valid, self.keys, self.pose_is_ego = ests, category, ground, valid, list(keys), pose_is_ego
+
+    @property
+    def sweeps(self) -> int:
+        return len(self.offsets_host) - 1
+
+    @property
+    def total_points(self) -> int:
+        return int(self.offsets_host[-1])
+
+    @classmethod
+    def from_frames(cls, frames, res_names, device=None, upload=None, keys=None) -> "FlowBatch":
+        """``frames``: dicts with ``pc0``, ``pose0``, ``pose1``, ``gm0``, ``flow``, ``flow_category_indices``, every stored name of
+        ``res_names`` (``raw`` packs nothing) and, for Scania, ``flow_is_valid`` (packed when every frame has it).  A missing key
+        is a ``KeyError``; an array whose length differs from ``pc0``'s raises ``ValueError`` naming the sweep.
+        ``upload(parts, dtype)``: the feeder's staging (``feeder.BatchFeeder``); None: one plain copy per array."""
+        from .compdis import host_upload
+        frames = list(frames)
+        if not frames:
+            raise ValueError("empty batch")
+        if upload is None:
+            upload = host_upload(device if device is not None else _lib.require_gpu())
+        counts = [int(np.asarray(f["pc0"]).shape[0]) for f in frames]
+        offsets = np.zeros(len(frames) + 1, dtype=np.int64)
+        np.cumsum(counts, out=offsets[1:])
+
+        def cat(key, dtype, width=None, labels=False):
+            parts = []
+            for f, n in zip(frames, counts):
+                a = as_labels_u8(f[key]) if labels else np.asarray(f[key])
+                if a.shape[0] != n or (width is not None and a.shape[1:] != (width,)):
+                    raise ValueError(f"{f.get('scene_id')} at {f.get('timestamp')}: {key} has shape {a.shape} for a sweep of {n} points")
+                parts.append(a)
+            return upload(parts, dtype)
+        return cls(offsets, upload([offsets], np.int64),
+                   upload([np.stack([np.asarray(f["pose0"], dtype=np.float64) for f in frames])], np.float64),
+                   upload([np.stack([np.asarray(f["pose1"], dtype=np.float64) for f in frames])], np.float64),
+                   cat("pc0", np.float32), cat("flow", np.float32, 3),
+                   [None if name == "raw" else cat(name, np.float32, 3) for name in res_names],
+                   cat("flow_category_indices", np.uint8, labels=True), cat("gm0", np.uint8, labels=True),
+                   cat("flow_is_valid", np.uint8, labels=True) if all("flow_is_valid" in f for f in frames) else None,
+                   keys if keys is not None else range(len(frames)))
+
+
+def _nanmean(values) -> float:
+    v = [x for x in values if not np.isnan(x)]
+    return float(np.mean(v)) if v else float("nan")
+
+
+class FlowMetrics:
+    """The batched evaluator: the integer tables of ``res_names`` -- ``buckets`` int64 [R][5][51][3] (count, sum q(epe),
+    sum q(speed)), ``threeway`` {dataset index: int64 [R][3][2]} (count, sum q(epe) of FD, FS, BS) and ``rejected`` int64 [R] --
+    fed whole batches of sweeps, and the float64 means made of them.  The three are host views: reading one waits for the
+    device and folds its tables in; assigning one replaces the counts."""
+
+    def __init__(self, res_names, data_name: str, sensor_dt: float = 0.1, device=None):
+        self.res_names = parse_res_names(res_names)
+        if len(self.res_names) > MAX_RESULTS:
+            raise ValueError(f"{len(self.res_names)} result names: at most {MAX_RESULTS} are evaluated in one pass")
+        if data_name not in ("av2", "scania"):
+            raise ValueError(f"data_name {data_name!r}: 'av2' or 'scania'")
+        self.data_name, self.sensor_dt, self.device = data_name, float(sensor_dt), device
+        self.lut = class_lut()
+        self._dev = self._ws = None
+        self.reset()
+
+    @classmethod
+    def from_counts(cls, res_names, data_name: str, buckets, threeway, rejected=None, sensor_dt: float = 0.1) -> "FlowMetrics":
+        """the evaluator holding host-set tables (no GPU involved)"""
+        m = cls(res_names, data_name, sensor_dt)
+        m.buckets, m.threeway = buckets, threeway
+        if rejected is not None:
+            m.rejected = rejected
+        m.frame_cnt = len(m._threeway)
+        return m
+
+    def reset(self) -> None:
+        r = len(self.res_names)
+        self._buckets = np.zeros((r, CLASSES, BUCKETS, 3), dtype=np.int64)
+        self._rejected = np.zeros(r, dtype=np.int64)
+        self._threeway = {}
+        self._pending = []                    # (dataset indices, device [F][R][3][2]) of the launches not folded in yet
+        if self._dev is not None:
+            self._dev[0].zero_()
+            self._dev[1].zero_()
+        self.frame_cnt = 0
+        self._next_key = 0
+
+    # ---- device side -----------------------------------------------------------------------------------------------
+    def add_batch(self, batch: FlowBatch) -> None:
+        import torch
+        r = len(self.res_names)
+        if len(batch.ests) != r:
+            raise ValueError(f"the batch packs {len(batch.ests)} results, the evaluator has {r} names")
+        if self._dev is None:
+            self.device = self.device if self.device is not None else _lib.require_gpu()
+            self._dev = (torch.zeros(self._buckets.shape, dtype=torch.int64, device=self.device),
+                         torch.zeros(r, dtype=torch.int64, device=self.device))
+        need = int(_lib.load().himo_flow_metrics_workspace_bytes(batch.sweeps))
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need + 16, dtype=torch.uint8, device=self.device)
+        tw = torch.zeros((batch.sweeps, r, 3, 2), dtype=torch.int64, device=self.device)
+        flow_metrics(self._dev[0], tw, self._dev[1], batch.offsets, batch.pose0, batch.pose1, batch.pc0, batch.gt, batch.ests,
+                     batch.category, batch.ground, batch.valid, self.lut, self.sensor_dt, scania=self.data_name == "scania",
+                     pose_is_ego=batch.pose_is_ego, workspace=self._ws)
+        self._pending.append((list(batch.keys), tw))
+        self.frame_cnt += batch.sweeps
+
+    def add(self, frames, keys=None) -> None:
+        """the sweeps of ``frames`` (host dicts) as one packed batch, one launch; ``keys``: their dataset indices (default: the
+        running count of sweeps added)"""
+        frames = list(frames)
+        if not frames:
+            return
+        if keys is None:
+            keys = range(self._next_key, self._next_key + len(frames))
+        keys = [int(k) for k in keys]
+        self._next_key = max(self._next_key, max(keys) + 1)
+        self.add_batch(FlowBatch.from_frames(frames, self.res_names, device=self.device, keys=keys))
+
+    def _fold(self) -> None:
+        if self._dev is not None and self._pending:
+            self._buckets = self._buckets + self._dev[0].cpu().numpy()
+            self._rejected = self._rejected + self._dev[1].cpu().numpy()
+            self._dev[0].zero_()
+            self._dev[1].zero_()
+            for keys, tw in self._pending:
+                self._merge_threeway(zip(keys, tw.cpu().numpy()))
+            self._pending = []
+
+    def _merge_threeway(self, items) -> None:
+        for key, words in items:
+            have = self._threeway.get(int(key))
+            self._threeway[int(key)] = np.array(words, dtype=np.int64) if have is None else have + words
+
+    # ---- host views ------------------------------------------------------------------------------------------------
+    @property
+    def buckets(self) -> np.ndarray:
+        self._fold()
+        return self._buckets
+
+    @buckets.setter
+    def buckets(self, value):
+        self._fold()
+        self._buckets = np.array(value, dtype=np.int64).reshape(self._buckets.shape)
+
+    @property
+    def rejected(self) -> np.ndarray:
+        self._fold()
+        return self._rejected
+
+    @rejected.setter
+    def rejected(self, value):
+        self._fold()
+        self._rejected = np.array(value, dtype=np.int64).reshape(self._rejected.shape)
+
+    @property
+    def threeway(self) -> dict:
+        """{dataset index: int64 [R][3][2]}, in dataset order"""
+        self._fold()
+        self._threeway = dict(sorted(self._threeway.items()))
+        return self._threeway
+
+    @threeway.setter
+    def threeway(self, value):
+        self._fold()
+        r = len(self.res_names)
+        self._threeway = {int(k): np.array(v, dtype=np.int64).reshape(r, 3, 2) for k, v in dict(value).items()}
+
+    def gather(self) -> None:
+        """Over the ranks of the process group: ONE all-reduce of the bucket and rejected integers and one gather of the per-sweep
+        three-way words, which every rank then holds ordered by dataset index.  Integer sums: every rank ends with exactly the
+        single-process tables."""
+        import torch
+        import torch.distributed as dist
+        self._fold()
+        if not (dist.is_available() and dist.is_initialized()):
+            return
+        t = torch.from_numpy(np.concatenate([self._buckets.reshape(-1), self._rejected, [self.frame_cnt]]).astype(np.int64))
+        if dist.get_backend() == "nccl":
+            t = t.to(torch.device("cuda", torch.cuda.current_device()))
+        dist.all_reduce(t, op=dist.ReduceOp.SUM)
+        flat = t.cpu().numpy()
+        nb = self._buckets.size
+        self._buckets = flat[:nb].reshape(self._buckets.shape).copy()
+        self._rejected = flat[nb:-1].copy()
+        self.frame_cnt = int(flat[-1])
+        parts = [None] * dist.get_world_size()
+        dist.all_gather_object(parts, sorted(self._threeway.items()))
+        self._threeway = {}
+        self._merge_threeway(sorted((item for part in parts for item in part), key=lambda kv: kv[0]))
+
+    # ---- rules 7 and 8: float64 on the integers ---------------------------------------------------------------------
+    def results(self) -> dict:
+        """{name: {"three_way", "FD", "FS", "BS", "static": {class: m}, "dynamic": {class: ratio}, "mean_static", "mean_dynamic",
+        "counted", "rejected"}}; a kind or class with nothing counted is nan.  ``counted`` = the points that entered the sums."""
+        buckets, rejected, threeway = self.buckets, self.rejected, self.threeway
+        out = {}
+        for r, name in enumerate(self.res_names):
+            tw = np.stack([v[r] for v in threeway.values()]) if threeway else np.zeros((0, 3, 2), dtype=np.int64)
+            res = {}
+            for k, kind in enumerate(KINDS):
+                has = tw[:, k, 0] > 0
+                per_sweep = tw[has, k, 1].astype(np.float64) / tw[has, k, 0].astype(np.float64) / UNIT
+                res[kind] = float(per_sweep.mean()) if per_sweep.size else float("nan")
+            res["three_way"] = float(np.mean([res[k] for k in KINDS]))
+            static, dynamic = {}, {}
+            for c, cname in enumerate(CLASS_NAMES):
+                b = buckets[r, c]
+                static[cname] = float(np.float64(b[0, 1]) / np.float64(b[0, 0]) / UNIT) if b[0, 0] > 0 else float("nan")
+                has = np.flatnonzero(b[1:, 0] > 0) + 1
+                ratios = b[has, 1].astype(np.float64) / b[has, 2].astype(np.float64)
+                dynamic[cname] = float(ratios.mean()) if ratios.size else float("nan")
+            res["static"], res["dynamic"] = static, dynamic
+            res["mean_static"], res["mean_dynamic"] = _nanmean(static.values()), _nanmean(dynamic.values())
+            res["counted"] = int(buckets[r, 0, :, 0].sum() + tw[:, :2, 0].sum())
+            res["rejected"] = int(rejected[r])
+            res = {k: res[k] for k in ("three_way",) + KINDS + ("static", "dynamic", "mean_static", "mean_dynamic", "counted", "rejected")}
+            out[name] = res
+        return out
+
+    def table(self) -> str:
+        """one text block per result name: the five classes' static EPE [m] and dynamic normalised EPE, then the three-way line"""
+        fmt = lambda v: "-" if np.isnan(v) else f"{v:.6f}"      # noqa: E731
+        width = max(len(c) for c in CLASS_NAMES) + 2
+        out = []
+        for name, res in self.results().items():
+            out.append(f"\nFlow metrics (v1) for {name} in {self.data_name}: {self.frame_cnt} sweeps, {res['counted']} points, "
+                       f"{res['rejected']} rejected")
+            out.append(f"{'':<9}" + "".join(f"{c:>{width}}" for c in CLASS_NAMES) + f"{'mean':>{width}}")
+            for row in ("static", "dynamic"):
+                out.append(f"{row:<9}" + "".join(f"{fmt(res[row][c]):>{width}}" for c in CLASS_NAMES) + f"{fmt(res['mean_' + row]):>{width}}")
+            out.append(f"three-way {fmt(res['three_way'])}  FD {fmt(res['FD'])}  FS {fmt(res['FS'])}  BS {fmt(res['BS'])}")
+        return "\n".join(out) + "\n"
+
+
+def merge_json(path, results: dict) -> dict:
+    """``{res_name: results}`` merged into the JSON object of ``path`` (created when absent; nan is written as NaN)"""
+    data = {}
+    if os.path.exists(path):
+        try:
+            with open(path) as f:
+                data = json.load(f)
+        except json.JSONDecodeError:
+            data = {}
+    data.update(results)
+    with open(path, "w") as f:
+        json.dump(data, f, indent=4)
+    return data
+
+
+class _MissingKey(Exception):
+    """carries the warnings printed before a KeyError to the thread that prints"""
+
+    def __init__(self, key, lines):
+        super().__init__(key)
+        self.key, self.lines = key, list(lines)
+
+
+def run_dataset(dataset, metrics: FlowMetrics, batch_frames: int = 32, overlap: bool = True) -> int:
+    """Shared body of ``main``: sweep i of ``dataset`` on rank i % world, ``batch_frames`` sweeps per launch.  A sweep without
+    ``flow`` or ``flow_category_indices`` is skipped with a warning line; one that lacks a stored result name (or another array
+    the rule reads) raises ``KeyError`` naming it.  With ``overlap`` the batches are read, packed and copied two ahead by
+    ``feeder.BatchFeeder``.  Returns the sweeps this rank evaluated."""
+    from .save_zip import _dist
+    rank, world, _ = _dist()
+    mine = list(range(rank, len(dataset), world))
+    names = metrics.res_names
+    required = ["pc0", "pose0", "pose1", "gm0"] + (["flow_is_valid"] if metrics.data_name == "scania" else []) + [n for n in names if n != "raw"]
+
+    def batches():
+        for lo in range(0, len(mine), batch_frames):
+            frames, keys, lines = [], [], []
+            for i in mine[lo:lo + batch_frames]:
+                f = dataset[i]
+                lacking = [k for k in ("flow", "flow_category_indices") if k not in f]
+                if lacking:
+                    lines += [f"[Warning]: No {k} in {f['scene_id']} at {f['timestamp']}, check the data." for k in lacking]
+                    continue
+                for key in required:
+                    if key not in f:
+                        lines.append(f"[Warning]: No {key} in {f['scene_id']} at {f['timestamp']}, check the data.")
+                        raise _MissingKey(key, lines)
+                frames.append(f)
+                keys.append(i)
+            yield frames, keys, lines
+
+    def show(lines):
+        for line in lines:
+            print(line)
+
+    done = 0
+    if not overlap:
+        try:
+            for frames, keys, lines in batches():
+                show(lines)
+                metrics.add(frames, keys)
+                done += len(frames)
+        except _MissingKey as e:
+            show(e.lines)
+            raise KeyError(e.key) from None
+        return done
+
+    from .feeder import BatchFeeder
+    dev = metrics.device if metrics.device is not None else _lib.require_gpu()
+    metrics.device = dev
+
+    def build(item, upload):
+        frames, keys, lines = item
+        batch = FlowBatch.from_frames(frames, names, device=dev, upload=upload, keys=keys) if frames else None
+        return (batch, lines), []                   # (the feeder keeps the staged blocks alive itself)
+    feed = BatchFeeder(batches(), build, device=dev)
+    try:
+        for batch, lines in feed:
+            show(lines)
+            if batch is not None:
+                metrics.add_batch(batch)
+                done += batch.sweeps
+    except _MissingKey as e:
+        feed.close()
+        show(e.lines)
+        raise KeyError(e.key) from None
+    except BaseException:
+        feed.close()
+        raise
+    return done
+
+
+def main(data_dir: str = "/home/kin/data/av2/h5py/sensor/himo", res_names="seflowpp_best,raw", data_name: str = "auto",
+         batch_frames: int = 32, json_path: str = "", dataset=None):
+    """Evaluate ``res_names`` over the sweeps of ``index_eval.pkl``.  ``data_name``: "av2" | "scania" | "auto" (sniffed from
+    ``data_dir``).  Under ``torchrun`` sweep i is counted by rank i % world on its own GPU; rank 0 prints the tables and, with
+    ``json_path``, merges ``{res_name: results}`` into that file.  Returns the ``FlowMetrics``."""
+    from . import distenv
+    from .dataset import FLOW_EVAL_FIELDS, open_dataset
+
+    names = parse_res_names(res_names)
+    if data_name == "auto":
+        data_name = data_name_of(data_dir)
+    with distenv.process_group() as (rank, world):
+        metrics = FlowMetrics(names, data_name)
+        err = None
+        t0 = time.perf_counter()
+        try:
+            if dataset is None:
+                stored = [n for n in names if n != "raw"]
+                dataset = open_dataset(data_dir, vis_name=stored, eval=True, fields=FLOW_EVAL_FIELDS + tuple(stored), zero_copy=True)
+            done = run_dataset(dataset, metrics, batch_frames=batch_frames)
+            metrics.buckets                                      # (wait for the device: the loop's time includes its kernels)
+            metrics.loop = {"seconds": time.perf_counter() - t0, "sweeps": done}
+        except Exception as e:                                   # (an interrupt leaves at once; the launcher ends the job)
+            err = e
+        distenv.rendezvous(err, "its sweeps, but no table was printed")
+        metrics.gather()
+        if rank == 0:
+            print(metrics.table(), end="")
+            if json_path:
+                merge_json(json_path, metrics.results())
+    return metrics
+
+
+def _cli(argv=None):
+    import argparse
+    ap = argparse.ArgumentParser(description="three-way and bucketed EPE of <res_name> against the ground-truth flow (MI355X path)")
+    ap.add_argument("--data_dir", default="/home/kin/data/av2/h5py/sensor/himo")
+    ap.add_argument("--res_names", default="seflowpp_best,raw", help="seflowpp_best,fastnsf,raw  or  \"['seflowpp_best','raw']\"")
+    ap.add_argument("--data_name", default="auto", choices=["auto", "av2", "scania"])
+    ap.add_argument("--batch_frames", type=int, default=32)
+    ap.add_argument("--json", dest="json_path", default="", help="merge {res_name: results} into this JSON file")
+    a = ap.parse_args(argv)
+    return main(a.data_dir, parse_res_names(a.res_names), data_name=a.data_name, batch_frames=a.batch_frames, json_path=a.json_path)
+
+
+if __name__ == "__main__":
+    start_time = time.time()
+    got = _cli()
+    print(f"Time used: {time.time() - start_time:.2f} s")
+    loop = getattr(got, "loop", None)
+    if loop is not None:
+        print(f"Evaluation loop: {loop['sweeps'] / max(loop['seconds'], 1e-9):.0f} sweeps/s ({loop['sweeps']} sweeps in {loop['seconds']:.2f} s)")

@@ -251,6 +251,34 @@ int himo_seg_confusion(int64_t total_points, const uint8_t* d_gt, const uint8_t*
                        const uint8_t* d_seg_valid, const uint8_t* h_class_lut, int64_t* d_conf, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Scene-flow evaluator ("flow metrics, v1", himo_amd/eval_flow.py; csrc/flowmetrics.hip): three-way and bucketed end-point
+ * error of up to HIMO_FLOWM_MAX_RESULTS estimated flows against the ground-truth flow of a packed batch of sweeps, one
+ * launch after the per-sweep transform prep.  PARITY UNPINNED: the reference does this in its absent OpenSceneFlow
+ * submodule; this is the package's own written rule and makes no claim about the reference's numbers.
+ * d_offsets int64[F+1]; d_pose0 / d_pose1 double[F][4][4] (with HIMO_FLAG_POSE_IS_EGO d_pose0 holds inv(pose1) @ pose0 and
+ * d_pose1 may be NULL); d_pc0 float[T][pc_stride]; d_gt float[T][3] (data['flow'], ego motion included); h_est: HOST array of
+ * n_results DEVICE pointers to float[T][3], NULL = "raw" (no estimate: ego motion only); d_category / d_ground uint8[T];
+ * d_valid uint8[T], read only with HIMO_FLAG_SCANIA (which also selects the Scania ego box); h_class_lut: HOST uint8[256],
+ * values 0..4 = BACKGROUND, CAR, OTHER_VEHICLES, PEDESTRIAN, WHEELED_VRU, 5 = other foreground (in no bucket).
+ * A point is counted where the evaluation mask of himo_compdis_batch holds (range 35 m).  Units: 2^-24 m.
+ * d_buckets int64[R][5][51][3] = count, sum q(epe), sum q(speed) per class and speed bucket (bucket b = #{k in 1..50:
+ * speed >= k * 0.4 sensor_dt}); d_threeway int64[F][R][3][2] = count, sum q(epe) per sweep for FD, FS, BS (dynamic: speed >
+ * 0.5 sensor_dt); d_rejected int64[R] = counted points with a non-finite estimate or an error of 1024 m or more, which
+ * enter nothing else.  All three are ADDED to (the caller zeroes them).  d_workspace: 16-byte aligned,
+ * himo_flow_metrics_workspace_bytes(F) bytes.  total_points < 2^31; zero points returns HIMO_OK.  Never synchronises. */
+#define HIMO_FLOWM_MAX_RESULTS 8
+#define HIMO_FLOWM_CLASSES 5
+#define HIMO_FLOWM_BUCKETS 51
+size_t himo_flow_metrics_workspace_bytes(int n_frames);
+int himo_flow_metrics_batch(int n_frames, int64_t total_points, const int64_t* d_offsets,
+                            const double* d_pose0, const double* d_pose1, const float* d_pc0, int pc_stride,
+                            const float* d_gt, const float* const* h_est, int n_results,
+                            const uint8_t* d_category, const uint8_t* d_ground, const uint8_t* d_valid,
+                            const uint8_t* h_class_lut, double sensor_dt, unsigned flags,
+                            int64_t* d_buckets, int64_t* d_threeway, int64_t* d_rejected,
+                            void* d_workspace, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Scania extractor: the labelling of dataprocess/extract_sca.py:95-145 (compute_flow) for a packed batch of sweeps, one
  * launch.  Replaces the pose flow of extract_sca.py:97, the `mmcv.ops.points_in_boxes_part` call of extract_sca.py:117 on double
  * tensors, the object flow and validity of :120-134 and the class / instance columns of :137-140.
