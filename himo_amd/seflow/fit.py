@@ -16,6 +16,12 @@ and affine folded into constants); validation always uses the running statistics
 cluster id) are GENERATED from the sweep pair on the GPU by default (``ssl_label="seflow_auto"``, the launcher's
 ``+ssl_label=seflow_auto``: seflow/ssl_label.py -- nearest-neighbour dynamic candidates + DBSCAN; the reference's generator
 and its label files are absent: unpinned); ``ssl_label=<frame key>`` (e.g. ``flow_instance_id``) reads them from the frames.
+
+``loss_fn="deflowLoss"`` (the launcher's other option value, ssl-train-av2.sh:34) trains SUPERVISED on the ground-truth ``flow`` every
+labelled frame carries ("DeFlow loss, v1", himo_amd/deflow_loss.py; parity unpinned, no claim about the reference's numbers): no
+labels are generated or read, validation uses the same loss, and the samples are built on the launch thread inside the step loop
+(``make_supervised_sample``, the shape of ``num_workers=0``) -- ``feeder.TrainFeeder`` does not prefetch supervised samples (timing
+unmeasured).
 """
 from __future__ import annotations
 
@@ -59,6 +65,19 @@ TRAIN_FIELDS = ("pc0", "pose0", "pose1", "pc1", "gm0", "gm1")
 
 def train_fields(label_key: str = "seflow_auto") -> tuple:
     return TRAIN_FIELDS if label_key in AUTO_LABELS else TRAIN_FIELDS + (label_key, label_key + "_next")
+
+
+LOSS_FNS = ("seflowppLoss", "deflowLoss")                     # the launcher's option values (ssl-train-av2.sh:34)
+
+# ... and what a supervised run reads: the sweep pair, their poses, the ground-truth flow and (where the file has it) its validity
+SUPERVISED_FIELDS = ("pc0", "pose0", "pose1", "pc1", "flow", "flow_is_valid")
+
+
+def loss_fields(loss_fn: str = "seflowppLoss", label_key: str = "seflow_auto") -> tuple:
+    """the frame keys a run with ``loss_fn`` reads (``label_key`` only matters to the self-supervised loss)"""
+    if loss_fn not in LOSS_FNS:
+        raise ValueError(f"loss_fn={loss_fn!r}: one of {LOSS_FNS}")
+    return SUPERVISED_FIELDS if loss_fn == "deflowLoss" else train_fields(label_key)
 
 
 def _frame(dataset, i, fields=None):
@@ -123,12 +142,32 @@ def make_sample(dataset, trip, device, label_key: str = "flow_instance_id"):
     return (up(h["pch1"]), p0, p1, h["pose_h1"], h["pose0"], h["pose1"], l0, l1, n_labels)
 
 
+def make_supervised_sample(dataset, trip, device):
+    """(pch1, pc0, pc1, pose_h1, pose0, pose1, gt_flow, valid_or_None) on ``device`` for one triplet -- the sample of
+    ``SeFlowTrainer(loss="deflow")`` -- built here and now on the calling thread and the current stream.  ``flow`` (n0, 3) is the
+    frame's ground truth with ego motion; ``flow_is_valid`` is optional.  A frame without ``flow`` is a KeyError naming it."""
+    ih, i0, i1 = trip
+    f0 = dataset[i0]
+    fh = _frame(dataset, ih, ("pc0", "pose0")) if ih != i0 else f0
+    if f0.get("flow") is None:
+        raise KeyError("flow: loss_fn=deflowLoss trains on the ground-truth flow, which this frame does not hold")
+    pc1 = f0["pc1"] if i1 is None else dataset[i1]["pc0"]
+    if np.shape(f0["flow"]) != (np.shape(f0["pc0"])[0], 3):
+        raise ValueError(f"flow has shape {np.shape(f0['flow'])} for {np.shape(f0['pc0'])[0]} points")
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(device)
+    valid = f0.get("flow_is_valid")
+    if valid is not None:
+        valid = torch.from_numpy(np.ascontiguousarray(valid).astype(np.uint8)).to(device)
+    return (up(fh["pc0"]), up(f0["pc0"]), up(pc1), np.asarray(fh["pose0"], np.float64), np.asarray(f0["pose0"], np.float64),
+            np.asarray(f0["pose1"], np.float64), up(f0["flow"]), valid)
+
+
 def fit(dataset, params: dict | None = None, out_dir=None, epochs: int = 12, batch_size: int = 8, lr: float = 6e-5,
         step_size: int = 3, gamma: float = 0.5, save_top: int = 3, val_dataset=None, resume=None, precision: str = "mixed",
         max_points: int = 140_000, device=None, seed: int = 0, max_steps: int | None = None, log=print,
         trainer: SeFlowTrainer | None = None, batchnorm: str = "batch", ssl_label: str = "seflow_auto",
         num_workers: int = 1, prefetch: int = 2, label_lanes: int = 1,
-        cache_labels: bool = True) -> dict:
+        cache_labels: bool = True, loss_fn: str = "seflowppLoss") -> dict:
     """Train for ``epochs`` passes over ``dataset``; returns {"trainer", "history", "best"}.
 
     ``num_workers`` > 0 (default; the launcher's ``num_workers=16``, ssl-train-av2.sh:32): the samples of an epoch come from
@@ -136,17 +175,27 @@ def fit(dataset, params: dict | None = None, out_dir=None, epochs: int = 12, bat
     optimiser step.  0: every sample is built inside the step loop on the launch thread (``make_sample``) -- same parameter bits, slower.
     ``cache_labels``: labels generated for a pair (``ssl_label=seflow_auto``) are kept on the host and uploaded again in the later
     epochs instead of being generated again (the reference's job reads labels an offline pass wrote once); same bits.
+    ``loss_fn``: "seflowppLoss" (default) or "deflowLoss" = supervised on the frames' ``flow`` (module docstring): ``ssl_label``, the
+    feeder options and the label cache are not used, every sample is built inside the step loop (``make_supervised_sample``).
 
     Ranks (torch.distributed, initialised by the caller / ``distenv.process_group``): step s of an epoch takes the global
     samples [s * batch_size, (s + 1) * batch_size) of that epoch's seeded shuffle; rank r takes every world-th of them.
     ``max_steps`` bounds the optimiser steps of the whole run (tests)."""
     import torch.distributed as dist
     rank, world = (dist.get_rank(), dist.get_world_size()) if dist.is_available() and dist.is_initialized() else (0, 1)
+    if loss_fn not in LOSS_FNS:
+        raise ValueError(f"loss_fn={loss_fn!r}: one of {LOSS_FNS}")
+    supervised = loss_fn == "deflowLoss"
+    if supervised and log is not None and rank == 0:
+        log(f"loss_fn=deflowLoss: supervised on the frames' ground-truth flow; ssl_label={ssl_label!r} is ignored")
     # a rank's share of a step's samples goes through the network in ONE pass (BatchNorm statistics over them: torch's semantics
     # for a per-process batch), up to 8 at a time
     per_rank = min(8, max(1, math.ceil(batch_size / world)))
     tr = trainer if trainer is not None else SeFlowTrainer(params, device=device, max_points=max_points, seed=seed, precision=precision,
-                                                           batchnorm=batchnorm, batch=per_rank)
+                                                           batchnorm=batchnorm, batch=per_rank,
+                                                           **({"loss": "deflow"} if supervised else {}))
+    if supervised != (getattr(tr, "loss_kind", "seflow") == "deflow"):
+        raise ValueError(f"loss_fn={loss_fn!r} does not match the loss the trainer was built with")
     dev = tr.device
     start_epoch = 0
     if resume is not None:
@@ -166,6 +215,10 @@ def fit(dataset, params: dict | None = None, out_dir=None, epochs: int = 12, bat
         """one iterator of device samples per group of triplets, in order; the groups' samples are prepared ahead across group
         boundaries (``TrainFeeder``), or built on the spot (``num_workers=0``)"""
         if not groups:
+            return
+        if supervised:                                       # (no prefetching of supervised samples: module docstring)
+            for grp in groups:
+                yield (make_supervised_sample(ds, t, dev) for t in grp)
             return
         if num_workers <= 0:
             for grp in groups:
@@ -228,13 +281,8 @@ def fit(dataset, params: dict | None = None, out_dir=None, epochs: int = 12, bat
     return {"trainer": tr, "history": history, "best": top.best() if top is not None else None}
 
 
-def main(argv=None):
-    """``python -m himo_amd.seflow.fit --dataset_path <dir> [--checkpoint init.npz] [--out_dir ckpt]``; under torchrun one
-    rank per GPU (RCCL)."""
+def _parser():
     import argparse
-    from .. import distenv
-    from ..dataset import open_dataset
-    from .checkpoint import load_params
     ap = argparse.ArgumentParser()
     ap.add_argument("--dataset_path", required=True)
     ap.add_argument("--val_path", default="")
@@ -249,19 +297,31 @@ def main(argv=None):
                     help="batch: BatchNorm in training mode (from-scratch training, the reference job); frozen: fine-tuning convention")
     ap.add_argument("--ssl_label", default="seflow_auto",
                     help="seflow_auto (the launcher's +ssl_label=seflow_auto): labels generated on the GPU; or the frame key that holds them")
+    ap.add_argument("--loss_fn", default="seflowppLoss", choices=list(LOSS_FNS),
+                    help="seflowppLoss: the self-supervised terms; deflowLoss: supervised on the scenes' ground-truth flow (--ssl_label is ignored)")
     ap.add_argument("--num_workers", type=int, default=1,
                     help="reader threads that prepare samples ahead of the step (the launcher's num_workers=16; one thread reads ~3.7 k samples/s from "
                          "warm .h5 files and more of them only contend with the launch thread for the interpreter lock); 0: inside the step loop")
     ap.add_argument("--precision", default="mixed", choices=["mixed", "bf16x3", "f32"])
-    a = ap.parse_args(argv)
+    ap.add_argument("--max_points", type=int, default=140_000, help="points per sweep the trainer's buffers are sized for")
+    return ap
+
+
+def main(argv=None):
+    """``python -m himo_amd.seflow.fit --dataset_path <dir> [--checkpoint init.npz] [--out_dir ckpt] [--loss_fn deflowLoss]``; under
+    torchrun one rank per GPU (RCCL)."""
+    from .. import distenv
+    from ..dataset import open_dataset
+    from .checkpoint import load_params
+    a = _parser().parse_args(argv)
     with distenv.process_group():
-        opts = {"fields": train_fields(a.ssl_label), "zero_copy": True}      # (h5 scene files; the npz container ignores them)
+        opts = {"fields": loss_fields(a.loss_fn, a.ssl_label), "zero_copy": True}      # (h5 scene files; the npz container ignores them)
         ds = open_dataset(Path(a.dataset_path), **opts)
         val = open_dataset(Path(a.val_path), **opts) if a.val_path else None
         params = load_params(a.checkpoint) if a.checkpoint else None
         return fit(ds, params, out_dir=a.out_dir, epochs=a.epochs, batch_size=a.batch_size, lr=a.lr, save_top=a.save_top_model,
                    val_dataset=val, resume=a.resume or None, batchnorm=a.batchnorm, ssl_label=a.ssl_label, num_workers=a.num_workers,
-                   precision=a.precision)
+                   precision=a.precision, loss_fn=a.loss_fn, max_points=a.max_points)
 
 
 if __name__ == "__main__":

@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from ..deflow_loss import DeFlowLoss
 from . import spec
 from .model import ConvDesc, EPI_BIAS, fastest_tile_hint
 
@@ -564,8 +565,12 @@ class SeFlowTrainer:
     """
 
     def __init__(self, params: dict | None = None, device=None, max_points: int = 140_000, seed: int = 0,
-                 precision: str = "bf16x3", batchnorm: str = "batch", batch: int = 1):
-        """``batch``: samples one forward / backward pass takes (the launcher's ``batch_size=8`` on one process,
+                 precision: str = "bf16x3", batchnorm: str = "batch", batch: int = 1, loss: str = "seflow"):
+        """``loss``: "seflow" (default) = the self-supervised terms on labelled sweep pairs (himo_amd/ssl_loss.py); "deflow" = the
+        supervised loss on the dataset's ground-truth flow (himo_amd/deflow_loss.py: "DeFlow loss, v1", parity unpinned), whose sample
+        tuples are (pch1, pc0, pc1, pose_h1, pose0, pose1, gt_flow, valid_or_None) -- everything else of the step is the same.
+
+        ``batch``: samples one forward / backward pass takes (the launcher's ``batch_size=8`` on one process,
         assets/slurm/ssl-train-av2.sh:32-34): every encoder layer runs over ``batch`` x F images in ONE launch, every decoder
         layer over ``batch`` images, and training-mode BatchNorm takes its statistics over the whole batch, as torch does
         (``forward_batch`` / ``backward_batch`` / ``train_batch``); saved activations and gradient buffers are ``batch`` times
@@ -587,6 +592,9 @@ class SeFlowTrainer:
             raise ValueError(batchnorm)
         if not 1 <= batch <= 16:
             raise ValueError("batch must be in 1..16")
+        if loss not in ("seflow", "deflow"):
+            raise ValueError(f"loss={loss!r}: 'seflow' or 'deflow'")
+        self.loss_kind = loss
         self.B = B = batch
         self.nb = 1
         self.precision = precision
@@ -1361,7 +1369,8 @@ class SeFlowTrainer:
         """sample slot b's loss engine (each keeps its own neighbour / count buffers: a batch's searches run ahead of its losses)"""
         from ..ssl_loss import SeFlowLoss
         if not hasattr(self, "losses"):
-            self.losses = [SeFlowLoss(device=self.device) for _ in range(self.B)]
+            make = DeFlowLoss if self.loss_kind == "deflow" else SeFlowLoss
+            self.losses = [make(device=self.device) for _ in range(self.B)]
             self.loss = self.losses[0]
         return self.losses[b]
 
@@ -1378,6 +1387,8 @@ class SeFlowTrainer:
         samples = list(samples)
         nb = len(samples)
         engines = [self._loss_engine(b) for b in range(nb)]
+        if self.loss_kind == "deflow":
+            return self._deflow_loss_and_grad_batch(samples, engines, exchange)
         hook = None
         raws, sizes_all = [None] * nb, [None] * nb
         if self.overlap_decoder:
@@ -1420,9 +1431,35 @@ class SeFlowTrainer:
         self.backward_batch(dres_list, exchange=exchange)
         return terms_all, totals
 
+    def _deflow_terms(self, b: int, engine, res, gt_flow, valid):
+        """the supervised loss of sample slot b of the pass that has just run: the raw pc0 rows, the same rows in pc1's frame and the
+        pillar stage's cell ids as the forward pass left them, the head's rows as they stand (pitch 4)"""
+        n0 = self.n_pts_b[b][1]
+        st = self.net._pt[b]
+        return engine(self._fwd_jobs[b][1][1], st["xyz_t"][1][:n0], res, gt_flow, pid=st["pid"][1][:n0], valid=valid)
+
+    def _deflow_loss_and_grad_batch(self, samples, engines, exchange=None):
+        """``loss_and_grad_batch`` for ``loss="deflow"``: ``samples`` = 1 .. ``batch`` tuples (pch1, pc0, pc1, pose_h1, pose0, pose1,
+        gt_flow, valid_or_None).  No side-stream work beside the forward pass: the loss has no input-only half."""
+        res = self.forward_batch([smp[:6] for smp in samples])
+        terms_all, totals, dres_list = [], [], []
+        for b, smp in enumerate(samples):
+            terms, total, grad = self._deflow_terms(b, engines[b], res[b], smp[6], smp[7] if len(smp) > 7 else None)
+            dres = torch.zeros((self.n_pts_b[b][1], 4), dtype=torch.float32, device=self.device)
+            dres[:, :3] = grad
+            terms_all.append(terms); totals.append(total); dres_list.append(dres)
+        if exchange is not None and exchange.words is not None:      # [sample count | loss sum] of this rank ride along with the first bucket
+            exchange.words[0] = float(len(samples))
+            exchange.words[1] = torch.stack(totals).sum().to(exchange.words.dtype)
+        self.backward_batch(dres_list, exchange=exchange)
+        return terms_all, totals
+
     def loss_only(self, pch1, pc0, pc1, pose_h1, pose0, pose1, label0, label1, n_labels: int | None = None):
-        """forward + loss without a backward pass (validation): the total as a 0-d float64 device tensor"""
+        """forward + loss without a backward pass (validation): the total as a 0-d float64 device tensor.  ``loss="deflow"``: the two
+        label arguments are ``gt_flow`` and ``valid`` (or None), as in that mode's sample tuples."""
         res = self.forward(pch1, pc0, pc1, pose_h1, pose0, pose1, training=False)
+        if self.loss_kind == "deflow":
+            return self._deflow_terms(0, self._loss_engine(0), res, label0, label1)[1]
         n0, n1 = self.n_pts[1], self.n_pts[2]
         _, total, _ = self._loss_engine(0)(self.net.xyz_t[1][:n0], self.net.xyz_t[2][:n1], res[:, :3].contiguous(), label0, label1, n_labels)
         return total

@@ -698,6 +698,39 @@ int himo_ssl_loss_presized(int n0, int n1, const float* d_pc0, const float* d_pc
                            double* d_loss, float* d_grad_flow, void* d_workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The supervised loss on ground-truth flow: "DeFlow loss, v1" (himo_amd/csrc/deflowloss.hip, himo_amd/deflow_loss.py).
+ * PARITY UNPINNED: the reference's `deflowLoss` is in the absent OpenSceneFlow submodule; this is the build's own written
+ * rule after the published DeFlow formulation (end-point error averaged inside three speed bands, the bands summed), and no
+ * claim is made about the reference's numbers.
+ *
+ * All arrays have n rows aligned 1:1 with pc0: d_pc0 raw pc0 xyz (float32, row pitch pc0_pitch >= 3 floats), d_moved [n][3]
+ * the same points in pc1's frame as the network saw them, d_gt [n][3] the dataset's `flow` (ego motion included), d_est the
+ * network's residual flow (row pitch est_pitch >= 3 floats), d_pid int32 or NULL (pid < 0: the row was dropped by the pillar
+ * stage), d_valid uint8 or NULL (`flow_is_valid`), sensor_dt > 0 (0.1).  IEEE double on the float32 inputs, every operation
+ * rounded on its own:
+ *   1. a row is COUNTED when (d_pid is NULL or pid >= 0) and (d_valid is NULL or valid != 0) and gt is finite in all three
+ *      components;
+ *   2. g = (p + gt) - m, component by component (the ground-truth residual in pc1's frame = gt - pose_flow);
+ *   3. s = sqrt((gx gx + gy gy) + gz gz);
+ *   4. band 0 when s < 0.4 dt, band 1 when s <= 1.0 dt, band 2 otherwise (both products in double from (double)sensor_dt);
+ *   5. d = est - g,  e = sqrt((dx dx + dy dy) + dz dz);
+ *   6. term_b = mean of e over the counted rows of band b, 0 when the band is empty;  total = (term_0 + term_1) + term_2;
+ *   7. d total / d est_i = (d_i / e_i) / count_band(i) for a counted row with e_i > 0, computed in double and rounded once to
+ *      float32; exactly 0 for an uncounted row and for a counted row with e_i = 0.  A non-finite est in a counted row is not
+ *      filtered: that row's gradient and the loss come out non-finite, other rows' gradients are unaffected.
+ * d_loss [4] = the three terms and the total (float64, device), d_counts [3] = counted rows per band (int64, device), d_grad
+ * [n][3] float32.  Sums are fixed-order trees and there are no atomics: loss and gradient are bit-identical from run to run.
+ * Never synchronises, keeps nothing between calls.  n == 0: HIMO_OK, zero loss and zero counts, nothing else is touched.
+ * HIMO_ERR_INVALID_ARGUMENT: n < 0, a pitch < 3, a NULL required array, sensor_dt not positive and finite; HIMO_ERR_UNSUPPORTED:
+ * n > 2^31 - 1; HIMO_ERR_WORKSPACE: a NULL, misaligned (16 bytes) or short workspace (himo_deflow_loss_workspace_bytes(n)). */
+size_t himo_deflow_loss_workspace_bytes(int64_t n);
+int himo_deflow_loss(int64_t n, const float* d_pc0, int pc0_pitch, const float* d_moved, const float* d_gt,
+                     const float* d_est, int est_pitch, const int32_t* d_pid /* nullable */,
+                     const uint8_t* d_valid /* nullable */, float sensor_dt, double* d_loss /* [4]: three terms, total */,
+                     int64_t* d_counts /* [3] */, float* d_grad /* [n][3] */, void* d_workspace, size_t workspace_bytes,
+                     void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * a12: optimisation-based scene flow ("fastnsf", README.md:53).  Reference implementation absent (OpenSceneFlow
  * submodule); specification in himo_amd/fastnsf.py.  The MLP forward / input-gradient products use himo_conv2d
  * (ksize 1) with HIMO_EPI_BIAS_RELU / HIMO_EPI_RELU_MASK; these are the fitting-specific pieces.
