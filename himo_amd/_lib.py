@@ -78,6 +78,10 @@ SIGNATURES = {
                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                     c_void_p]),
     "himo_nsfp_keep_best": (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_void_p]),
+    "himo_raymap_map_bytes": (c_size_t, [c_void_p]),
+    "himo_raymap_carve": (c_int, [c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "himo_raymap_query": (c_int, [c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "himo_raymap_status": (c_int, [c_void_p]),
 }
 
 FLAG_F32_CHAIN = 0x1

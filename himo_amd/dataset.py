@@ -212,6 +212,8 @@ class HDF5Dataset:
     ``feeder.SampleFeeder``, then copy each sweep once instead of twice).
     A name in ``fields`` that is none of the loader's own keys is served from the dataset of that name in the sweep's group when
     there is one, with its on-disk dtype (``seg_valid``, the segmentation results of downstream/eval_seg.py:219).
+    A name ``<name>_next`` in ``fields`` is served from dataset ``<name>`` of the NEXT sweep's group when that group holds it (stored
+    labels of both sweeps of a pair: ``seflow.fit --ssl_label <name>``).
     ``allow_dropped_eval`` (default: env ``HIMO_ALLOW_DROPPED_EVAL``, else False): see the KeyError below.
     ``need_next=False``: for consumers that read a sweep alone (no ``pose1`` / ``pc1``): every index entry stays, the last sweep
     of a scene included, and asking such an item for a successor's key is a KeyError."""
@@ -349,7 +351,9 @@ class HDF5Dataset:
             for k in sorted(want - _LOADER_KEYS):
                 if k not in d and k in g:
                     d[k] = self._array(g[k])
-        if not any(need(k) for k in ("pose1", "pc1", "gm1", "flow_instance_id_next")):
+        # any other requested field ``<name>_next``: dataset ``<name>`` of the successor's group (stored labels of the next sweep)
+        others_next = [] if want is None else sorted(k for k in want - _LOADER_KEYS if k.endswith("_next") and len(k) > 5 and k not in d)
+        if not (any(need(k) for k in ("pose1", "pc1", "gm1", "flow_instance_id_next")) or others_next):
             return d
         nxt = f[self._next[(scene_id, ts)]]
         if need("pose1"):
@@ -360,6 +364,9 @@ class HDF5Dataset:
             d["gm1"] = np.asarray(nxt["ground_mask"][:]).astype(bool)
         if need("flow_instance_id_next") and "flow_instance_id" in nxt:        # the training loop clusters both sweeps (seflow/fit.py)
             d["flow_instance_id_next"] = self._array(nxt["flow_instance_id"])
+        for k in others_next:
+            if k[:-5] in nxt:
+                d[k] = self._array(nxt[k[:-5]])
         return d
 
 

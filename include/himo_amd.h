@@ -334,6 +334,48 @@ int himo_ground_seg_batch(int n_frames, int64_t total_points, const int64_t* h_o
                           float* d_cell_ground, void* d_workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Free-space labeller: which points of a target sweep sit where OTHER sweeps saw through (himo_amd/csrc/raymap.hip).  The
+ * reference's label generator is in its absent submodule, so this stage follows the build's own written rule, "free-space ray
+ * map, v1" (the module docstring of himo_amd/raymap.py is normative): PARITY UNPINNED.
+ *   quantise  f = (c - min) * scale (float32, two operations), scale = (float)(256.0 / voxel); a point is unusable when an f is
+ *             not finite or |f| >= 2^22; u = (int)floorf(f) in 1/256 voxel, voxel index u >> 8
+ *   carve     every ray walks the voxels from its origin's to its end point's in exact integer arithmetic (the next boundary
+ *             crossing by 64-bit cross-multiplication, ties to the lowest axis); a visited voxel in the grid whose Chebyshev index
+ *             distance to the end voxel is > guard gets FREE bit `slot`, the end voxel (never visited) HIT bit 16 + slot.
+ *             Marks are OR-ed into the caller's map (uint32 [nz][ny][nx], cleared by the caller): calls accumulate.
+ *   query     w = the word of a point's voxel, fv = popcount((w & 0xFFFF) & ~(w >> 16)), hv = popcount(w >> 16); the point is
+ *             DYNAMIC iff it is not skipped, usable, in the grid, fv >= min_votes and fv > hv
+ * d_pts: float[n][pitch], pitch 3 or 4 (x, y, z first) in the map's frame; d_slot: one byte per ray, 0..15 = the sweep the ray
+ * belongs to (its origin is d_origins[slot]), 255 = the ray takes no part; d_origins: float[16][3]; d_skip: uint8[n] or NULL,
+ * non-zero = the point is never DYNAMIC; d_free_votes / d_hit_votes / d_dynamic: uint8[n], each may be NULL (fv and hv are 0 for
+ * a skipped, unusable or out-of-grid point).
+ * Refused with HIMO_ERR_INVALID_ARGUMENT, nothing launched and nothing written: n < 0, a pitch other than 3 or 4, NULL where data
+ * is required, d_pts / d_origins / d_map not 4-byte aligned, and parameters outside: every float finite, voxel > 0, scale ==
+ * (float)(256.0 / voxel) and finite, 1 <= nx, ny <= 1024, 1 <= nz <= 64, nx*ny*nz <= 2^24, 0 <= guard <= 8, 1 <= min_votes <= 16
+ * (himo_raymap_map_bytes returns 0 for them).  n > 2^31 - 1: HIMO_ERR_UNSUPPORTED.  n == 0: HIMO_OK without a launch.
+ * A slot byte in 16..254 makes the WHOLE carve call a refused one, found on the device: a first kernel reads every slot byte, the
+ * carving kernel behind it on the stream then marks nothing, and the refusal is recorded in a flag word of the device.  Both calls
+ * are asynchronous on `stream`, so himo_raymap_carve itself still returns HIMO_OK for such a call; himo_raymap_status(stream) waits
+ * for `stream`, returns HIMO_ERR_INVALID_ARGUMENT when a carve call on the current device was refused in this way since the last
+ * himo_raymap_status, and clears the flag.  The map after equal calls is the same bytes on every run (OR is order-independent). */
+typedef struct himo_raymap_params {
+    float x0, y0, z0;      /* grid minimum */
+    float voxel;           /* voxel edge, m */
+    float scale;           /* (float)(256.0 / voxel), the division in double */
+    int32_t nx, ny, nz;
+    int32_t guard;         /* voxels in front of a return (Chebyshev) that its ray does not carve */
+    int32_t min_votes;     /* sweeps that must have seen through a voxel */
+} himo_raymap_params;
+
+size_t himo_raymap_map_bytes(const himo_raymap_params* params);        /* 4*nx*ny*nz; 0 = parameters refused */
+int himo_raymap_carve(int64_t n_rays, const float* d_pts, int pitch, const unsigned char* d_slot, const float* d_origins,
+                      const himo_raymap_params* params, uint32_t* d_map, void* stream);
+int himo_raymap_query(int64_t n, const float* d_pts, int pitch, const unsigned char* d_skip, const himo_raymap_params* params,
+                      const uint32_t* d_map, unsigned char* d_free_votes, unsigned char* d_hit_votes, unsigned char* d_dynamic,
+                      void* stream);
+int himo_raymap_status(void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * ICP-Flow baseline (`save --model icpflow`, result key `icpflow`): clusters of the non-ground points of pc0, one rigid fit
  * (yaw + 3-D translation) per cluster against pc1, flow = fitted motion.  The reference's ICP-Flow code is in its absent
  * submodule (only the key name is in its tree, tools/view_instance.py:155-156), so this stage follows the build's own written
