@@ -82,6 +82,9 @@ SIGNATURES = {
     "himo_raymap_carve": (c_int, [c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "himo_raymap_query": (c_int, [c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "himo_raymap_status": (c_int, [c_void_p]),
+    "himo_render_clear": (c_int, [c_void_p, c_int, c_int, c_void_p]),
+    "himo_render_splat": (c_int, [c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, ctypes.c_uint32, c_void_p, c_void_p]),
+    "himo_render_resolve": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
 }
 
 FLAG_F32_CHAIN = 0x1

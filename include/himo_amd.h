@@ -376,6 +376,61 @@ int himo_raymap_query(int64_t n, const float* d_pts, int pitch, const unsigned c
 int himo_raymap_status(void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The headless viewer's renderer ("point splat, v1"; csrc/render.hip; the rule is the module docstring of himo_amd/view.py and is
+ * this build's own: no claim is made about the pixels of any other viewer).
+ *
+ * The visibility buffer is one uint64 per pixel, [height][width]: ~0 = empty, else (zq << 32) | point index, zq the 24-bit depth.
+ * himo_render_clear fills it with ~0.  himo_render_splat adds n points (float32 rows of `pitch` >= 3 floats; d_offset, nullable,
+ * float32 [n][3], is added per component first; d_skip, nullable, non-zero = not drawn): p -> camera coordinates
+ * ((m0 x + m1 y) + m2 z) + m3 per row of the 3x4 matrix `m` (the camera looks along +z; x right, y down), dropped when a
+ * coordinate is not finite or zc is outside [znear, zfar]; u = fx (xc / zc) + cx, v = fy (yc / zc) + cy (ortho: without the
+ * divide), dropped when not finite or outside [-(radius + 1), extent + radius + 1); pixel (floor u, floor v);
+ * zq = min(2^24 - 1, floor((zc - znear) * inv_range * 2^24)); then a 64-bit atomic minimum of (zq << 32) | (index_base + i) into
+ * every pixel (px + dx, py + dy), dx^2 + dy^2 <= radius^2, that lies inside the image.  The nearest point wins, the lowest index
+ * among equal zq; calls accumulate, in any order and any split, to the same bits.  Every float operation rounds on its own.
+ * himo_render_resolve writes uint8 RGB [height][width][3]: an empty pixel takes `background`; a hit takes the colour of the
+ * attribute at the key's low 32 bits (an index >= n_attr: `neutral`) -- mode 0: rgba[idx] (r | g << 8 | b << 16); mode 1:
+ * lut[clamp(floor((scalar[idx] - lo) * scale), 0, 255)], a non-finite scalar: `neutral`; mode 2: palette[ids[idx] % palette_n], a
+ * negative id: `neutral` -- shaded, when edl_strength > 0, by exp2(-edl_strength * resp), resp = the mean over the four
+ * neighbours at +-edl_px of max(0, L_c - L_nb), L = log2(1 + zq), an empty neighbour L = 24, one outside the image L_c; a channel
+ * becomes floor(c * shade + 0.5).  All pointers of himo_shade are device pointers; lut holds 256 entries.
+ *
+ * All three are asynchronous on `stream`.  Refused with HIMO_ERR_INVALID_ARGUMENT, nothing launched and nothing written: radius
+ * outside 0..8, pitch < 3, n < 0, a non-positive width or height, a NULL or misaligned buffer, camera or shade, NULL points with
+ * n > 0, znear / zfar / inv_range not finite or zfar <= znear or inv_range <= 0, a mode outside 0..2, the mode's attribute array NULL
+ * with n_attr > 0, a NULL lut (mode 1) or palette (mode 2), palette_n <= 0 in mode 2, lo / scale not finite in mode 1, an
+ * edl_strength that is negative or not finite, edl_px < 1 with edl_strength > 0.  HIMO_ERR_UNSUPPORTED: a side above 16384,
+ * n > 2^31 - 1, index_base + n > 2^32.  n == 0: HIMO_OK without a launch. */
+typedef struct himo_camera {
+    float m[12];           /* world -> camera, 3 rows of 4 */
+    int32_t ortho;         /* 0 = perspective */
+    float fx, fy, cx, cy;
+    float znear, zfar;
+    float inv_range;       /* (float)1 / (zfar - znear), computed in float32 on the host */
+    int32_t width, height;
+} himo_camera;
+
+typedef struct himo_shade {
+    int32_t mode;          /* 0 = rgba, 1 = scalar through lut, 2 = ids through palette */
+    int32_t palette_n;
+    const uint32_t* rgba;
+    const float* scalar;
+    const int32_t* ids;
+    const uint32_t* lut;
+    const uint32_t* palette;
+    int64_t n_attr;        /* entries behind the mode's attribute array */
+    float lo, scale;
+    uint32_t background, neutral;
+    float edl_strength;
+    int32_t edl_px;
+} himo_shade;
+
+int himo_render_clear(uint64_t* d_vis, int width, int height, void* stream);
+int himo_render_splat(int64_t n, const float* d_pts, int pitch, const float* d_offset, const unsigned char* d_skip,
+                      const himo_camera* cam, int radius, uint32_t index_base, uint64_t* d_vis, void* stream);
+int himo_render_resolve(const uint64_t* d_vis, int width, int height, const himo_shade* shade, unsigned char* d_rgb, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * ICP-Flow baseline (`save --model icpflow`, result key `icpflow`): clusters of the non-ground points of pc0, one rigid fit
  * (yaw + 3-D translation) per cluster against pc1, flow = fitted motion.  The reference's ICP-Flow code is in its absent
  * submodule (only the key name is in its tree, tools/view_instance.py:155-156), so this stage follows the build's own written
