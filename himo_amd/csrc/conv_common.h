@@ -32,8 +32,11 @@ struct ConvArgs {
     float* aux_out; int aux_out_pitch;                        // r*h (kEpiGruZR) / h in place (kEpiGruQ)
     int act_flags;                                            // kActSplitIn | kActSplitOut: split activation format (convsg.hip)
     unsigned* range_seen;                                     // himo_conv_desc.d_range_seen (split outputs; may be null)
+    const unsigned long long* mask;                           // kActRowMask: one bit per output pixel (himo_conv_desc.d_mask), strides
+    int64_t mask_batch_stride, mask_outer_stride;             //               in 64-bit words, addressed like x / y (image_offset)
 };
-enum ActFlags { kActSplitIn = 1, kActSplitOut = 2, kActVecStore = 4, kActAccumulate = 8, kActStuffedIn = 16 };
+enum ActFlags { kActSplitIn = 1, kActSplitOut = 2, kActVecStore = 4, kActAccumulate = 8, kActStuffedIn = 16, kActRowMask = 32 };
+// kActRowMask (HIMO_ACT_ROW_MASK): only the output pixels whose mask bit is set are formed and written (convsg.hip, conv3_rowmask_kernel)
 // kActStuffedIn (HIMO_ACT_STUFFED_2X): x is a compact [H / 2][W / 2] map read as its zero-stuffed x2 image (two-term bf16 3x3 kernel)
 // kActVecStore: set by plan_conv (conv_plan.h, vec_store_ok).  kActAccumulate (HIMO_ACT_ACCUMULATE): y += result -- float32 output of the
 // two-term bf16 3x3 kernels only (the training step's stride-2 data gradients add into the decoder's skip gradient in place)

@@ -106,9 +106,17 @@ inline bool plan_from_l2(ConvPlan& p, int rows_hint) {
 // rows_hint: 4 | 2 | 1 = 32-pixel segments (1x1) / image rows (3x3 stride 1) per wave, 4 on 64-channel layers becomes 2;
 // 8 (64-channel layers) | 12 (wide layers) = two 32-channel column tiles per wave, only with a 16-byte-storable output;
 // anything else, and every hint at stride 2 (one variant per width class), leaves the heuristic in charge.
+// kActRowMask (admitted by plan_conv's table): ONE variant -- the 8-row x 32-pixel x 64-channel tile of rows_hint 8 whose
+// fragments are the tile's listed pixels (conv3_rowmask_kernel) -- under a profiler name of its own; every hint is ignored.
 inline int plan_presplit(ConvPlan& p, int rows_hint) {
     ConvArgs& a = p.args;
     if (!below_2gb((int64_t)a.H * a.W, a.x_pitch)) return HIMO_ERR_UNSUPPORTED;       // 32-bit DMA source offsets
+    if (a.act_flags & kActRowMask) {
+        p.family = kConvPresplit3;
+        p.prof_name = "conv3x3_masked_f16x2_kernel";
+        plan_rows_tile(p, 4, 2, 2);
+        return HIMO_OK;
+    }
     const bool wide = a.Cout > 64, vec = vec_store_ok(a), pinned = rows_hint == 4 || rows_hint == 2 || rows_hint == 1;
     const int ph = wide ? 1 : 2;
     p.family = p.ks == 1 ? kConvPresplit1 : kConvPresplit3;
@@ -168,6 +176,16 @@ inline int plan_conv(const himo_conv_desc& d, ConvPlan& p) {
     a.range_seen = (d.act_layout & kActSplitOut) ? d.d_range_seen : nullptr;
 
     // ---- act_layout: which combinations exist at all ----
+    // HIMO_ACT_ROW_MASK: the split-input fp16-split 3x3 stride-1 layers of <= 64 channels with a float32 output, whole 32-pixel
+    // row segments (a tile row's 32 mask bits are one aligned 32-bit word); the mask is read by plan_presplit's kernel only
+    if (d.act_layout & kActRowMask) {
+        if (!d.d_mask || (reinterpret_cast<uintptr_t>(d.d_mask) & 7u)) return HIMO_ERR_INVALID_ARGUMENT;
+        if (d.act_layout != (kActRowMask | kActSplitIn) || !d.w_packed || d.packed_format != 1 || d.ksize != 3 || d.stride != 1 ||
+            d.cout > 64 || (d.w_in & 31) || (d.epilogue != kEpiBias && d.epilogue != kEpiBiasBnGelu) || (d.cin & 15) || (d.x_pitch & 15))
+            return HIMO_ERR_UNSUPPORTED;
+        a.mask = reinterpret_cast<const unsigned long long*>(d.d_mask);
+        a.mask_batch_stride = d.mask_batch_stride; a.mask_outer_stride = d.mask_outer_stride;
+    }
     // HIMO_ACT_ACCUMULATE alone on a row GEMM (ksize 1) of either bf16 split with the bias epilogue: kConvStaged
     const bool gemm_acc = d.act_layout == kActAccumulate && d.w_packed && d.ksize == 1 && d.epilogue == kEpiBias && (d.packed_format == 0 || d.packed_format == 2);
     if (d.act_layout & (kActAccumulate | kActStuffedIn)) {
@@ -177,7 +195,7 @@ inline int plan_conv(const himo_conv_desc& d, ConvPlan& p) {
             return HIMO_ERR_UNSUPPORTED;
         if ((d.act_layout & kActStuffedIn) && ((d.h & 1) || (d.w_in & 1) || !below_2gb((int64_t)(d.h / 2) * (d.w_in / 2), d.x_pitch)))
             return HIMO_ERR_UNSUPPORTED;
-    } else if (d.act_layout) {   // split activation format: fp16-split layers only, whole 16-channel groups
+    } else if (d.act_layout && !(d.act_layout & kActRowMask)) {   // split activation format: fp16-split layers only, whole 16-channel groups
         if ((d.act_layout & ~(kActSplitIn | kActSplitOut)) || !d.w_packed || d.packed_format != 1) return HIMO_ERR_UNSUPPORTED;
         if (d.ksize == 1 && !(d.act_layout & kActSplitIn)) return HIMO_ERR_UNSUPPORTED;      // 1x1: split output only with split input
         if (d.epilogue != kEpiBias && d.epilogue != kEpiBiasBnGelu) return HIMO_ERR_UNSUPPORTED;

@@ -31,6 +31,7 @@
 // Specification / oracle as conv.hip (reference network absent: PARITY UNPINNED).
 #include "conv_plan.h"
 #include "bf16x3.h"
+#include <type_traits>
 
 namespace himo {
 
@@ -232,6 +233,241 @@ void conv3_presplit_kernel(ConvArgs a, const unsigned short* __restrict__ wpk) {
     }
 }
 
+// ---- row-masked 3x3 stride 1 (kActRowMask): only the output pixels whose mask bit is set are formed and written --------------------
+// The 64-channel tile of conv3_presplit_kernel<EPI, 4, 2, false, 1, 2> -- 8 rows x 32 pixels, 10-row x 40-slot double-buffered
+// patch staged by LDS-DMA, weight fragments from L2 two taps ahead, one barrier per slab -- with another choice of the 32 pixels of
+// a fragment: not one image row but 32 consecutive entries of the tile's LIST of set pixels.
+//   prologue   every wave reads the tile's 8 x 32 mask bits (a tile row is one aligned 32-bit word: Wo is a multiple of 32) and
+//              forms n_occ and its own two rows' list positions from popcounts alone; thread t writes pixel t (row t >> 5, column
+//              t & 31, one byte) to list[position] when its bit is set.  n_occ = 0: the block returns before any DMA or weight load.
+//   fragments  ceil(n_occ / 32) <= 8, dealt to the four waves as (fragment group g, 32-channel column tile t): role r = (wave +
+//              tile index) & 3, g = r >> 1, t = r & 1.  Group 0 takes the first n0 = min(n, max(2, ceil(n / 2))) fragments, group 1
+//              the other n - n0: (1,0) (2,0) (2,1) (2,2) (3,2) (3,3) (4,3) (4,4) for n = 1 .. 8 -- a weight fragment meets two
+//              activation fragments wherever the tile has two for it, and from three fragments on all four waves (SIMDs) work.
+//              Per wave of m fragments and tap: 2 weight loads and 2 m fragment reads for 3 m matrix instructions (the dense
+//              2-rows-per-wave x 32-channel tile at m = 2).  Registers: 16 m accumulator + 8 m fragment + 24 weight registers
+//              (three rotating sets) + 3 m read offsets -- 132 at m = 4 against the dense 8-row tile's 134 -- and three for
+//              the DMA sources.  A wave without fragments (or whose column tile lies past Cout) only stages the patch.  The
+//              role rotates with the tile so that uneven groups of the blocks sharing a CU spread over its SIMDs.  A lane's
+//              three read offsets per fragment (plane 1 is offset ^ 32) come from ITS pixel's row and column in the patch, same
+//              XOR slot swizzle; the tap adds ky * kRow as before.  Gathered ds_read_b128 meet bank conflicts; accepted.
+//              Lanes past n_occ in the last fragment read the last listed pixel and store nothing.
+//   order      per output value exactly the dense kernel's: slab-major, ky, kx, then l*h, h*l, h*h into ONE accumulator, and
+//              the same epi_affine / epi_activate -- a row of a matrix instruction does not depend on its neighbours, so every
+//              value written has the bits conv3_presplit_kernel writes for that pixel.
+//   stores     register r of an accumulator block is 32 consecutive channels of ONE listed pixel per half-wave: a full 128-byte
+//              line, stored straight to y + pixel * y_pitch + channel (float32 output only; no LDS transpose).
+// Compiler's resource report (gfx950, launch bounds 256 x 3, both epilogues): 168 VGPRs, 0 AGPRs, no scratch, no spills, 51,456 bytes
+// of LDS (the dense tile's 51,200 + the 256-byte list): three blocks per CU.
+template <int EPI>
+__global__ __launch_bounds__(256, 3)
+void conv3_rowmask_kernel(ConvArgs a, const unsigned short* __restrict__ wpk) {
+    constexpr int TW = 32, TH = 8, PHt = TH + 2, PWP = 40;
+    constexpr int kRow = PWP * 64, kBuf = (PHt * kRow + 1023) / 1024 * 1024;
+    static_assert(PHt * PWP == 25 * 16 && kBuf == 25 * 1024, "25 DMA units of 16 slots fill a patch buffer exactly");
+    __shared__ __attribute__((aligned(1024))) unsigned char patch[2 * kBuf];
+    __shared__ __attribute__((aligned(16))) unsigned char s_list[TH * TW];
+
+    const int tile = xcd_block_id(blockIdx.x, gridDim.x);        // (Cout <= 64: one channel tile)
+    int bid = tile;
+    const int tx = a.Wo / TW, ty = (a.Ho + TH - 1) / TH;
+    // (uniform, but the divisions run in the vector unit: back to scalar registers, with everything derived from them)
+    const int ox0 = __builtin_amdgcn_readfirstlane((bid % tx) * TW); bid /= tx;
+    const int oy0 = __builtin_amdgcn_readfirstlane((bid % ty) * TH);
+    const int img = __builtin_amdgcn_readfirstlane(bid / ty);
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int li = lane & 31, lh = lane >> 5;
+
+    // ---- the tile's occupancy: row i of the tile in lane i, then in scalar registers ----
+    const unsigned* __restrict__ mrow = reinterpret_cast<const unsigned*>(a.mask + image_offset(img, a.n_inner, a.mask_batch_stride, a.mask_outer_stride));
+    unsigned mine = 0u;
+    if (lane < TH && oy0 + lane < a.Ho) mine = mrow[((unsigned)(oy0 + lane) * (unsigned)a.Wo + (unsigned)ox0) >> 5];
+    int n_occ = 0, before = 0;                                   // set pixels of the tile; of the rows above this wave's two
+#pragma unroll
+    for (int i = 0; i < TH; ++i) {
+        const int c = __builtin_popcount(__builtin_amdgcn_readlane(mine, i));
+        n_occ += c;
+        before += i < 2 * wave ? c : 0;
+    }
+    if (n_occ == 0) return;                                      // nothing of this tile is read: no DMA, no weight load
+    {
+        const unsigned r0 = __builtin_amdgcn_readlane(mine, 2 * wave), r1 = __builtin_amdgcn_readlane(mine, 2 * wave + 1);
+        const unsigned bits = lh ? r1 : r0, below = (1u << li) - 1u;
+        if ((bits >> li) & 1u) s_list[before + (lh ? __builtin_popcount(r0) : 0) + __builtin_popcount(bits & below)] = (unsigned char)threadIdx.x;
+    }
+    const int role = (wave + tile) & 3, ct = role & 1;           // fragment group role >> 1, column tile ct
+    const int n_frag = (n_occ + 31) >> 5;
+    const int half = (n_frag + 1) >> 1, n0 = n_frag < 2 ? n_frag : (half > 2 ? half : 2);
+    const int first = (role >> 1) ? n0 : 0;                      // this wave's fragments: first .. first + mine_n - 1
+    const int mine_n = ct * 32 < a.Cout ? ((role >> 1) ? n_frag - n0 : n0) : 0;
+
+    const unsigned char* __restrict__ xin = reinterpret_cast<const unsigned char*>(a.x + image_offset(img, a.n_inner, a.x_batch_stride, a.x_outer_stride));
+    const int slabs = a.Cin >> 4;
+    const int iy0 = oy0 - 1, ix0 = ox0 - 1;
+    const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)(&patch[0]);
+
+    // DMA units of 16 pixel slots run linearly over the patch as in conv3_presplit_kernel (unit u lands at u * 1024), but a wave
+    // takes the units of one residue class mod 5: units u and u + 5 are 80 slots = two patch rows apart and hold the SAME columns,
+    // so a class needs ONE source offset (+ j row pairs) and one validity bit per unit instead of a register per unit -- three
+    // registers where the dense tile holds seven.  Wave w: units w, w + 5, .. w + 20 (class w) and unit 4 + 5 w of class 4;
+    // wave 0 also the 25th unit (24).  Offsets are 32-bit (an image is < 2 GB), the piece's 16-byte slot an OR (x_pitch is a
+    // multiple of 16 floats).
+    unsigned offA, offB, vm = 0u;                                // bit j: unit w + 5 j; bit 5: unit 4 + 5 w; bit 6: unit 24 (wave 0)
+    const unsigned rs2 = (unsigned)(2 * a.W) * (unsigned)a.x_pitch * 4u;       // two image rows
+    {
+        const int q = wave * 16 + (lane >> 2), row = q / PWP, px = q - row * PWP, ix = ix0 + px;
+        const bool col_ok = px < TW + 2 && ix >= 0 && ix < a.W;
+        offA = (((unsigned)((iy0 + row) * a.W + ix) * (unsigned)a.x_pitch) << 2) | (unsigned)(((lane & 3) ^ ((px >> 2) & 3)) << 4);
+#pragma unroll
+        for (int j = 0; j < 5; ++j) vm |= (col_ok && iy0 + row + 2 * j >= 0 && iy0 + row + 2 * j < a.H) ? 1u << j : 0u;
+    }
+    {
+        const int q = 4 * 16 + (lane >> 2), row = q / PWP + 2 * wave, px = q % PWP, ix = ix0 + px;      // (row 1 + 2 w, slots 24 .. 39)
+        const bool col_ok = px < TW + 2 && ix >= 0 && ix < a.W;
+        offB = (((unsigned)((iy0 + row) * a.W + ix) * (unsigned)a.x_pitch) << 2) | (unsigned)(((lane & 3) ^ ((px >> 2) & 3)) << 4);
+        vm |= (col_ok && iy0 + row >= 0 && iy0 + row < a.H) ? 1u << 5 : 0u;
+        vm |= (wave == 0 && col_ok && iy0 + row + 8 >= 0 && iy0 + row + 8 < a.H) ? 1u << 6 : 0u;
+    }
+    auto stage = [&](int slab, int buf) {
+        int ln = threadIdx.x;
+        unsigned oa = offA, ob = offB, m = vm;
+        asm volatile("" : "+v"(ln), "+v"(oa), "+v"(ob), "+v"(m));   // (the 64-bit source pointers are formed at each of the four call
+        const unsigned char* zero = g_zero_page + (ln & 3) * 16;    //  sites, not kept in registers through the slab loop)
+        const unsigned dst = lds_base + buf * kBuf;
+#pragma unroll
+        for (int j = 0; j < 5; ++j)
+            glds16((m >> j) & 1u ? xin + (oa + j * rs2 + (unsigned)slab * 64u) : zero, dst + (wave + 5 * j) * 1024);
+        glds16((m >> 5) & 1u ? xin + (ob + (unsigned)slab * 64u) : zero, dst + (4 + 5 * wave) * 1024);
+        if (wave == 0) glds16((m >> 6) & 1u ? xin + (ob + 4 * rs2 + (unsigned)slab * 64u) : zero, dst + 24 * 1024);
+    };
+    stage(0, 0);
+    __syncthreads();                                             // the list is complete (the DMA stays in flight)
+
+    if (mine_n <= 0) {                                           // a staging-only wave: its share of every slab's DMA, every barrier
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();                                         // (the working waves' barrier ahead of slab 0)
+#pragma unroll 1
+        for (int slab = 0; slab + 1 < slabs; ++slab) {           // ... and the one that ends every slab but the last
+            stage(slab + 1, (slab & 1) ^ 1);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();
+        }
+        return;
+    }
+
+    const unsigned char* __restrict__ wb = reinterpret_cast<const unsigned char*>(wpk);
+    unsigned b_lane;
+    {
+        const int c = ct * 32 + li < a.Cout ? ct * 32 + li : a.Cout - 1;
+        b_lane = (unsigned)c * 32u + (unsigned)lh * 16u;
+        asm volatile("" : "+v"(b_lane));                         // (ONE register: the compiler otherwise keeps the sum's parts alive)
+    }
+    const unsigned b_plane = (unsigned)a.Cout * 32u, b_block = 2u * b_plane;
+    auto load_b = [&](int tap, int slab, uint4 (&b)[2]) {
+        const unsigned off = (unsigned)(tap * slabs + slab) * b_block + b_lane;
+        b[0] = *reinterpret_cast<const uint4*>(wb + off);
+        b[1] = *reinterpret_cast<const uint4*>(wb + (off + b_plane));
+    };
+    float* __restrict__ yout = a.y + image_offset(img, a.n_inner, a.y_batch_stride, a.y_outer_stride);
+
+    // the slab loop and the epilogue for a wave of MIW fragments (1 .. 4)
+    auto run = [&](auto miw) {
+        constexpr int MIW = decltype(miw)::value;
+        // fragment read offsets (buffer 0, kernel row 0, plane 0): [fragment][kx], from the lane's own listed pixel; plane 1 sits at
+        // slot ^ 2, i.e. offset ^ 32 -- formed at the read, which keeps the offsets at the dense tile's six registers
+        int rd[MIW][3];
+        int lw = threadIdx.x;
+        asm volatile("" : "+v"(lw) :: "memory");                     // (per instantiation: nothing below is formed ahead of the branch and
+        const int li = lw & 31, lh = (lw >> 5) & 1;                  //  kept alive through the other instantiation's loop)
+#pragma unroll
+        for (int mi = 0; mi < MIW; ++mi) {
+            const int e = (first + mi) * 32 + li;
+            int pxl = s_list[e < n_occ ? e : n_occ - 1];
+            asm volatile("" : "+v"(pxl));                            // (per instantiation: nothing of this is shared ahead of the branch)
+            const int r = pxl >> 5, c = pxl & 31;
+#pragma unroll
+            for (int kx = 0; kx < 3; ++kx) {
+                const int p = c + kx, f = (p >> 2) & 3;
+                rd[mi][kx] = r * kRow + p * 64 + ((lh ^ f) << 4);
+                asm volatile("" : "+v"(rd[mi][kx]));
+            }
+        }
+        floatx16 acc[MIW];
+#pragma unroll
+        for (int mi = 0; mi < MIW; ++mi)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[mi][r] = 0.f;
+
+        uint4 bq[3][2];
+        load_b(0, 0, bq[0]);
+        load_b(1, 0, bq[1]);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+
+#pragma unroll 1
+        for (int slab = 0; slab < slabs; ++slab) {
+            const int buf = slab & 1;
+            const bool more = slab + 1 < slabs;
+            const int nslab = more ? slab + 1 : slab;
+            if (more) stage(slab + 1, buf ^ 1);                  // that buffer was last read before the previous barrier
+#pragma unroll 1
+            for (int ky = 0; ky < 3; ++ky) {
+                const int rowoff = buf * kBuf + ky * kRow;
+#pragma unroll
+                for (int kx = 0; kx < 3; ++kx) {
+                    const int tap = ky * 3 + kx;
+                    const int t2 = tap + 2;
+                    load_b(t2 < 9 ? t2 : t2 - 9, t2 < 9 ? slab : nslab, bq[(kx + 2) % 3]);
+                    f16x8 af[MIW][2];
+#pragma unroll
+                    for (int s = 0; s < 2; ++s)
+#pragma unroll
+                        for (int mi = 0; mi < MIW; ++mi)
+                            af[mi][s] = *reinterpret_cast<const f16x8*>(&patch[(rd[mi][kx] ^ (s << 5)) + rowoff]);
+                    const uint4 (&bcur)[2] = bq[kx];
+#define HIMO_TERM16(SA, SB)                                                                                        \
+    _Pragma("unroll") for (int mi = 0; mi < MIW; ++mi)                                                               \
+        acc[mi] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[mi][SA], __builtin_bit_cast(f16x8, bcur[SB]), acc[mi], 0, 0, 0);
+                    { HIMO_TERM16(1, 0) HIMO_TERM16(0, 1) HIMO_TERM16(0, 0) }
+#undef HIMO_TERM16
+                    __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x100, MIW * 2, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x008, MIW * 3, 0);
+                }
+            }
+            if (more) {
+                asm volatile("s_waitcnt vmcnt(4)" ::: "memory");     // at most the next slab's first two weight fragments stay in flight
+                __syncthreads();
+            }
+        }
+
+        int ln = threadIdx.x;
+        asm volatile("" : "+v"(ln));                                 // (the epilogue's addresses are formed here, not ahead of the slab loop)
+        const int co = ct * 32 + (ln & 31), lhe = (ln >> 5) & 1;     // this lane's channel, its half-wave
+        const int cl = co < a.Cout ? co : a.Cout - 1;
+        float eA, eB;
+        epi_affine<EPI>(kF16AccScale, a.bias ? a.bias[cl] : 0.f, EPI == kEpiBiasBnGelu ? a.scale[cl] : 1.f, EPI == kEpiBiasBnGelu ? a.shift[cl] : 0.f, eA, eB);
+#pragma unroll
+        for (int mi = 0; mi < MIW; ++mi) {
+            const int e0 = (first + mi) * 32 + 4 * lhe;              // accumulator register r holds list entry e0 + (r & 3) + 8 (r >> 2)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const unsigned four = *reinterpret_cast<const unsigned*>(&s_list[e0 + 8 * g]);      // four consecutive entries
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int pxl = (four >> (8 * j)) & 255;
+                    if (e0 + 8 * g + j < n_occ && co < a.Cout)
+                        yout[((int64_t)(oy0 + (pxl >> 5)) * a.Wo + (ox0 + (pxl & 31))) * a.y_pitch + co] = epi_activate<EPI>(acc[mi][4 * g + j], eA, eB);
+                }
+            }
+        }
+    };
+    if (mine_n == 1) { run(std::integral_constant<int, 1>{}); return; }
+    if (mine_n == 2) { run(std::integral_constant<int, 2>{}); return; }
+    if (mine_n == 3) { run(std::integral_constant<int, 3>{}); return; }
+    run(std::integral_constant<int, 4>{});
+}
+
 // 1x1 layers (row GEMMs over the pixels of an image) on the same structure: a block owns TH = MI * PH segments of 32
 // consecutive pixels, two 16-channel slabs are staged per barrier step, weight fragments run one slab ahead in two
 // register sets.  Same summation order as convbf.hip's row GEMM (slab by slab, terms l*h, h*l, h*h): identical bits.
@@ -403,6 +639,11 @@ void launch_conv_presplit1(const ConvPlan& p, hipStream_t s) {
 
 // 3x3 layers (stride 1 | 2) whose input is in the split activation format: mi image rows per wave, nt 32-channel column tiles per wave
 void launch_conv_presplit3(const ConvPlan& p, hipStream_t s) {
+    if (p.args.act_flags & kActRowMask) {                        // one variant: listed pixels of 8 x 32 tiles, float32 output
+        if (p.epi == kEpiBias) hipLaunchKernelGGL((conv3_rowmask_kernel<kEpiBias>), p.grid, dim3(256), 0, s, p.args, (const unsigned short*)p.w_packed);
+        else hipLaunchKernelGGL((conv3_rowmask_kernel<kEpiBiasBnGelu>), p.grid, dim3(256), 0, s, p.args, (const unsigned short*)p.w_packed);
+        return;
+    }
     if (p.stride == 2) { if (p.ph == 1) launch_sg<1, 2, 2>(p, s); else launch_sg<2, 1, 2>(p, s); }
     else if (p.nt == 2) {
         if (p.ph == 4) launch_sg<4, 2, 1, 2>(p, s);

@@ -57,6 +57,8 @@ struct PillarArgs {
                               //        in HBM sector writes), one 16-byte load per point in the feature kernel
     unsigned long long* occ;  // incremental images (or NULL): bit c of word w = cell 64 w + c was non-empty the LAST time this
                               //        workspace's image was written -- an empty cell that was empty then is already zero
+    unsigned long long* occ_out;   // himo_sweep.d_occupancy (or NULL): the same layout for THIS pass, in a buffer of the caller's --
+                              //        a row mask for the layers that are read at this sweep's cells only (convsg.hip, kActRowMask)
 };
 
 // up to twelve sweeps per launch (blockIdx.y selects the sweep): the stage's kernels are latency chains on small grids,
@@ -201,7 +203,11 @@ __global__ __launch_bounds__(256) void pillar_feature_kernel(PillarBatch m) {
         const unsigned long long below = (1ull << threadIdx.x) - 1ull;
         if (cnt == 1) s_list[__popcll(one & below)] = threadIdx.x;
         if (cnt > 1) s_list[__popcll(one) + __popcll(many & below)] = threadIdx.x;
-        if (threadIdx.x == 0) { s_nlist = __popcll(one | many); if (a.occ) a.occ[blockIdx.x] = one | many; }
+        if (threadIdx.x == 0) {
+            s_nlist = __popcll(one | many);
+            if (a.occ) a.occ[blockIdx.x] = one | many;
+            if (a.occ_out) a.occ_out[blockIdx.x] = one | many;
+        }
     }
     // zero rows of the empty cells (those that are not zero already): 16 bytes per lane, 8 lanes per 128-byte row, 32 rows per pass
 #pragma unroll
@@ -678,6 +684,7 @@ static int sweeps_status(int n_sweeps, const himo_sweep* h_sweeps, int image_pit
     if (image_split && (image_pitch & 15)) return HIMO_ERR_INVALID_ARGUMENT;
     for (int i = 0; i < n_sweeps; ++i) {
         if (image_split && (reinterpret_cast<uintptr_t>(h_sweeps[i].d_image) & 63)) return HIMO_ERR_INVALID_ARGUMENT;
+        if (reinterpret_cast<uintptr_t>(h_sweeps[i].d_occupancy) & 7) return HIMO_ERR_INVALID_ARGUMENT;
         for (int j = 0; check_shared && j < i; ++j)
             if (h_sweeps[j].d_workspace == h_sweeps[i].d_workspace) return HIMO_ERR_INVALID_ARGUMENT;     // one workspace per sweep
     }
@@ -760,6 +767,7 @@ extern "C" int himo_pillarize_multi_ex(int n_sweeps, const himo_sweep* h_sweeps,
                                    w.d_workspace, workspace_bytes, incremental);
         if (st != HIMO_OK) return st;
         m.s[i].image_split = image_split ? 1 : 0;
+        m.s[i].occ_out = reinterpret_cast<unsigned long long*>(w.d_occupancy);
     }
     return pillar_launch(m, n_sweeps, (hipStream_t)stream);
 }
@@ -920,6 +928,7 @@ extern "C" int himo_pillar_features_multi(int n_sweeps, const himo_sweep* h_swee
                                    w.d_workspace, workspace_bytes, incremental);
         if (st != HIMO_OK) return st;
         m.s[i].image_split = image_split ? 1 : 0;
+        m.s[i].occ_out = reinterpret_cast<unsigned long long*>(w.d_occupancy);
     }
     hipStream_t s = (hipStream_t)stream;
     const int cells = grid_w * grid_h;

@@ -56,6 +56,7 @@ class HiMoPipeline:
         self.auto = net is None and precision == "auto"
         self._net_args = dict(params=params, device=self.device, max_points=max_points, max_batch=max_batch)
         self.net = net if net is not None else SeFlowNet(precision="f16x2" if self.auto else precision, **self._net_args)
+        self._set_sparse_dec4()
         self.compdis = CompDisEngine(device=self.device)
         self._batch = None
         self._bufs, self._turn = {}, 0
@@ -126,9 +127,18 @@ class HiMoPipeline:
             grp = samples[lo:lo + mb]
             self.net.forward_batch([(s.pch1, s.pc0, s.pc1, s.pose_h1, s.pose0, s.pose1) for s in grp], outs[lo:lo + mb])
 
+    def _set_sparse_dec4(self):
+        """The pipeline reads the decoder output through the fused head alone, i.e. at the cells of pc0's points: where the network
+        has the masked kernel (fp16 split, split activations, fused head) dec4 forms only those cells; off everywhere else (the
+        bf16x3 fallback of "auto", ``split_acts = False``)."""
+        net = self.net
+        if hasattr(net, "sparse_dec4"):
+            net.sparse_dec4 = bool(net.precision == "f16x2" and net.fused_head and net.split_acts)
+
     def _fall_back(self):
         """precision="auto": leave the fp16 split for the bf16 split (float32 range) for good"""
         self.net = SeFlowNet(precision="bf16x3", **self._net_args)
+        self._set_sparse_dec4()
 
     def _guard_begin(self):
         """fp16 split: zero the network's finite-flow word (the fused head ORs 1 into it when it writes a NaN / inf flow value,

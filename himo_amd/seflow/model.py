@@ -32,10 +32,12 @@ class ConvDesc(ctypes.Structure):
                 ("aux_out", ctypes.c_void_p), ("aux_out_pitch", ctypes.c_int), ("w_packed", ctypes.c_void_p),
                 ("tile_hint", ctypes.c_int), ("packed_format", ctypes.c_int),
                 ("n_outer", ctypes.c_int), ("x_outer_stride", ctypes.c_int64), ("y_outer_stride", ctypes.c_int64),
-                ("act_layout", ctypes.c_int), ("range_seen", ctypes.c_void_p)]
+                ("act_layout", ctypes.c_int), ("range_seen", ctypes.c_void_p),
+                ("mask", ctypes.c_void_p), ("mask_batch_stride", ctypes.c_int64), ("mask_outer_stride", ctypes.c_int64)]
 
 
 ACT_SPLIT_IN, ACT_SPLIT_OUT = 1, 2      # himo_conv_desc.act_layout: x / y in the split activation format (csrc/convsg.hip)
+ACT_ROW_MASK = 32                       # with ACT_SPLIT_IN: only the output pixels whose bit is set in ``mask`` are formed and written
 ACT_ACCUMULATE = 8                      # y += result (two-term bf16 3x3 kernel, float32 maps)
 ACT_STUFFED_2X = 16                     # x is a compact [H/2][W/2] map read as its zero-stuffed x2 image (same kernel)
 
@@ -90,7 +92,7 @@ class HimoSweep(ctypes.Structure):
     """mirror of `himo_sweep` (include/himo_amd.h)"""
     _fields_ = [("n", ctypes.c_int64), ("d_pts", ctypes.c_void_p), ("pc_stride", ctypes.c_int), ("transform", ctypes.c_float * 16),
                 ("d_xyz_t", ctypes.c_void_p), ("d_pid", ctypes.c_void_p), ("d_offsets", ctypes.c_void_p), ("d_image", ctypes.c_void_p),
-                ("d_workspace", ctypes.c_void_p)]
+                ("d_workspace", ctypes.c_void_p), ("d_occupancy", ctypes.c_void_p)]
 
 
 class HimoOp(ctypes.Structure):
@@ -174,6 +176,9 @@ class SeFlowNet:
         # gathers) is stored already split -- fp16 pairs in place of floats, csrc/convsg.hip -- and staged by LDS-DMA;
         # results are bit-identical either way.  False keeps every activation buffer float32 (the training pass reads them)
         self._split_acts = precision == "f16x2"
+        # dec4 formed only at the cells that hold a point of the sweep the head gathers at (csrc/convsg.hip, ACT_ROW_MASK); off
+        # by default -- DEC's other cells then keep whatever they held.  pipeline.HiMoPipeline switches it on
+        self._sparse_dec4 = False
         self.tiles = {}
         self.lib = _lib.load()
         self.device = device if device is not None else _lib.require_gpu()
@@ -255,7 +260,12 @@ class SeFlowNet:
         self.T3 = buf((H // 2) * (W // 2), 64)
         self.CAT3 = buf(H * W, 128)
         self.U = [buf(H * W, 64) for _ in range(2)]
+        # DEC: the decoder output the head gathers, float32.  With ``sparse_dec4`` only the cells that hold a point of pc0 (a set bit
+        # of ``occ0``) are defined after a backbone pass; every other cell keeps what an earlier pass, or the allocator, left there
         self.DEC = buf(H * W, 64)
+        # occupancy of the head's sweep (frame slot HEAD_SLOT = pc0), one bit per cell, bit c of word w = cell 64 w + c: written by
+        # the pillar stage of every forward (himo_sweep.d_occupancy), read by dec4 as its row mask.  Fixed address, new contents per batch
+        self.occ0 = torch.zeros((B, (H * W + 63) // 64), dtype=torch.int64, device=dev)
         self.max_points = 0
         self._reserve_points(max_points)
         # guard words of the fp16 split (one buffer, one clear, one read-back).  [0] finite-flow guard: the fused head ORs 1 into it
@@ -320,8 +330,25 @@ class SeFlowNet:
         on = bool(on)
         if on != self._split_acts:
             self._split_acts = on
+            if not on:
+                self._sparse_dec4 = False              # the masked kernel reads split activations only
             self.drop_plan()                           # recorded operator lists carry the old layout flags
             self.reset_images()                        # the persisted image bytes are in the other format
+
+    HEAD_SLOT = 1                         # frame slot of pc0, the sweep whose points the head gathers at
+
+    @property
+    def sparse_dec4(self) -> bool:
+        return self._sparse_dec4
+
+    @sparse_dec4.setter
+    def sparse_dec4(self, on: bool):
+        on = bool(on)
+        if on and not (self.packed_format == 1 and self._split_acts and self.fused_head):
+            raise ValueError("sparse_dec4 needs precision='f16x2' with split activations and the fused head")
+        if on != self._sparse_dec4:
+            self._sparse_dec4 = on
+            self.drop_plan()                           # recorded operator lists carry the layout flag and the mask pointer
 
     @property
     def B0(self):
@@ -374,10 +401,11 @@ class SeFlowNet:
     # ---- launch helpers ---------------------------------------------------------------------------
     def _conv(self, x, x_bs, x_pitch, wname, y, y_bs, y_pitch, n, h, w, cin, cout, ks, stride, epi, x_off=0, y_off=0,
               scale=None, shift=None, aux_in=None, aux_in_pitch=0, aux_out=None, aux_out_pitch=0, bias=None, batched=True,
-              act=0):
+              act=0, mask=None):
         """``x`` / ``y``: activation buffers [sample][...] -- with ``batched`` the layer runs over the first
         ``self._nb`` samples in one launch (outer stride = one sample of the buffer).  ``act``: ACT_SPLIT_IN / _OUT when
-        x / y are in the split activation format (only honoured with ``self.split_acts``)."""
+        x / y are in the split activation format (only honoured with ``self.split_acts``).  ``mask``: [sample][words] int64
+        row mask (ACT_ROW_MASK): only the output pixels whose bit is set are formed and written."""
         d = ConvDesc()
         d.x = x.data_ptr() + 4 * x_off; d.x_batch_stride = x_bs; d.x_pitch = x_pitch
         if batched and self._nb > 1:
@@ -394,6 +422,9 @@ class SeFlowNet:
         d.w_packed = None if pk is None else pk.data_ptr()
         d.packed_format = self.packed_format
         d.act_layout = act if self.split_acts else 0
+        if mask is not None:
+            d.act_layout |= ACT_ROW_MASK
+            d.mask, d.mask_batch_stride, d.mask_outer_stride = mask.data_ptr(), 0, mask.stride(0)
         if (d.act_layout & ACT_SPLIT_OUT) and self.packed_format == 1 and epi in (EPI_BIAS, EPI_BIAS_BN_GELU):
             d.range_seen = self._range_word(wname)
         key = (n * max(d.n_outer, 1), h, w, cin, cout, ks, stride, epi, pk is not None, d.act_layout)
@@ -408,7 +439,7 @@ class SeFlowNet:
     def _tune(self, d: "ConvDesc") -> int:
         """Time the tile variants of one layer shape once (the kernels are idempotent for the non-GRU epilogues; the
         GRU ones update state in place, so they keep the library heuristic) and remember the fastest."""
-        if d.epilogue in (EPI_GRU_ZR, EPI_GRU_Q):
+        if d.epilogue in (EPI_GRU_ZR, EPI_GRU_Q) or (d.act_layout & ACT_ROW_MASK):      # (the masked kernel has one variant)
             return 0
         cands = [(bn << 4) | mi for bn in (128, 64) if not (bn == 128 and d.cout % 128) for mi in (2, 1)]
         if d.act_layout:                                  # split activation format: only the weights-from-L2 structures
@@ -520,7 +551,9 @@ class SeFlowNet:
         s = block("dec1", self.F3, 256 * F, H // 8, W // 8, self.T1, self.CAT1, self.F2, 128 * F, 256, 256, self.S, ("dec2", self.T2, 128))
         t = block("dec2", s, 256, H // 4, W // 4, self.T2, self.CAT2, self.F1, 64 * F, 128, 128, self.T, ("dec3", self.T3, 64))
         u = block("dec3", t, 128, H // 2, W // 2, self.T3, self.CAT3, self.B0, 32 * F, 64, 64, self.U)
-        self._conv(u, 0, 64, "dec4", self.DEC, 0, 64, 1, H, W, 64, 64, 3, 1, EPI_BIAS, act=IN)      # DEC stays float32: the head gathers it
+        # DEC stays float32: the head gathers it -- at the cells of pc0's points only, so with sparse_dec4 nothing else is formed
+        self._conv(u, 0, 64, "dec4", self.DEC, 0, 64, 1, H, W, 64, 64, 3, 1, EPI_BIAS, act=IN,
+                   mask=self.occ0 if self._sparse_dec4 else None)
         return self.DEC
 
     def head(self, pc0: torch.Tensor, slot0: int = 1, slot1: int = 2, out: torch.Tensor | None = None) -> torch.Tensor:
@@ -597,6 +630,8 @@ class SeFlowNet:
         """The fused head (csrc/gruhead.hip) over samples ``samples`` (default 0..len(pc0s)-1) of the activation buffers
         in ONE launch."""
         p, pk, F = self.p, self.packed, self.F
+        if self._sparse_dec4 and slot0 != self.HEAD_SLOT:
+            raise ValueError("sparse_dec4: DEC is defined at the cells of frame slot HEAD_SLOT only")
         samples = list(range(len(pc0s))) if samples is None else list(samples)
         for lo in range(0, len(pc0s), self.MAX_HEAD_SAMPLES):
             grp = range(lo, min(lo + self.MAX_HEAD_SAMPLES, len(pc0s)))
@@ -651,6 +686,7 @@ class SeFlowNet:
                     w.d_xyz_t, w.d_pid, w.d_offsets = st["xyz_t"][slot].data_ptr(), st["pid"][slot].data_ptr(), st["offsets"][slot].data_ptr()
                     w.d_image = self.B0[sample].data_ptr() + 4 * 32 * slot
                     w.d_workspace = st["ws_slots"][slot].data_ptr()
+                    w.d_occupancy = self.occ0[sample].data_ptr() if slot == self.HEAD_SLOT else None
             status = self.lib.himo_pillarize_multi_ex(len(arr), ctypes.addressof(arr), self._range, self._voxel, self._centre, self.W, self.H,
                                                       self.p["pfn.weight"].data_ptr(), self.p["pfn.scale"].data_ptr(),
                                                       self.p["pfn.shift"].data_ptr(), 32 * self.F, self._pt[0]["ws_slots"][0].numel(),
@@ -687,6 +723,7 @@ class SeFlowNet:
         w.d_xyz_t, w.d_pid, w.d_offsets = self.xyz_t[slot].data_ptr(), self.pid[slot].data_ptr(), self.offsets[slot].data_ptr()
         w.d_image = self.B0[self._sample].data_ptr() + 4 * 32 * slot
         w.d_workspace = self.ws_slots[slot].data_ptr()
+        w.d_occupancy = self.occ0[self._sample].data_ptr() if slot == self.HEAD_SLOT else None
         st = self.lib.himo_pillarize_multi_ex(1, ctypes.addressof(arr), self._range, self._voxel, self._centre, self.W, self.H,
                                               self.p["pfn.weight"].data_ptr(), self.p["pfn.scale"].data_ptr(),
                                               self.p["pfn.shift"].data_ptr(), 32 * self.F, self.ws_slots[slot].numel(),

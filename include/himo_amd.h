@@ -524,6 +524,12 @@ typedef struct himo_sweep {
     float* d_xyz_t; int32_t* d_pid; float* d_offsets;      /* per-point outputs as in himo_pillarize */
     float* d_image;                                        /* first of this sweep's 32 image channels */
     void* d_workspace;
+    uint64_t* d_occupancy;                                 /* NULL, or grid_w * grid_h / 64 (rounded up) words, 8-byte aligned: bit c of
+                                                              word w is set when cell 64 w + c holds a point of THIS pass -- the feature
+                                                              kernel's own list of non-empty cells, every word written.  Not the
+                                                              incremental-image bits of the workspace (those describe the previous
+                                                              pass).  A himo_conv_desc.d_mask for the layers whose output is read at this
+                                                              sweep's cells only.  Misaligned: HIMO_ERR_INVALID_ARGUMENT (step 1) */
 } himo_sweep;
 int himo_pillarize_multi(int n_sweeps, const himo_sweep* h_sweeps, const float* h_range, const float* h_voxel,
                          const float* h_centre_offset, int grid_w, int grid_h, const float* d_pfn_weight,
@@ -539,7 +545,8 @@ int himo_pillarize_multi(int n_sweeps, const himo_sweep* h_sweeps, const float* 
  * Refusals of the multi-sweep forms (himo_pillar_features_multi included), in the order they are checked, nothing launched:
  *   1. HIMO_ERR_INVALID_ARGUMENT  n_sweeps outside [1, 12], h_sweeps NULL (himo_pillar_features_multi: d_scale / d_shift NULL);
  *                                 HIMO_IMAGE_SPLIT with image_pitch not a multiple of 16 or a sweep's d_image not 64-byte
- *                                 aligned; two sweeps naming the same workspace (himo_pillarize_multi*);
+ *                                 aligned; a sweep's d_occupancy not 8-byte aligned; two sweeps naming the same workspace
+ *                                 (himo_pillarize_multi*);
  *   2. then sweep by sweep, steps 1-3 of himo_pillarize; with HIMO_IMAGE_INCREMENTAL step 3 (HIMO_ERR_WORKSPACE) also refuses a
  *      workspace_bytes that is not a multiple of 16 or leaves no room for the occupancy words behind the sweep's lists.
  * himo_pillar_occupancy_reset: HIMO_ERR_INVALID_ARGUMENT for a NULL workspace or a grid side < 1, HIMO_ERR_UNSUPPORTED beyond
@@ -594,6 +601,8 @@ typedef struct himo_conv_desc {
       rows 8                same, 3x3 stride 1, cout <= 64    two 32-channel column tiles per wave,   ignored (heuristic) on wider layers or when the
                                                               8-row tiles                             output does not admit 16-byte stores
       rows 12               same, 3x3 stride 1, cout > 64     4 rows x 64 channels per wave           ignored (heuristic) likewise
+      any value             same with HIMO_ACT_ROW_MASK       one variant (8 x 32 pixels x 64         ignored
+                                                              channels, listed pixels only)
       anything else         --                                --                                      the tile is the heuristic's, but a non-zero value
                                                                                                       without 0x1000 still selects the family as the
                                                                                                       first row does (packed 3x3 layers) */
@@ -616,9 +625,21 @@ typedef struct himo_conv_desc {
                                                               max(2^-25 absolute, 2^-23 relative): a layer whose word stays 0
                                                               after a forward pass sits on the absolute floor and the caller
                                                               should redo the pass in the bf16 split (pipeline.HiMoPipeline does) */
+    const uint64_t* d_mask;                                /* HIMO_ACT_ROW_MASK: one bit per OUTPUT pixel -- bit c of 64-bit word w is
+                                                              pixel 64 w + c of the image, pixels numbered iy * w_in + ix (the order of
+                                                              himo_sweep.d_occupancy).  Only pixels whose bit is set are computed and
+                                                              written; every other byte of y keeps what it held.  (h * w_in + 63) / 64
+                                                              words per image, 8-byte aligned */
+    int64_t mask_batch_stride, mask_outer_stride;          /* in 64-bit words: image i's mask starts at d_mask + (i % n) *
+                                                              mask_batch_stride + (i / n) * mask_outer_stride, as x and y do */
 } himo_conv_desc;
 #define HIMO_ACT_SPLIT_IN 1
 #define HIMO_ACT_SPLIT_OUT 2
+#define HIMO_ACT_ROW_MASK 32    /* with HIMO_ACT_SPLIT_IN and nothing else: d_mask selects the output pixels (csrc/convsg.hip,
+                                   conv3_rowmask_kernel; values bit-identical to the unmasked layer's).  Admitted: ksize 3, stride 1,
+                                   packed_format HIMO_PACK_F16X2, bias or bias+BN+GELU epilogue, float32 output, cout <= 64, w_in a multiple
+                                   of 32.  HIMO_ERR_INVALID_ARGUMENT for a NULL or misaligned d_mask, HIMO_ERR_UNSUPPORTED for every other
+                                   descriptor that carries the bit; nothing is written either way */
 #define HIMO_ACT_ACCUMULATE 8   /* alone: y += result instead of y = result -- float32 maps, 3x3 stride 1, packed_format HIMO_PACK_BF16X2,
                                    bias epilogue (the training step's stride-2 data gradients add into the decoder's skip gradient in place);
                                    also ksize 1 (row GEMM) with packed weights of either bf16 split and the bias epilogue, output map below
