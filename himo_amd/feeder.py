@@ -476,6 +476,12 @@ class ReaderPool:
 
     # ---- the child ---------------------------------------------------------------------------------------------------
     def _child(self, w):
+        # everything inherited through the fork stays out of this process's collector: unreachable cycles of the parent that hold a
+        # device or pinned tensor, an event or a stream would otherwise be finalised HERE, by whichever allocation of the reader
+        # starts a collection, and their release calls into a HIP runtime the child must not touch (observed: a reader died of a
+        # segmentation fault while "Garbage-collecting" under ``results.put``, forked from a process that had run many device tests)
+        import gc
+        gc.freeze()
         tasks, results, maps = self._tasks[w], self._results, self._maps
         while True:
             t = tasks.get()

@@ -24,7 +24,8 @@ Admitted: every value finite and positive, ``half <= 64``.
    order (``ssl_label._compact``).
 1. Clusters.  ``ssl_label.dbscan(a, EPS, MIN_PTS, skip=~participates)`` over ALL participating points of ``a`` (not only dynamic
    candidates: the rigid fit of a static cluster is its own sanity check).  Labels run 1..C; label 0 and the points that take no
-   part get the identity transform.
+   part get the identity transform.  ``IcpFlow(cluster="hdbscan", min_cluster_size=, min_samples=)`` takes the clusters from
+   ``ssl_label.hdbscan`` ("HDBSCAN, v1"; its own host wait for the edge list) instead: nothing else of the rule changes.
 2. Translation vote (integers: exact).  Every clustered point ``a_i`` and every target point ``q_j`` with ``|q_z - a_z| <= z_gate``
    (one float32 subtraction) give ``kx = rint((q_x - a_x) / bin)`` and ``ky = rint((q_y - a_y) / bin)`` in float32: a true
    division, round half to even.  The pair votes for bin ``(kx, ky)`` of its cluster iff ``|kx|, |ky| <= half``; a cluster has
@@ -120,10 +121,20 @@ class IcpFlow:
     docstring).  After a fit ``last_status`` (int32 [C, 4]: state, inliers, kx, ky), ``last_transforms`` (float64 [C, 5]: c, s,
     tx, ty, tz) and ``last_labels`` (int32 [N0]) describe it (host copies, made when asked for).  There is no CPU path."""
 
-    def __init__(self, device=None, params: IcpParams | None = None, eps: float | None = None, min_pts: int | None = None):
-        """``eps`` / ``min_pts``: the clustering of rule 1 when not ``ssl_label.EPS`` / ``MIN_PTS`` (sparser sweeps)"""
+    def __init__(self, device=None, params: IcpParams | None = None, eps: float | None = None, min_pts: int | None = None,
+                 cluster: str = "dbscan", min_cluster_size: int | None = None, min_samples: int | None = None):
+        """``eps`` / ``min_pts``: the clustering of rule 1 when not ``ssl_label.EPS`` / ``MIN_PTS`` (sparser sweeps).  ``cluster``:
+        "dbscan" (the default) or "hdbscan" with ``min_cluster_size`` / ``min_samples`` (``ssl_label.HDB_MIN_CLUSTER`` /
+        ``HDB_MIN_SAMPLES`` when None)"""
         from . import _lib
-        from .seflow.ssl_label import EPS, MIN_PTS
+        from .seflow.ssl_label import CLUSTERINGS, EPS, HDB_MIN_CLUSTER, HDB_MIN_SAMPLES, MIN_PTS
+        if cluster not in CLUSTERINGS:
+            raise ValueError(f"cluster={cluster!r}: one of {', '.join(CLUSTERINGS)}")
+        self.cluster = cluster
+        self.min_cluster_size = int(HDB_MIN_CLUSTER if min_cluster_size is None else min_cluster_size)
+        self.min_samples = int(HDB_MIN_SAMPLES if min_samples is None else min_samples)
+        if self.min_cluster_size < 2 or not 1 <= self.min_samples <= 32:
+            raise ValueError(f"min_cluster_size={min_cluster_size!r} (>= 2), min_samples={min_samples!r} (1..32)")
         self.eps, self.min_pts = float(EPS if eps is None else eps), int(MIN_PTS if min_pts is None else min_pts)
         if not (math.isfinite(self.eps) and self.eps > 0 and self.min_pts >= 1):
             raise ValueError(f"eps={eps!r}, min_pts={min_pts!r}: a finite positive radius and a positive count")
@@ -148,7 +159,7 @@ class IcpFlow:
     def fit(self, pc0, pc1, gm0, gm1, pose0, pose1):
         import torch
         from . import _lib
-        from .seflow.ssl_label import RANGE_NET, _compact, _moved, dbscan
+        from .seflow.ssl_label import RANGE_NET, _compact, _moved, cluster_points
         from .ssl_loss import GRID_CELL, GRID_H, GRID_W, GRID_X0, GRID_Y0
         lib, dev, s, P = self.lib, self.device, _lib.stream_handle, _lib.ptr
         up = lambda x, dt: (x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))).to(device=dev, dtype=dt)
@@ -170,7 +181,7 @@ class IcpFlow:
         a = _moved(p0, T)                                           # rule 0
         b = p1[:, :3].contiguous()
         use_a = ~(g0 | (a[:, :2].abs().amax(dim=1) > RANGE_NET))
-        labels, count = dbscan(a, self.eps, self.min_pts, ~use_a)             # rule 1
+        labels, count = cluster_points(a, ~use_a, self.cluster, self.eps, self.min_pts, self.min_cluster_size, self.min_samples)   # rule 1
         if n1:
             use_b = ~(g1 | (b[:, :2].abs().amax(dim=1) > RANGE_NET))
             buf_b, _, cnt_b = _compact(b, use_b)

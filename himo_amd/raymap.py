@@ -42,7 +42,9 @@ F. Labels of a target sweep (``cluster_labels``; host glue on existing kernels).
    and ``MIN_PTS`` over the target's points that are not ground, are finite and lie inside ``RANGE_NET`` in x and y.  A DBSCAN
    cluster with ``n`` points, of which ``k`` are DYNAMIC, is a dynamic cluster iff ``k >= 3`` and ``4*k >= n`` (``min_dynamic = 3``,
    ``share = (1, 4)``).  Dynamic clusters are renumbered 1..K in ascending order of their DBSCAN id; every other point is 0,
-   including DYNAMIC points that DBSCAN left as noise.
+   including DYNAMIC points that DBSCAN left as noise.  ``cluster_labels(cluster="hdbscan", min_cluster_size=, min_samples=)`` /
+   ``--cluster hdbscan`` takes the clusters from ``ssl_label.hdbscan`` ("HDBSCAN, v1"; parity unpinned) over the same points instead;
+   the default is DBSCAN, and nothing else of this rule changes.
 G. The map of a target sweep ``t`` in a scene (``dynamic_flags``).  The neighbours are the sweeps ``t-window .. t+window`` of the same
    scene without ``t``, clipped to the scene (``window`` 5: at most 10 neighbours; admitted up to 8).  Neighbour ``k`` gets slot = its
    rank among the neighbours; its points are moved with ``T = inv(pose_t) @ pose_k``, computed in float64 on the host, rounded to
@@ -62,7 +64,8 @@ and ego speed 5 m/s the rule flagged 3.1 % of the wall points and 93.6 % of the 
 tried only with ``guard`` 1, at ego speed 10 m/s: 4.8 % of its points were flagged, and 6.5 % of the wall.  Without the ``fv > hv``
 clause the wall share was 3.7 % (guard 2) to 13 % (guard 1).  NOTHING HAS BEEN MEASURED ON FIELD DATA.
 
-The program: ``python -m himo_amd.raymap --data_dir D [--window 5] [--key ray_label] [--dynamic_key ray_dynamic] [--overwrite]`` walks
+The program: ``python -m himo_amd.raymap --data_dir D [--window 5] [--key ray_label] [--dynamic_key ray_dynamic] [--overwrite]
+[--cluster dbscan|hdbscan [--min_cluster_size M --min_samples K]]`` walks
 the ``<scene>.h5`` files of ``D``, reads ``lidar``, ``pose`` and ``ground_mask`` of every sweep (``python -m himo_amd.ground_seg``
 writes the masks) and writes ``<timestamp>/<key>`` (int32, rule F) and ``<timestamp>/<dynamic_key>`` (uint8, the flags of rule E)
 INTO the scene file.  There is no CPU path.
@@ -217,12 +220,17 @@ def dynamic_flags(sweeps, poses, grounds, t: int, params: RaymapParams | None = 
     return out + (moved,) if return_moved else out
 
 
-def cluster_labels(points, ground, dynamic, min_dynamic: int = MIN_DYNAMIC, share: tuple = SHARE, return_ids: bool = False):
+def cluster_labels(points, ground, dynamic, min_dynamic: int = MIN_DYNAMIC, share: tuple = SHARE, return_ids: bool = False,
+                   cluster: str = "dbscan", min_cluster_size: int | None = None, min_samples: int | None = None):
     """Rule F: int32 device labels [n] of a target sweep from its points (device (n, >= 3) float32), its ground mask and the DYNAMIC
-    flags of rule E.  ``return_ids``: also the DBSCAN ids the labels were derived from.  Waits for the cluster count."""
+    flags of rule E.  ``return_ids``: also the cluster ids the labels were derived from.  ``cluster``: "dbscan" (the default) or
+    "hdbscan" with ``min_cluster_size`` / ``min_samples`` (``ssl_label.HDB_MIN_CLUSTER`` / ``HDB_MIN_SAMPLES`` when None).  Waits for
+    the cluster count."""
     import torch
     from . import _lib
-    from .seflow.ssl_label import RANGE_NET, dbscan
+    from .seflow.ssl_label import CLUSTERINGS, EPS, HDB_MIN_CLUSTER, HDB_MIN_SAMPLES, MIN_PTS, RANGE_NET, cluster_points
+    if cluster not in CLUSTERINGS:
+        raise ValueError(f"cluster={cluster!r}: one of {', '.join(CLUSTERINGS)}")
     dev = _lib.require_gpu()
     p = _device_points(points, dev)
     n = p.shape[0]
@@ -232,7 +240,8 @@ def cluster_labels(points, ground, dynamic, min_dynamic: int = MIN_DYNAMIC, shar
         z = torch.zeros(0, dtype=torch.int32, device=dev)
         return (z, z.clone()) if return_ids else z
     skip = (up(ground).reshape(-1) != 0) | ~torch.isfinite(p).all(dim=1) | ~(p[:, :2].abs().amax(dim=1) <= RANGE_NET)
-    ids, _ = dbscan(p, skip=skip)
+    ids, _ = cluster_points(p, skip, cluster, EPS, MIN_PTS, HDB_MIN_CLUSTER if min_cluster_size is None else min_cluster_size,
+                            HDB_MIN_SAMPLES if min_samples is None else min_samples)
     idx = ids.to(torch.int64)
     top = int(idx.max().item()) + 1
     size = torch.bincount(idx, minlength=top)
@@ -248,7 +257,8 @@ def cluster_labels(points, ground, dynamic, min_dynamic: int = MIN_DYNAMIC, shar
 # the program
 # --------------------------------------------------------------------------------------------------------------------------
 def label_scene(path, params: RaymapParams | None = None, window: int = 5, key: str = "ray_label", dynamic_key: str = "ray_dynamic",
-                overwrite: bool = False, opener=None) -> dict:
+                overwrite: bool = False, opener=None, cluster: str = "dbscan", min_cluster_size: int | None = None,
+                min_samples: int | None = None) -> dict:
     """One scene file: read ``lidar``, ``pose`` and ``ground_mask`` of every sweep, compute the labels of every sweep, and only once
     the reads are done open the file for modification and write ``<timestamp>/<key>`` (int32) and ``<timestamp>/<dynamic_key>``
     (uint8).  Returns {"sweeps", "points", "dynamic", "clusters", "seconds"} (seconds: upload, carving, clustering and the copy back;
@@ -281,7 +291,7 @@ def label_scene(path, params: RaymapParams | None = None, window: int = 5, key: 
         grid = new_map(params, dev)
         for t in range(len(stamps)):
             dyn, _, _ = dynamic_flags(on_dev, poses, masks, t, params, window, grid=grid)
-            lab = cluster_labels(on_dev[t], masks[t], dyn)
+            lab = cluster_labels(on_dev[t], masks[t], dyn, cluster=cluster, min_cluster_size=min_cluster_size, min_samples=min_samples)
             labels.append(lab.cpu().numpy().astype(np.int32))
             flags.append(dyn.cpu().numpy().astype(np.uint8))
     seconds = time.perf_counter() - t0
@@ -304,11 +314,15 @@ def label_scene(path, params: RaymapParams | None = None, window: int = 5, key: 
 
 
 def main(data_dir: str, window: int = 5, key: str = "ray_label", dynamic_key: str = "ray_dynamic", overwrite: bool = False,
-         params: RaymapParams | None = None) -> dict:
+         params: RaymapParams | None = None, cluster: str = "dbscan", min_cluster_size: int | None = None,
+         min_samples: int | None = None) -> dict:
     """The program.  Under ``torchrun`` (one rank per GPU) the scenes are dealt round-robin to the ranks, so every file has one
     writer.  Returns {scene: what ``label_scene`` returned} of this rank."""
     from . import distenv
     from .save import h5_writer
+    from .seflow.ssl_label import CLUSTERINGS
+    if cluster not in CLUSTERINGS:
+        raise ValueError(f"cluster={cluster!r}: one of {', '.join(CLUSTERINGS)}")
     params = params if params is not None else RaymapParams()
     scenes = sorted(Path(data_dir).glob("*.h5"))
     if not scenes:
@@ -322,7 +336,8 @@ def main(data_dir: str, window: int = 5, key: str = "ray_label", dynamic_key: st
         err = None
         try:
             for path in scenes[rank::world]:
-                s = done[path.stem] = label_scene(path, params, window, key, dynamic_key, overwrite, opener=lambda p: mod.File(p, "a"))
+                s = done[path.stem] = label_scene(path, params, window, key, dynamic_key, overwrite, opener=lambda p: mod.File(p, "a"),
+                                                       cluster=cluster, min_cluster_size=min_cluster_size, min_samples=min_samples)
                 share = s["dynamic"] / s["points"] if s["points"] else 0.0
                 rate = s["sweeps"] / s["seconds"] if s["seconds"] > 0 else float("inf")
                 print(f"{path.stem}: {s['sweeps']} sweeps, {s['points']} points, {100.0 * share:.1f} % dynamic, {s['clusters']} clusters "
@@ -342,12 +357,17 @@ def _parser():
     ap.add_argument("--key", default="ray_label", help="dataset name of the int32 cluster labels (seflow.fit --ssl_label <key>)")
     ap.add_argument("--dynamic_key", default="ray_dynamic", help="dataset name of the uint8 per-point flags of rule E")
     ap.add_argument("--overwrite", action="store_true", help="replace existing datasets instead of refusing the scene")
+    ap.add_argument("--cluster", default="dbscan", help="the clustering of rule F: 'dbscan' (the default) or 'hdbscan' (HDBSCAN, v1; parity "
+                                                        "unpinned); anything else is refused")
+    ap.add_argument("--min_cluster_size", type=int, default=None, help="--cluster hdbscan: the smallest cluster (ssl_label.HDB_MIN_CLUSTER)")
+    ap.add_argument("--min_samples", type=int, default=None, help="--cluster hdbscan: the core neighbour count, 1..32 (ssl_label.HDB_MIN_SAMPLES)")
     return ap
 
 
 def _cli(argv=None):
     a = _parser().parse_args(argv)
-    main(a.data_dir, a.window, a.key, a.dynamic_key, a.overwrite)
+    main(a.data_dir, a.window, a.key, a.dynamic_key, a.overwrite, cluster=a.cluster, min_cluster_size=a.min_cluster_size,
+         min_samples=a.min_samples)
 
 
 if __name__ == "__main__":

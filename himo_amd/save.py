@@ -362,11 +362,12 @@ def run_nsfp(dataset, res_name: str = "nsfp", sink=None, by_scene: bool = False,
     return run_fastnsf(dataset, res_name, sink=sink, by_scene=by_scene, iters=iters, engine=NSFP, **fit_options)
 
 
-def run_icpflow(dataset, res_name: str = "icpflow", sink=None, by_scene: bool = False, params=None):
+def run_icpflow(dataset, res_name: str = "icpflow", sink=None, by_scene: bool = False, params=None, cluster: str = "dbscan",
+                min_cluster_size=None, min_samples=None):
     """``--model icpflow``: the clustering + rigid-ICP baseline instead of the network (``himo_amd/icpflow.py``, "cluster-rigid ICP,
     v1"; PARITY UNPINNED like the network) -- no checkpoint, no fit: DBSCAN clusters of the non-ground points of pc0, one yaw +
     translation per cluster against pc1, the flow of every pc0 row including ego motion stored under ``res_name`` exactly like the
-    network's.  Needs both sweeps' ground masks (``gm0`` / ``gm1``).  Results leave through the same pinned-buffer writer thread as
+    network's.  ``cluster="hdbscan"``: the clusters of "HDBSCAN, v1" (``ssl_label.hdbscan``) instead.  Needs both sweeps' ground masks (``gm0`` / ``gm1``).  Results leave through the same pinned-buffer writer thread as
     ``run``'s."""
     import torch.distributed as dist
     rank, world = (dist.get_rank(), dist.get_world_size()) if dist.is_available() and dist.is_initialized() else (0, 1)
@@ -389,7 +390,7 @@ def run_icpflow(dataset, res_name: str = "icpflow", sink=None, by_scene: bool = 
             if icp is None:
                 from .feeder import ResultDrain
                 from .icpflow import IcpFlow
-                icp = IcpFlow(params=params)
+                icp = IcpFlow(params=params, cluster=cluster, min_cluster_size=min_cluster_size, min_samples=min_samples)
                 drain = ResultDrain(deliver, device=icp.device)
             drain.put((i, f0), icp.fit(np.asarray(f0["pc0"]), np.asarray(pc1), np.asarray(f0["gm0"]), np.asarray(gm1), f0["pose0"], f0["pose1"]))
             done += 1
@@ -402,16 +403,21 @@ def run_icpflow(dataset, res_name: str = "icpflow", sink=None, by_scene: bool = 
 
 
 def main(checkpoint: str = "", dataset_path: str = "", res_name: str = "", model: str = "", iters: int = 100, objective: str = "dt",
-         lr: float = 0.0, patience: int = -1):
+         lr: float = 0.0, patience: int = -1, cluster: str = "dbscan", min_cluster_size=None, min_samples=None):
     """``python -m himo_amd.save --checkpoint <weights.npz> --dataset_path <dir>`` (the feed-forward network), or
     ``--model fastnsf --dataset_path <dir>`` (the optimisation-based baseline, README.md:50-53), or ``--model icpflow`` (clustering +
     rigid ICP per cluster; needs the scenes' ground masks); under ``torchrun`` one rank per GPU.  ``--model fastnsf --objective nn`` is
     the NSFP baseline (result key ``nsfp``; ``iters`` is its cap; ``model="nsfp"`` itself is not a spelling this program takes).
-    ``lr=0.0`` / ``patience=-1`` mean the model's own defaults; ``patience=0`` never stops early (NSFP only)."""
+    ``lr=0.0`` / ``patience=-1`` mean the model's own defaults; ``patience=0`` never stops early (NSFP only).  ``cluster``:
+    ``--model icpflow`` only, "dbscan" (the default) or "hdbscan" with ``min_cluster_size`` / ``min_samples``."""
     from . import distenv
     from .dataset import SAVE_FIELDS, NpzDataset, open_dataset
     if model not in ("", "seflowpp", "deflowpp", "fastnsf", "icpflow"):
         raise ValueError(f"model={model!r}: this build runs the SeFlow++-style network (default), 'fastnsf' and 'icpflow'")
+    if cluster not in ("dbscan", "hdbscan"):
+        raise ValueError(f"cluster={cluster!r}: 'dbscan' (the default) or 'hdbscan'")
+    if cluster != "dbscan" and model != "icpflow":
+        raise ValueError(f"cluster={cluster!r}: only --model icpflow clusters")
     if objective not in ("dt", "nn"):
         raise ValueError(f"objective={objective!r}: 'dt' (FastNSF's distance transform) or 'nn' (NSFP's truncated Chamfer distance)")
     fastnsf, icpflow = model == "fastnsf", model == "icpflow"
@@ -435,7 +441,8 @@ def main(checkpoint: str = "", dataset_path: str = "", res_name: str = "", model
         try:
             done = (run_nsfp(ds, name, sink=sink, by_scene=not npz, iters=iters, **fit_options) if nsfp else
                     run_fastnsf(ds, name, sink=sink, by_scene=not npz, iters=iters, **fit_options) if fastnsf else
-                    run_icpflow(ds, name, sink=sink, by_scene=not npz) if icpflow else
+                    run_icpflow(ds, name, sink=sink, by_scene=not npz, cluster=cluster, min_cluster_size=min_cluster_size,
+                                min_samples=min_samples) if icpflow else
                     run(ds, name, params, sink=sink, by_scene=not npz))
         except Exception as e:                                  # arrive at the rendezvous anyway, then re-raise
             err = e
@@ -457,9 +464,12 @@ if __name__ == "__main__":
                                                       "is spelled: '--model nsfp' is refused")
     ap.add_argument("--lr", type=float, default=0.0, help="learning rate of the fit (0: the model's own -- fastnsf 1e-3, NSFP 8e-3)")
     ap.add_argument("--patience", type=int, default=-1, help="NSFP's early-stopping patience (-1: its own, 100; 0: never stop before --iters)")
+    ap.add_argument("--cluster", default="dbscan", help="--model icpflow only: 'dbscan' (the default) or 'hdbscan' (HDBSCAN, v1; parity unpinned)")
+    ap.add_argument("--min_cluster_size", type=int, default=None, help="--cluster hdbscan: the smallest cluster (ssl_label.HDB_MIN_CLUSTER)")
+    ap.add_argument("--min_samples", type=int, default=None, help="--cluster hdbscan: the core neighbour count, 1..32 (ssl_label.HDB_MIN_SAMPLES)")
     import sys
     # the reference's program takes hydra-style overrides (`save.py checkpoint=... dataset_path=...`, `model=fastnsf`: README.md:46-53)
     argv = [("--" + x) if (not x.startswith("-") and "=" in x and x.split("=", 1)[0] in ("checkpoint", "dataset_path", "res_name", "model", "iters", "objective", "lr", "patience"))
             else x for x in sys.argv[1:]]
     a = ap.parse_args(argv)
-    main(a.checkpoint, a.dataset_path, a.res_name, a.model, a.iters, a.objective, a.lr, a.patience)
+    main(a.checkpoint, a.dataset_path, a.res_name, a.model, a.iters, a.objective, a.lr, a.patience, a.cluster, a.min_cluster_size, a.min_samples)

@@ -971,6 +971,29 @@ size_t himo_dbscan_workspace_bytes(int n, int grid_w, int grid_h);
 int himo_dbscan(int n, const float* d_xyz, int pitch, const unsigned char* d_skip, float eps, int min_pts, float x0, float y0, float cell,
                 int grid_w, int grid_h, int32_t* d_labels, int32_t* d_n_clusters, void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* HDBSCAN beside DBSCAN ("HDBSCAN, v1": this build's own rule, PARITY UNPINNED like its neighbours; the rule is written out in
+ * csrc/hdbscan.hip and himo_amd/seflow/ssl_label.py, its restatement is tests/hdbscan_ref.py).  Two phases:
+ *   himo_hdbscan_mst   (device, asynchronous, never synchronises) the minimum spanning tree of the mutual-reachability graph of the
+ *                      participating points P under the strict edge order (w, lo, hi).  d_xyz [n][pitch >= 3] float32; d_skip [n] bytes or
+ *                      NULL (non-zero, or a NaN coordinate: the point takes no part); 1 <= min_samples <= 32.  Writes d_counts [4] int32:
+ *                      {|P|, edges emitted, Boruvka rounds taken, 0}; d_index [n] int32: the original indices of P, ascending, in its
+ *                      first |P| entries; d_core2 [n] float32 or NULL: the squared core distance by ORIGINAL index, +inf for a point that
+ *                      takes no part or has fewer than min_samples points around; d_edges [n - 1][3] uint32: {bits of the float32 weight
+ *                      w, lo, hi} with lo < hi original indices, |P| - 1 of them in no particular order (none when |P| < max(min_samples,
+ *                      2)).  The cost is quadratic in |P| per round, ceil(log2 n) rounds at most; core2 is a brute-force k-select.
+ *   himo_hdbscan_tree  (host, plain C++, no HIP call) dendrogram, condensed tree, stabilities, excess-of-mass selection and labels from
+ *                      HOST copies of d_index and d_edges: h_labels [n] int32: 0 = noise / no part, 1 .. K = clusters in the order of their
+ *                      lowest point index; h_n_clusters: K (or NULL).  An edge list that is not a spanning tree of the n_part points
+ *                      (wrong count, an index that is out of range or takes no part, lo >= hi, a weight that is no non-negative float, a
+ *                      cycle) is refused with HIMO_ERR_INVALID_ARGUMENT; n_part < max(min_samples, 2) wants n_edges == 0 and labels all 0.
+ * himo_hdbscan_workspace_bytes: grid_w, grid_h >= 1 are the BEV cell grid of a core-distance search that is not built (the brute-force
+ * form keeps no cell table); 0 for arguments it refuses.  Errors as himo_dbscan: HIMO_ERR_INVALID_ARGUMENT, HIMO_ERR_WORKSPACE. */
+size_t himo_hdbscan_workspace_bytes(int n, int grid_w, int grid_h);
+int himo_hdbscan_mst(int n, const float* d_xyz, int pitch, const unsigned char* d_skip, int min_samples, int32_t* d_counts, int32_t* d_index,
+                     float* d_core2, uint32_t* d_edges, void* d_workspace, size_t workspace_bytes, void* stream);
+int himo_hdbscan_tree(int n, int n_part, const int32_t* h_index, int n_edges, const uint32_t* h_edges, int min_cluster_size, int min_samples,
+                      int32_t* h_labels, int32_t* h_n_clusters);
+
 /* FastNSF (README.md:53 `model=fastnsf`; specification himo_amd/fastnsf.py, PARITY UNPINNED) -- one optimiser iteration of the
  * coordinate MLP as THREE launches (csrc/nsffused.hip):
  *   himo_nsf_forward   the MLP over all points (activations spilled as two-term bf16 matrix fragments + ReLU mask bits for the backward
