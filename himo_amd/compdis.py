@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .sweeps import SweepPacker, host_upload  # noqa: F401  (host_upload: scripts import it from here)
 
 # `CLOSE_DISTANCE_THRESHOLD` comes from the reference's absent OpenSceneFlow submodule (eval.py:21 / save_zip.py:26 import it from
 # `src.utils.av2_eval`); 35 m is the Argoverse-2 convention, recorded as unverified in SURVEY.md 0.1.  THIS is the one place the
@@ -32,14 +33,6 @@ EGO_BOX = {
     "scania": ([-9.5, -3 / 2, 0], [5, 2.760004 / 2, 5]),
     "av2": ([-1.5, -1.5, -2.0], [1.5, 1.5, 2.0]),
 }
-
-
-def host_upload(dev):
-    """default ``upload(parts, dtype)``: concatenate on the host, one synchronous copy to ``dev``"""
-    def up(parts, dtype):
-        host = np.concatenate([np.asarray(p).astype(dtype, copy=False) for p in parts], axis=0)
-        return torch.from_numpy(np.ascontiguousarray(host)).to(dev, non_blocking=False)
-    return up
 
 
 @dataclass
@@ -87,26 +80,10 @@ class FrameBatch:
         ``host_ego``: ``ego_pose = inv(pose1) @ pose0`` of every frame comes from numpy in the poses' own dtype -- the very expression of
         save_zip.py:115, so the 4x4 bits are the reference's and a singular pose raises numpy's ``LinAlgError`` -- instead of the library's
         float64 LU (within 1 ulp of it in the results; ``run_frame`` has the same switch)."""
-        dev = device if device is not None else _lib.require_gpu()
-        to_dev = upload if upload is not None else host_upload(dev)
-        frames = list(frames)
-        if not frames:
-            raise ValueError("empty batch")
+        p = SweepPacker(frames, upload, device)
+        frames, cat, to_dev = p.frames, p.cat, p.upload
         raw = res_name in (None, "raw")
-        counts = [int(np.asarray(f["pc0"]).shape[0]) for f in frames]
-        offsets = np.zeros(len(frames) + 1, dtype=np.int64)
-        np.cumsum(counts, out=offsets[1:])
         stride = int(np.asarray(frames[0]["pc0"]).shape[1])
-
-        def cat(key, dtype, width=None):
-            parts = []
-            for f, n in zip(frames, counts):
-                a = np.asarray(f[key])
-                if a.shape[0] != n:
-                    raise ValueError(f"{key}: {a.shape[0]} rows for a sweep of {n} points")
-                parts.append(a)
-            return to_dev(parts, dtype)
-
         if host_ego:
             egos = [np.linalg.inv(np.asarray(f["pose1"])) @ np.asarray(f["pose0"]) for f in frames]      # save_zip.py:115
             f32_chain = all(e.dtype == np.float32 for e in egos)
@@ -114,11 +91,9 @@ class FrameBatch:
         else:
             pose_dtypes = {np.asarray(f[k]).dtype for f in frames for k in ("pose0", "pose1")}
             f32_chain = all(dt == np.float32 for dt in pose_dtypes)
-            pose0 = to_dev([np.stack([np.asarray(f["pose0"], dtype=np.float64) for f in frames])], np.float64)
-            pose1 = to_dev([np.stack([np.asarray(f["pose1"], dtype=np.float64) for f in frames])], np.float64)
+            pose0, pose1 = p.stack("pose0", np.float64), p.stack("pose1", np.float64)
         b = cls(
-            offsets_host=offsets,
-            offsets=to_dev([offsets], np.int64),
+            offsets_host=p.offsets_host, offsets=p.offsets,
             pose0=pose0, pose1=pose1,
             pc0=cat("pc0", np.float32, stride),
             lidar_dt=cat("lidar_dt", np.float32),
@@ -136,7 +111,7 @@ class FrameBatch:
             if all("flow_instance_id" in f for f in frames):
                 b.instance = cat("flow_instance_id", np.int32)             # (the uint32 column's bits: ``astype(np.uint32)`` wraps alike)
             from . import feather
-            b.gt_offsets_host = gt_body_offsets(offsets, feather.gt_schema(b.category is not None, b.instance is not None)[1])
+            b.gt_offsets_host = gt_body_offsets(p.offsets_host, feather.gt_schema(b.category is not None, b.instance is not None)[1])
             b.gt_offsets = to_dev([b.gt_offsets_host], np.int64)            # rides in the batch's one upload: no copy at launch time
         return b
 

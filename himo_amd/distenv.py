@@ -3,7 +3,7 @@
 applied to its serial per-frame loops (save_zip.py:112, eval.py:281): frame i belongs to rank i % world, every rank drives
 the GPU of its LOCAL_RANK, and the only exchange is the final gather / barrier.
 
-Without this, ``_dist()`` would see no process group, every rank would walk the whole dataset on cuda:0 and all of them
+Without this, ``rank_world()`` would see no process group, every rank would walk the whole dataset on cuda:0 and all of them
 would race on the same result files.  The group is RCCL (``"nccl"``) when a HIP device is visible, gloo otherwise (the
 CPU tests); ``HIMO_DIST_BACKEND`` overrides.
 """
@@ -12,6 +12,14 @@ from __future__ import annotations
 import os
 from contextlib import contextmanager
 from datetime import timedelta
+
+
+def rank_world() -> tuple:
+    """(rank, world) of the process group that is initialised, (0, 1) without one: what the sharded loops deal their items by"""
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized():
+        return dist.get_rank(), dist.get_world_size()
+    return 0, 1
 
 
 def launched_world() -> int:
@@ -102,3 +110,14 @@ def rendezvous(err: Exception | None, what: str = "its share of the frames") -> 
         raise err
     if not everyone:
         raise RuntimeError(f"another rank failed; this rank finished {what}")
+
+
+def run_shard(loop, what: str = "its share of the frames") -> None:
+    """``loop()`` -- this rank's share of the work -- then the rendezvous, which a rank whose loop raised an ``Exception`` reaches too
+    (``rendezvous`` raises it there)."""
+    err = None
+    try:
+        loop()
+    except Exception as e:                                       # (an interrupt leaves at once; the launcher ends the job)
+        err = e
+    rendezvous(err, what)

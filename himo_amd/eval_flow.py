@@ -38,7 +38,8 @@ import numpy as np
 
 from . import _lib
 from .eval import BUCKETED_METACATAGORIES, CATEGORY_TO_INDEX
-from .eval_seg import as_labels_u8, parse_res_names  # noqa: F401  (parse_res_names is part of this module's interface)
+from .eval_seg import parse_res_names  # noqa: F401  (parse_res_names is part of this module's interface)
+from .sweeps import MissingKey, SweepPacker, fed, raise_missing, sharded_batches, timed
 
 CLASS_NAMES = ("BACKGROUND", "CAR", "OTHER_VEHICLES", "PEDESTRIAN", "WHEELED_VRU")
 KINDS = ("FD", "FS", "BS")
@@ -138,32 +139,14 @@ class FlowBatch:
         ``res_names`` (``raw`` packs nothing) and, for Scania, ``flow_is_valid`` (packed when every frame has it).  A missing key
         is a ``KeyError``; an array whose length differs from ``pc0``'s raises ``ValueError`` naming the sweep.
         ``upload(parts, dtype)``: the feeder's staging (``feeder.BatchFeeder``); None: one plain copy per array."""
-        from .compdis import host_upload
-        frames = list(frames)
-        if not frames:
-            raise ValueError("empty batch")
-        if upload is None:
-            upload = host_upload(device if device is not None else _lib.require_gpu())
-        counts = [int(np.asarray(f["pc0"]).shape[0]) for f in frames]
-        offsets = np.zeros(len(frames) + 1, dtype=np.int64)
-        np.cumsum(counts, out=offsets[1:])
-
-        def cat(key, dtype, width=None, labels=False):
-            parts = []
-            for f, n in zip(frames, counts):
-                a = as_labels_u8(f[key]) if labels else np.asarray(f[key])
-                if a.shape[0] != n or (width is not None and a.shape[1:] != (width,)):
-                    raise ValueError(f"{f.get('scene_id')} at {f.get('timestamp')}: {key} has shape {a.shape} for a sweep of {n} points")
-                parts.append(a)
-            return upload(parts, dtype)
-        return cls(offsets, upload([offsets], np.int64),
-                   upload([np.stack([np.asarray(f["pose0"], dtype=np.float64) for f in frames])], np.float64),
-                   upload([np.stack([np.asarray(f["pose1"], dtype=np.float64) for f in frames])], np.float64),
+        p = SweepPacker(frames, upload, device)
+        cat = p.cat
+        return cls(p.offsets_host, p.offsets, p.stack("pose0", np.float64), p.stack("pose1", np.float64),
                    cat("pc0", np.float32), cat("flow", np.float32, 3),
                    [None if name == "raw" else cat(name, np.float32, 3) for name in res_names],
                    cat("flow_category_indices", np.uint8, labels=True), cat("gm0", np.uint8, labels=True),
-                   cat("flow_is_valid", np.uint8, labels=True) if all("flow_is_valid" in f for f in frames) else None,
-                   keys if keys is not None else range(len(frames)))
+                   cat("flow_is_valid", np.uint8, labels=True) if all("flow_is_valid" in f for f in p.frames) else None,
+                   keys if keys is not None else range(len(p.frames)))
 
 
 def _nanmean(values) -> float:
@@ -373,29 +356,18 @@ def merge_json(path, results: dict) -> dict:
     return data
 
 
-class _MissingKey(Exception):
-    """carries the warnings printed before a KeyError to the thread that prints"""
-
-    def __init__(self, key, lines):
-        super().__init__(key)
-        self.key, self.lines = key, list(lines)
-
-
 def run_dataset(dataset, metrics: FlowMetrics, batch_frames: int = 32, overlap: bool = True) -> int:
     """Shared body of ``main``: sweep i of ``dataset`` on rank i % world, ``batch_frames`` sweeps per launch.  A sweep without
     ``flow`` or ``flow_category_indices`` is skipped with a warning line; one that lacks a stored result name (or another array
     the rule reads) raises ``KeyError`` naming it.  With ``overlap`` the batches are read, packed and copied two ahead by
     ``feeder.BatchFeeder``.  Returns the sweeps this rank evaluated."""
-    from .save_zip import _dist
-    rank, world, _ = _dist()
-    mine = list(range(rank, len(dataset), world))
     names = metrics.res_names
     required = ["pc0", "pose0", "pose1", "gm0"] + (["flow_is_valid"] if metrics.data_name == "scania" else []) + [n for n in names if n != "raw"]
 
     def batches():
-        for lo in range(0, len(mine), batch_frames):
+        for mine in sharded_batches(dataset, batch_frames):
             frames, keys, lines = [], [], []
-            for i in mine[lo:lo + batch_frames]:
+            for i in mine:
                 f = dataset[i]
                 lacking = [k for k in ("flow", "flow_category_indices") if k not in f]
                 if lacking:
@@ -404,49 +376,27 @@ def run_dataset(dataset, metrics: FlowMetrics, batch_frames: int = 32, overlap: 
                 for key in required:
                     if key not in f:
                         lines.append(f"[Warning]: No {key} in {f['scene_id']} at {f['timestamp']}, check the data.")
-                        raise _MissingKey(key, lines)
+                        raise MissingKey(key, lines)
                 frames.append(f)
                 keys.append(i)
             yield frames, keys, lines
 
-    def show(lines):
-        for line in lines:
-            print(line)
-
-    done = 0
-    if not overlap:
-        try:
-            for frames, keys, lines in batches():
-                show(lines)
-                metrics.add(frames, keys)
-                done += len(frames)
-        except _MissingKey as e:
-            show(e.lines)
-            raise KeyError(e.key) from None
-        return done
-
-    from .feeder import BatchFeeder
-    dev = metrics.device if metrics.device is not None else _lib.require_gpu()
-    metrics.device = dev
+    if overlap and metrics.device is None:
+        metrics.device = _lib.require_gpu()
 
     def build(item, upload):
         frames, keys, lines = item
-        batch = FlowBatch.from_frames(frames, names, device=dev, upload=upload, keys=keys) if frames else None
-        return (batch, lines), []                   # (the feeder keeps the staged blocks alive itself)
-    feed = BatchFeeder(batches(), build, device=dev)
+        return (FlowBatch.from_frames(frames, names, device=metrics.device, upload=upload, keys=keys) if frames else None), lines
+    done = 0
     try:
-        for batch, lines in feed:
-            show(lines)
+        for batch, lines in fed(batches(), build, device=metrics.device, overlap=overlap):
+            for line in lines:
+                print(line)
             if batch is not None:
                 metrics.add_batch(batch)
                 done += batch.sweeps
-    except _MissingKey as e:
-        feed.close()
-        show(e.lines)
-        raise KeyError(e.key) from None
-    except BaseException:
-        feed.close()
-        raise
+    except MissingKey as e:
+        raise_missing(e)
     return done
 
 
@@ -461,20 +411,19 @@ def main(data_dir: str = "/home/kin/data/av2/h5py/sensor/himo", res_names="seflo
     names = parse_res_names(res_names)
     if data_name == "auto":
         data_name = data_name_of(data_dir)
+
+    def loop():
+        t0 = time.perf_counter()
+        data = dataset
+        if data is None:
+            stored = [n for n in names if n != "raw"]
+            data = open_dataset(data_dir, vis_name=stored, eval=True, fields=FLOW_EVAL_FIELDS + tuple(stored), zero_copy=True)
+        done = run_dataset(data, metrics, batch_frames=batch_frames)
+        metrics.buckets                                          # (wait for the device: the loop's time includes its kernels)
+        metrics.loop = {"seconds": time.perf_counter() - t0, "sweeps": done}
     with distenv.process_group() as (rank, world):
         metrics = FlowMetrics(names, data_name)
-        err = None
-        t0 = time.perf_counter()
-        try:
-            if dataset is None:
-                stored = [n for n in names if n != "raw"]
-                dataset = open_dataset(data_dir, vis_name=stored, eval=True, fields=FLOW_EVAL_FIELDS + tuple(stored), zero_copy=True)
-            done = run_dataset(dataset, metrics, batch_frames=batch_frames)
-            metrics.buckets                                      # (wait for the device: the loop's time includes its kernels)
-            metrics.loop = {"seconds": time.perf_counter() - t0, "sweeps": done}
-        except Exception as e:                                   # (an interrupt leaves at once; the launcher ends the job)
-            err = e
-        distenv.rendezvous(err, "its sweeps, but no table was printed")
+        distenv.run_shard(loop, "its sweeps, but no table was printed")
         metrics.gather()
         if rank == 0:
             print(metrics.table(), end="")
@@ -496,9 +445,4 @@ def _cli(argv=None):
 
 
 if __name__ == "__main__":
-    start_time = time.time()
-    got = _cli()
-    print(f"Time used: {time.time() - start_time:.2f} s")
-    loop = getattr(got, "loop", None)
-    if loop is not None:
-        print(f"Evaluation loop: {loop['sweeps'] / max(loop['seconds'], 1e-9):.0f} sweeps/s ({loop['sweeps']} sweeps in {loop['seconds']:.2f} s)")
+    timed(_cli)

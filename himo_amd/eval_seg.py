@@ -25,6 +25,7 @@ import numpy as np
 from . import _lib
 from .eval import ANNOTATION_CATEGORIES, BUCKETED_METACATAGORIES
 from .eval import CATEGORY_TO_INDEX as _AV2_CATEGORY_TO_INDEX
+from .sweeps import MissingKey, SweepPacker, fed, raise_missing, sharded_batches, timed
 
 # the package's AV2 table (eval.py; the reference builds the same dict from av2's AnnotationCategories, eval_seg.py:24-27)
 CATEGORY_TO_INDEX = dict(_AV2_CATEGORY_TO_INDEX)
@@ -198,18 +199,9 @@ class SegBatch:
         """``frames``: dicts with ``flow_category_indices``, ``seg_valid`` and every name of ``res_names`` (a missing key is the
         reference's KeyError, eval_seg.py:248 / :260).  ``upload(parts, dtype)``: the feeder's staging (``feeder.BatchFeeder``);
         None: one plain copy per array."""
-        import torch
-        if upload is None:
-            dev = device if device is not None else _lib.require_gpu()
-
-            def upload(parts, dtype):
-                return torch.from_numpy(np.concatenate(parts).astype(dtype, copy=False)).to(dev)
-        cols = [[as_labels_u8(f[key]) for f in frames] for key in ("flow_category_indices", "seg_valid") + tuple(res_names)]
-        for f, *arrays in zip(frames, *cols):
-            if len({a.shape[0] for a in arrays}) != 1:
-                raise ValueError(f"{f.get('scene_id')} at {f.get('timestamp')}: label arrays of different lengths")
-        gt, valid, *preds = [upload(parts, np.uint8) for parts in cols]
-        return cls(gt, valid, preds, len(frames))
+        p = SweepPacker(frames, upload, device, count_key="flow_category_indices")
+        gt, valid, *preds = [p.cat(key, np.uint8, labels=True) for key in ("flow_category_indices", "seg_valid") + tuple(res_names)]
+        return cls(gt, valid, preds, len(p.frames))
 
 
 class SegMetrics:
@@ -310,15 +302,12 @@ def run_dataset(dataset, metrics: SegMetrics, batch_frames: int = 32, overlap: b
     result name raises ``KeyError`` naming it, where the reference fails (eval_seg.py:248, :260).  With ``overlap`` the batches
     are read, packed and copied two ahead by ``feeder.BatchFeeder``; the warnings travel with their batch and are printed by the
     calling thread, in sweep order.  Returns the sweeps this rank evaluated."""
-    from .save_zip import _dist
-    rank, world, _ = _dist()
-    mine = list(range(rank, len(dataset), world))
     names = metrics.res_names
 
     def batches():
-        for lo in range(0, len(mine), batch_frames):
+        for keys in sharded_batches(dataset, batch_frames):
             frames, lines = [], []
-            for i in mine[lo:lo + batch_frames]:
+            for i in keys:
                 f = dataset[i]
                 lines += sweep_warnings(f, names)
                 if "flow_category_indices" not in f:
@@ -326,57 +315,27 @@ def run_dataset(dataset, metrics: SegMetrics, batch_frames: int = 32, overlap: b
                     continue
                 for key in ["seg_valid"] + names:
                     if key not in f:
-                        raise _MissingKey(key, lines)
+                        raise MissingKey(key, lines)
                 frames.append(f)
             yield frames, lines
 
-    def show(lines):
-        for line in lines:
-            print(line)
-
-    done = 0
-    if not overlap:
-        try:
-            for frames, lines in batches():
-                show(lines)
-                metrics.add(frames)
-                done += len(frames)
-        except _MissingKey as e:
-            show(e.lines)
-            raise KeyError(e.key) from None
-        return done
-
-    from .feeder import BatchFeeder
-    dev = metrics.device if metrics.device is not None else _lib.require_gpu()
-    metrics.device = dev
+    if overlap and metrics.device is None:
+        metrics.device = _lib.require_gpu()
 
     def build(item, upload):
         frames, lines = item
-        batch = SegBatch.from_frames(frames, names, device=dev, upload=upload) if frames else None
-        return (batch, lines), []                   # (the feeder keeps the staged blocks alive itself)
-    feed = BatchFeeder(batches(), build, device=dev)
+        return (SegBatch.from_frames(frames, names, device=metrics.device, upload=upload) if frames else None), lines
+    done = 0
     try:
-        for batch, lines in feed:
-            show(lines)
+        for batch, lines in fed(batches(), build, device=metrics.device, overlap=overlap):
+            for line in lines:
+                print(line)
             if batch is not None:
                 metrics.add_batch(batch)
                 done += batch.sweeps
-    except _MissingKey as e:
-        feed.close()
-        show(e.lines)
-        raise KeyError(e.key) from None
-    except BaseException:
-        feed.close()
-        raise
+    except MissingKey as e:
+        raise_missing(e)
     return done
-
-
-class _MissingKey(Exception):
-    """carries the warnings printed before the reference's KeyError to the thread that prints"""
-
-    def __init__(self, key, lines):
-        super().__init__(key)
-        self.key, self.lines = key, list(lines)
 
 
 def main(data_dir: str = "/home/kin/data/av2/h5py/sensor/himo", res_names: list = ["seg_raw", "seg_flow"],  # noqa: B006
@@ -388,19 +347,16 @@ def main(data_dir: str = "/home/kin/data/av2/h5py/sensor/himo", res_names: list 
     from .dataset import SEG_FIELDS, open_dataset
 
     names = parse_res_names(res_names)
+
+    def loop():
+        t0 = time.perf_counter()
+        data = dataset if dataset is not None else open_dataset(data_dir, vis_name=names, eval=True, fields=SEG_FIELDS + tuple(names), need_next=False)
+        done = run_dataset(data, metrics, batch_frames=batch_frames)
+        metrics.conf                                             # (wait for the device: the loop's time includes its kernels)
+        metrics.loop = {"seconds": time.perf_counter() - t0, "sweeps": done}
     with distenv.process_group() as (rank, world):
         metrics = SegMetrics(names)
-        err = None
-        t0 = time.perf_counter()
-        try:
-            if dataset is None:
-                dataset = open_dataset(data_dir, vis_name=names, eval=True, fields=SEG_FIELDS + tuple(names), need_next=False)
-            done = run_dataset(dataset, metrics, batch_frames=batch_frames)
-            metrics.conf                                         # (wait for the device: the loop's time includes its kernels)
-            metrics.loop = {"seconds": time.perf_counter() - t0, "sweeps": done}
-        except Exception as e:                                   # (an interrupt leaves at once; the launcher ends the job)
-            err = e
-        distenv.rendezvous(err, "its sweeps, but no table was printed")
+        distenv.run_shard(loop, "its sweeps, but no table was printed")
         metrics.gather()
         if rank == 0:
             for mode in ((0, 1) if both else ((1,) if mask_only else (0,))):
@@ -421,9 +377,4 @@ def _cli(argv=None):
 
 
 if __name__ == "__main__":
-    start_time = time.time()
-    got = _cli()
-    print(f"Time used: {time.time() - start_time:.2f} s")
-    loop = getattr(got, "loop", None)
-    if loop is not None:
-        print(f"Evaluation loop: {loop['sweeps'] / max(loop['seconds'], 1e-9):.0f} sweeps/s ({loop['sweeps']} sweeps in {loop['seconds']:.2f} s)")
+    timed(_cli)

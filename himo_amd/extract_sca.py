@@ -36,6 +36,7 @@ from pathlib import Path
 import numpy as np
 
 from .eval_seg import CATEGORY_TO_INDEX
+from .sweeps import SweepPacker, draining, fed, sweep_offsets
 
 BOUNDING_BOX_EXPANSION_DEFAULT = 0.2
 BOUNDING_BOX_EXPANSION = float(os.environ.get("HIMO_BOUNDING_BOX_EXPANSION", str(BOUNDING_BOX_EXPANSION_DEFAULT)))
@@ -178,23 +179,16 @@ class LabelBatch:
 
     def __init__(self, sweeps, background: int, device=None, upload=None):
         """``sweeps``: [(pc f32 [N,4], ego1_SE3_ego0 f64 [4,4] or [3,4], (geom, obj_flow, cls, vel_finite))]"""
-        from . import _lib
-        from .compdis import host_upload
-        dev = device if device is not None else _lib.require_gpu()
-        up = upload if upload is not None else host_upload(dev)
+        p = SweepPacker([{"pc": pc, "ego": np.asarray(ego, dtype=np.float64)[:3, :4], "scene_id": "sweep", "timestamp": k}
+                         for k, (pc, ego, _) in enumerate(sweeps)], upload, device, count_key="pc")
+        up = p.upload
         self.n = len(sweeps)
         self.background = int(background)
-        self.offsets_host = np.zeros(self.n + 1, dtype=np.int64)
-        self.box_offsets_host = np.zeros(self.n + 1, dtype=np.int32)
-        for k, (pc, _, table) in enumerate(sweeps):
-            if np.asarray(pc).ndim != 2 or np.asarray(pc).shape[1] != 4:
-                raise ValueError(f"sweep {k}: points are rows of x, y, z, intensity")
-            self.offsets_host[k + 1] = self.offsets_host[k] + len(pc)
-            self.box_offsets_host[k + 1] = self.box_offsets_host[k] + len(table[0])
-        self.offsets = up([self.offsets_host], np.int64)
+        self.offsets_host, self.offsets = p.offsets_host, p.offsets
+        self.box_offsets_host = sweep_offsets(len(t[0]) for _, _, t in sweeps).astype(np.int32)
         self.box_offsets = up([self.box_offsets_host], np.int32)
-        self.ego = up([np.stack([np.asarray(e, dtype=np.float64)[:3, :4] for _, e, _ in sweeps])], np.float64)
-        self.pc = up([pc for pc, _, _ in sweeps], np.float32)
+        self.ego = p.stack("ego", np.float64)
+        self.pc = p.cat("pc", np.float32, 4)
         self.geom = up([t[0].reshape(-1, 8) for _, _, t in sweeps], np.float64)
         self.obj_flow = up([t[1].reshape(-1, 3) for _, _, t in sweeps], np.float32)
         self.box_class = up([t[2] for _, _, t in sweeps], np.uint8)
@@ -256,15 +250,8 @@ class GroundBatch:
     parity with the reference's own segmenter unpinned), uploaded with the batch that labels the boxes."""
 
     def __init__(self, pcs, params, device=None, upload=None):
-        from . import _lib
-        from .compdis import host_upload
-        dev = device if device is not None else _lib.require_gpu()
-        up = upload if upload is not None else host_upload(dev)
-        self.params = params
-        self.offsets_host = np.zeros(len(pcs) + 1, dtype=np.int64)
-        self.offsets_host[1:] = np.cumsum([len(pc) for pc in pcs])
-        self.offsets = up([self.offsets_host], np.int64)
-        self.pc = up(pcs, np.float32)
+        p = SweepPacker([{"pc": pc} for pc in pcs], upload, device, count_key="pc")
+        self.params, self.offsets_host, self.offsets, self.pc = params, p.offsets_host, p.offsets, p.cat("pc", np.float32)
 
     @property
     def total_points(self) -> int:
@@ -451,7 +438,7 @@ def run_scenes(scenes, origin_data, output_dir, lidar_ext_dir, name_mapping: dic
     import torch
 
     from . import _lib
-    from .feeder import BatchFeeder, ResultDrain
+    from .feeder import ResultDrain
     dev = _lib.require_gpu()
     background = CATEGORY_TO_INDEX[name_mapping["none"]]
     readers = ThreadPoolExecutor(max_workers=max(1, int(nproc)), thread_name_prefix="himo-sca-read")
@@ -487,7 +474,7 @@ def run_scenes(scenes, origin_data, output_dir, lidar_ext_dir, name_mapping: dic
         todo = [r for _, _, r in group if r["label"] is not None]
         batch = LabelBatch([(r["pc"], r["label"][0], r["label"][1]) for r in todo], background, device=dev, upload=upload) if todo else None
         gb = GroundBatch([r["pc"] for _, _, r in group], ground_params, device=dev, upload=upload) if ground_params is not None else None
-        return (group, batch, gb), []
+        return group, batch, gb
 
     files = {}
     written = [0]
@@ -510,27 +497,20 @@ def run_scenes(scenes, origin_data, output_dir, lidar_ext_dir, name_mapping: dic
             written[0] += 1
 
     drain = ResultDrain(sink, device=dev, threads=1, copy=False)
-    feed = BatchFeeder(batches(), build, device=dev)
+    feed = fed(batches(), build, device=dev)
     try:
-        for group, batch, gb in feed:
-            size = out_layout(batch.total_points)[1] if batch is not None else 0
-            extra = gb.total_points if gb is not None else 0
-            out = torch.empty(max(size + extra, 16), dtype=torch.uint8, device=dev)
-            if batch is not None:
-                label_batch(batch, out)
-            if gb is not None and extra:
-                ground_batch(gb, out[size:size + extra])
-            drain.put((group, batch.offsets_host if batch is not None else None, gb.offsets_host if gb is not None else None), out)
-    except BaseException:
-        feed.close()
-        try:
-            drain.close()
-        except BaseException:
-            pass
-        raise
+        with draining(feed, drain):
+            for group, batch, gb in feed:
+                size = out_layout(batch.total_points)[1] if batch is not None else 0
+                extra = gb.total_points if gb is not None else 0
+                out = torch.empty(max(size + extra, 16), dtype=torch.uint8, device=dev)
+                if batch is not None:
+                    label_batch(batch, out)
+                if gb is not None and extra:
+                    ground_batch(gb, out[size:size + extra])
+                drain.put((group, batch.offsets_host if batch is not None else None, gb.offsets_host if gb is not None else None), out)
     finally:
         readers.shutdown(wait=False, cancel_futures=True)
-    drain.close()
     for f in files.values():
         f.close()
     return written[0]
@@ -555,17 +535,14 @@ def main(origin_data: str = "/home/kin/data/Scania/val", metadata_pkl: str = "/h
     with distenv.process_group() as (rank, world):
         mine = scenes[rank::world]
         print(f"Using {nproc} readers for creating {len(mine)} of {len(scenes)} scene.")
-        err = None
-        try:
+
+        def loop():
             ground_params = None
             if ground_mask:
                 from .ground_seg import GroundParams
                 ground_params = GroundParams(sensor_height=sensor_height)
-            run_scenes(mine, origin_data, output_dir, lidar_ext_dir, mapping, nproc=nproc, batch_sweeps=batch_sweeps,
-                       ground_params=ground_params)
-        except Exception as e:                                         # (an interrupt leaves at once; the launcher ends the job)
-            err = e
-        distenv.rendezvous(err, "its scene files, but no index was written")
+            run_scenes(mine, origin_data, output_dir, lidar_ext_dir, mapping, nproc=nproc, batch_sweeps=batch_sweeps, ground_params=ground_params)
+        distenv.run_shard(loop, "its scene files, but no index was written")
         if rank == 0:
             create_reading_index(Path(output_dir))
         if world > 1:

@@ -339,7 +339,7 @@ class BatchFeeder(_Prefetcher):
     """Iterate device-resident batch objects prepared ``depth`` batches ahead of the consumer.
 
     ``source`` yields items (lists of host frame dicts, ...); ``build(item, upload)`` packs one item into a batch object whose
-    device tensors all come from ``upload(parts, dtype)`` and returns ``(object to yield, [its device tensors])``.  A background
+    device tensors all come from ``upload(parts, dtype)`` and returns it (the feeder keeps the staged blocks alive itself).  A background
     thread runs ``build``: ``upload`` concatenates (and converts) the parts STRAIGHT into pinned staging memory on a small
     thread pool (numpy releases the GIL: the arrays of a batch are staged in parallel) and issues the host -> device copies on
     the process's copy stream; the consumer's stream is ordered after them by an event, so it never waits for a copy it did not
@@ -393,7 +393,7 @@ class BatchFeeder(_Prefetcher):
                 return _view(twins[bi], off, shape, pin.dtype)
 
             with torch.cuda.stream(self._stream):
-                obj, _ = self._build(item, upload)
+                obj = self._build(item, upload)
             for job in jobs:
                 job.result()
             for bi, twin in twins.items():
@@ -849,7 +849,5 @@ class EvalFeeder(BatchFeeder):
 
         def build(item, upload):
             frames, comp_dis = item if isinstance(item, tuple) else (item, None)
-            eb = EvalBatch.from_frames(list(frames), res_name, comp_dis, device=dev, upload=upload)
-            b = eb.batch
-            return eb, [b.offsets, b.pose0, b.pose1, b.pc0, b.lidar_dt, b.gm0, b.flow_is_valid, eb.gt, eb.category, eb.instance, eb.est]
+            return EvalBatch.from_frames(list(frames), res_name, comp_dis, device=dev, upload=upload)
         super().__init__(source, build, device=dev, depth=depth, stage_threads=stage_threads)

@@ -98,6 +98,7 @@ def ground_masks(sweeps, params: GroundParams | None = None, device=None, return
     cells.  There is no CPU path."""
     import torch
     from . import _lib
+    from .sweeps import host_upload, sweep_offsets
     params = params if params is not None else GroundParams()
     dev = device if device is not None else _lib.require_gpu()
     sweeps = list(sweeps)
@@ -109,15 +110,13 @@ def ground_masks(sweeps, params: GroundParams | None = None, device=None, return
     if workspace_bytes(len(sweeps), params) == 0:
         raise ValueError("ground_masks: parameters outside r_min > 0, bin_size > 0, 1 <= n_bins <= 4096, 1 <= K <= 512, finite floats")
     pitch = 4 if all(s.shape[1] == 4 for s in sweeps) else 3
-    offsets_host = np.zeros(len(sweeps) + 1, dtype=np.int64)
-    offsets_host[1:] = np.cumsum([s.shape[0] for s in sweeps])
+    offsets_host = sweep_offsets(s.shape[0] for s in sweeps)
     if all(isinstance(s, np.ndarray) for s in sweeps):
-        host = np.concatenate([np.asarray(s[:, :pitch], dtype=np.float32) for s in sweeps], axis=0)
-        pc = torch.from_numpy(np.ascontiguousarray(host)).to(dev)
+        pc = host_upload(dev)([s[:, :pitch] for s in sweeps], np.float32)
     else:
         pc = torch.cat([(torch.from_numpy(np.ascontiguousarray(s, dtype=np.float32)) if isinstance(s, np.ndarray) else s)[:, :pitch]
                         .to(device=dev, dtype=torch.float32) for s in sweeps], dim=0).contiguous()
-    offsets = torch.from_numpy(offsets_host).to(dev)
+    offsets = host_upload(dev)([offsets_host], np.int64)
     cell = None
     if return_cell_ground:
         cell = torch.full((len(sweeps), int(params.n_bins), params.segments), float(np.float32(-np.float32(params.sensor_height))),

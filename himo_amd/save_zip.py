@@ -16,7 +16,6 @@ from __future__ import annotations
 
 import os
 import shutil
-import time
 from pathlib import Path
 from typing import Tuple
 from zipfile import ZipFile
@@ -93,13 +92,6 @@ class ZipSink:
         self.close()
 
 
-def _dist():
-    import torch.distributed as dist
-    if dist.is_available() and dist.is_initialized():
-        return dist.get_rank(), dist.get_world_size(), dist
-    return 0, 1, None
-
-
 OVERLAP = True          # read / stage / copy ahead and write behind on background threads (False: the reference's plain serial loop)
 
 
@@ -112,67 +104,44 @@ def run_dataset(dataset, res_name: str, output_dir: Path, batch_frames: int = 32
     batches ahead (``feeder.BatchFeeder``), the launch thread only enqueues the fused kernel, and the compensation distances
     leave through pinned buffers to a writer thread that encodes and writes the Feather files (``feeder.ResultDrain``)."""
     from .compdis import CompDisEngine, FrameBatch
+    from .sweeps import FeatherSink, draining, fed, sharded_batches
 
     overlap = OVERLAP if overlap is None else overlap
-    rank, world, _ = _dist()
     eng = CompDisEngine(max_frames=batch_frames)
-    mine = list(range(rank, len(dataset), world))
 
     def batches():
-        for lo in range(0, len(mine), batch_frames):
-            frames = [dataset[i] for i in mine[lo:lo + batch_frames]]
+        for keys in sharded_batches(dataset, batch_frames):
+            frames = [dataset[i] for i in keys]
             for f in frames:
                 if len(f["lidar_dt"]) == 0:
                     raise ValueError("max() arg is an empty sequence")       # save_zip.py:120
             yield frames
 
-    written = 0
-    if not overlap:
-        for frames in batches():
-            batch = FrameBatch.from_frames(frames, res_name)
-            host = eng.run(batch, sensor_dt=sensor_dt)["comp_dis"].cpu().numpy()      # one D2H copy per batch
-            o = batch.offsets_host
-            for k, f in enumerate(frames):
-                write_output_file(host[o[k]:o[k + 1]], (f["scene_id"], str(f["timestamp"])), output_dir)
-                written += 1
-        return written
-
-    from .feeder import BatchFeeder, ResultDrain
-    dev = eng.device
-
     def build(frames, upload):
-        b = FrameBatch.from_frames(frames, res_name, device=dev, upload=upload)
-        return (frames, b), [b.offsets, b.pose0, b.pose1, b.pc0, b.lidar_dt, b.flow]
-    made = set()
-    made_lock = __import__("threading").Lock()
-
-    def write_sweep(key, arr):                  # (a writer thread; arr is a view of the drain's pinned buffer, gone when this returns)
-        scene_dir = Path(output_dir) / key[0]
-        if key[0] not in made:
-            with made_lock:
-                scene_dir.mkdir(exist_ok=True, parents=True)
-                made.add(key[0])
-        with open(scene_dir / f"{key[1]}.feather", "wb") as fh:
-            fh.write(memoryview(_frame_table(arr)))
-    # one Feather file per sweep, independent of each other: four writer threads (the column gather and the file write release the
-    # GIL), fed views of the pinned drain buffers -- a single writer thread was the bound of this loop (1.25 k sweeps/s in round 4)
-    drain = ResultDrain(write_sweep, device=dev, threads=4, copy=False)
-    feed = BatchFeeder(batches(), build, device=dev)
-    try:
+        staged = {} if upload is None else {"device": eng.device, "upload": upload}
+        return frames, FrameBatch.from_frames(frames, res_name, **staged)
+    drain = None
+    if overlap:
+        # one Feather file per sweep, independent of each other: four writer threads (the column gather and the file write release the
+        # GIL), fed views of the pinned drain buffers -- a single writer thread was the bound of this loop (1.25 k sweeps/s in round 4)
+        from .feeder import ResultDrain
+        files = FeatherSink(output_dir)     # (a writer thread's ``arr`` is a view of the drain's pinned buffer, gone when the sink returns)
+        drain = ResultDrain(lambda key, arr: files.write(key[0], key[1], [memoryview(_frame_table(arr))]), device=eng.device, threads=4, copy=False)
+    written = 0
+    feed = fed(batches(), build, device=eng.device if overlap else None, overlap=overlap)
+    with draining(feed, drain):
         for frames, batch in feed:
             cd = eng.run(batch, sensor_dt=sensor_dt)["comp_dis"]
+            if drain is None:
+                cd = cd.cpu().numpy()           # one D2H copy per batch
             o = batch.offsets_host
             for k, f in enumerate(frames):
-                drain.put((f["scene_id"], str(f["timestamp"])), cd[int(o[k]):int(o[k + 1])])
+                key, part = (f["scene_id"], str(f["timestamp"])), cd[int(o[k]):int(o[k + 1])]
+                if drain is None:
+                    write_output_file(part, key, output_dir)
+                else:
+                    drain.put(key, part)
                 written += 1
-    except BaseException:
-        feed.close()
-        try:
-            drain.close()                       # the sweeps already computed still reach the disk, as in the serial loop
-        except BaseException:
-            pass
-        raise
-    drain.close()
     return written
 
 
@@ -187,14 +156,12 @@ def main(data_dir: str = "/home/kin/data/av2/h5py/sensor/himo/demo", res_name: s
     data_dir = Path(data_dir)
     output_dir = data_dir / "results"
     output_dir.mkdir(exist_ok=True, parents=True)
+
+    def loop():
+        dataset = open_dataset(data_dir, vis_name=res_name, eval=True, allow_dropped_eval=allow_dropped_eval)
+        run_dataset(dataset, res_name, output_dir, batch_frames=batch_frames)
     with distenv.process_group() as (rank, world):
-        err = None
-        try:
-            dataset = open_dataset(data_dir, vis_name=res_name, eval=True, allow_dropped_eval=allow_dropped_eval)
-            run_dataset(dataset, res_name, output_dir, batch_frames=batch_frames)
-        except Exception as e:                                   # (an interrupt leaves at once; the launcher ends the job)
-            err = e
-        distenv.rendezvous(err, "its Feather files, but no submit zip was written")   # every rank's files are on disk -- or somebody failed
+        distenv.run_shard(loop, "its Feather files, but no submit zip was written")   # every rank's files are on disk -- or somebody failed
         if rank == 0:
             zip_res(output_dir, output_file=f"{output_dir}/{res_name}-submit.zip")
         if world > 1:
@@ -214,6 +181,5 @@ def _cli(argv=None):
 
 
 if __name__ == "__main__":
-    start_time = time.time()
-    _cli()
-    print(f"Time used: {time.time() - start_time:.2f} s")
+    from .sweeps import timed
+    timed(_cli)

@@ -16,7 +16,6 @@ initialised the sweeps are sharded across ranks (frame i -> rank i % world), eve
 """
 from __future__ import annotations
 
-import time
 from pathlib import Path
 from typing import Tuple
 from zipfile import ZipFile
@@ -24,7 +23,7 @@ from zipfile import ZipFile
 import numpy as np
 
 from . import feather
-from .save_zip import _dist, zip_res  # noqa: F401  (zip_res: the reference's public name, same function as save_zip's)
+from .save_zip import zip_res  # noqa: F401  (zip_res: the reference's public name, same function as save_zip's)
 
 COMP_DIS_COLUMNS = ("comp_dis_x_m", "comp_dis_y_m", "comp_dis_z_m")
 PC0_COLUMNS = ("pc0_x", "pc0_y", "pc0_z")
@@ -94,15 +93,14 @@ def run_dataset(dataset, data_name: str, output_dir: Path, batch_frames: int = 3
     which decodes the columns and goes through ``write_output_file``.  A batch holds sweeps of one schema: the reference decides
     per sweep whether a label column exists (save_zip_gt.py:172-173), so sweeps that lack one form a batch of their own."""
     from .compdis import CompDisEngine, FrameBatch
+    from .sweeps import FeatherSink, draining, fed, sharded_batches
 
     overlap = OVERLAP if overlap is None else overlap
-    rank, world, _ = _dist()
     eng = CompDisEngine(max_frames=batch_frames)
-    mine = list(range(rank, len(dataset), world))
 
     def batches():
-        for lo in range(0, len(mine), batch_frames):
-            frames = [dataset[i] for i in mine[lo:lo + batch_frames]]
+        for keys in sharded_batches(dataset, batch_frames):
+            frames = [dataset[i] for i in keys]
             for f in frames:
                 if len(f["lidar_dt"]) == 0:
                     raise ValueError("max() arg is an empty sequence")       # save_zip_gt.py:164
@@ -113,61 +111,34 @@ def run_dataset(dataset, data_name: str, output_dir: Path, batch_frames: int = 3
             for kind in kinds:
                 yield [f for f in frames if _schema_key(f) == kind]
 
-    written = 0
-    if not overlap:
-        for frames in batches():
-            batch = FrameBatch.from_frames(frames, "flow", with_masks=True, with_labels=True, host_ego=True)
-            body, at, (names, dtypes) = eng.run_gt(batch, data_name, sensor_dt=sensor_dt)
-            host = body.cpu().numpy()                                         # one D2H copy per batch
-            o = batch.offsets_host
-            for k, f in enumerate(frames):
-                c = body_columns(host[int(at[k]):int(at[k + 1])], names, dtypes, int(o[k + 1] - o[k]))
-                write_output_file(np.stack([c[n] for n in COMP_DIS_COLUMNS], axis=1), (f["scene_id"], str(f["timestamp"])), output_dir,
-                                  c["eval_mask"], flow_category_indices=c.get("flow_category_indices"),
-                                  flow_instance_id=c.get("flow_instance_id"), gt_flow_norm=c["gt_flow_norm"],
-                                  pc0=np.stack([c[n] for n in PC0_COLUMNS], axis=1))
-                written += 1
-        return written
-
-    import threading
-    from .feeder import BatchFeeder, ResultDrain
-    dev = eng.device
-
     def build(frames, upload):
-        b = FrameBatch.from_frames(frames, "flow", device=dev, with_masks=True, upload=upload, with_labels=True, host_ego=True)
-        return (frames, b), []                  # (the feeder keeps the staged blocks alive itself)
-    made = set()
-    made_lock = threading.Lock()
-
-    def write_sweep(key, body):                 # (a writer thread; body is a view of the drain's pinned buffer, gone when this returns)
-        scene, stamp, head, tail = key
-        scene_dir = Path(output_dir) / scene
-        if scene not in made:
-            with made_lock:
-                scene_dir.mkdir(exist_ok=True, parents=True)
-                made.add(scene)
-        with open(scene_dir / f"{stamp}.feather", "wb") as fh:
-            fh.write(head)
-            fh.write(memoryview(body))
-            fh.write(tail)
-    drain = ResultDrain(write_sweep, device=dev, threads=4, copy=False)
-    feed = BatchFeeder(batches(), build, device=dev)
-    try:
+        staged = {} if upload is None else {"device": eng.device, "upload": upload}
+        return frames, FrameBatch.from_frames(frames, "flow", with_masks=True, with_labels=True, host_ego=True, **staged)
+    drain = None
+    if overlap:
+        from .feeder import ResultDrain
+        files = FeatherSink(output_dir)     # (a writer thread's ``body`` is a view of the drain's pinned buffer, gone when the sink returns)
+        drain = ResultDrain(lambda key, body: files.write(key[0], key[1], [key[2], memoryview(body), key[3]]), device=eng.device, threads=4,
+                            copy=False)
+    written = 0
+    feed = fed(batches(), build, device=eng.device if overlap else None, overlap=overlap)
+    with draining(feed, drain):
         for frames, batch in feed:
             body, at, (names, dtypes) = eng.run_gt(batch, data_name, sensor_dt=sensor_dt)
+            if drain is None:
+                body = body.cpu().numpy()       # one D2H copy per batch
             o = batch.offsets_host
             for k, f in enumerate(frames):
-                head, tail, _, _ = feather.framing(names, dtypes, int(o[k + 1] - o[k]))
-                drain.put((f["scene_id"], str(f["timestamp"]), head, tail), body[int(at[k]):int(at[k + 1])])
+                key, rows, part = (f["scene_id"], str(f["timestamp"])), int(o[k + 1] - o[k]), body[int(at[k]):int(at[k + 1])]
+                if drain is None:               # the serial loop decodes the columns and goes through the host encoder
+                    c = body_columns(part, names, dtypes, rows)
+                    write_output_file(np.stack([c[n] for n in COMP_DIS_COLUMNS], axis=1), key, output_dir, c["eval_mask"],
+                                      flow_category_indices=c.get("flow_category_indices"), flow_instance_id=c.get("flow_instance_id"),
+                                      gt_flow_norm=c["gt_flow_norm"], pc0=np.stack([c[n] for n in PC0_COLUMNS], axis=1))
+                else:
+                    head, tail, _, _ = feather.framing(names, dtypes, rows)
+                    drain.put(key + (head, tail), part)
                 written += 1
-    except BaseException:
-        feed.close()
-        try:
-            drain.close()                       # the sweeps already computed still reach the disk, as in the serial loop
-        except BaseException:
-            pass
-        raise
-    drain.close()
     return written
 
 
@@ -183,15 +154,13 @@ def main(data_dir: str = "/home/kin/data/av2/h5py/sensor/himo/demo", output_dir:
     data_dir, output_dir = Path(data_dir), Path(output_dir)
     output_dir.mkdir(exist_ok=True, parents=True)
     data_name, _ = check_valid(str(data_dir), res_name, None)
+
+    def loop():
+        # vis_name="": the estimate named by res_name is not read (the reference computes an est_flow from it and drops it)
+        dataset = open_dataset(data_dir, vis_name="", eval=True, allow_dropped_eval=allow_dropped_eval, fields=EVAL_FIELDS)
+        run_dataset(dataset, data_name, output_dir, batch_frames=batch_frames)
     with distenv.process_group() as (rank, world):
-        err = None
-        try:
-            # vis_name="": the estimate named by res_name is not read (the reference computes an est_flow from it and drops it)
-            dataset = open_dataset(data_dir, vis_name="", eval=True, allow_dropped_eval=allow_dropped_eval, fields=EVAL_FIELDS)
-            run_dataset(dataset, data_name, output_dir, batch_frames=batch_frames)
-        except Exception as e:                                   # (an interrupt leaves at once; the launcher ends the job)
-            err = e
-        distenv.rendezvous(err, "its Feather files, but no ground-truth zip was written")
+        distenv.run_shard(loop, "its Feather files, but no ground-truth zip was written")
         if rank == 0:
             zip_res(output_dir, output_file=f"{output_dir}/{res_name}-submit.zip")
         if world > 1:
@@ -212,6 +181,5 @@ def _cli(argv=None):
 
 
 if __name__ == "__main__":
-    start_time = time.time()
-    _cli()
-    print(f"Time used: {time.time() - start_time:.2f} s")
+    from .sweeps import timed
+    timed(_cli)

@@ -24,6 +24,7 @@ from . import feather
 
 from .eval import (BUCKETED_METACATAGORIES, CATEGORY_TO_INDEX, EVAL_GROUPS, MODE_SCORE, RANGES,  # noqa: F401
                    InstanceEvaluator, chamfer_distance, range_name_of)
+from .sweeps import sweep_offsets
 
 
 def read_data_file(data_path: str, sweep_uuid: tuple) -> tuple:
@@ -110,8 +111,7 @@ class ScoreMetrics:
 
     def _run_group(self, sweeps, have_norm: bool, have_pc0: bool, sensor_dt: float):
         ev, dev = self._evaluator, self._evaluator.device
-        counts = [len(s[0]) for s in sweeps]
-        offsets = torch.from_numpy(np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)).to(dev)
+        offsets = torch.from_numpy(sweep_offsets(len(s[0]) for s in sweeps)).to(dev)
         cat = lambda k, dt: torch.from_numpy(np.ascontiguousarray(np.concatenate([np.asarray(s[k]).astype(dt) for s in sweeps]))).to(dev)
         return ev.run(len(sweeps), offsets, cat(6, np.float32) if have_pc0 else None, cat(0, np.float32), cat(1, np.float32),
                       cat(5, np.float32) if have_norm else None, cat(3, np.uint8), cat(4, np.int64), cat(2, np.uint8),

@@ -28,8 +28,7 @@ dev = torch.device("cuda:0")
 
 
 def build(fr, upload):
-    b = FrameBatch.from_frames(fr, "seflowpp_best", device=dev, upload=upload)
-    return (fr, b), [b.offsets, b.pose0, b.pose1, b.pc0, b.lidar_dt, b.flow]
+    return fr, FrameBatch.from_frames(fr, "seflowpp_best", device=dev, upload=upload)
 
 
 for rep in range(2):

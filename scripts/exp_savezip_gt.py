@@ -49,7 +49,7 @@ if STEP in ("serial", "overlapped"):
 
 if STEP == "feeder":
     def build(fr, upload):
-        return (fr, FrameBatch.from_frames(fr, "flow", device=dev, with_masks=True, upload=upload, with_labels=True, host_ego=True)), []
+        return fr, FrameBatch.from_frames(fr, "flow", device=dev, with_masks=True, upload=upload, with_labels=True, host_ego=True)
     for rep in range(2):
         t0 = time.perf_counter()
         n = 0
