@@ -56,6 +56,9 @@ SIGNATURES = {
     "himo_flow_metrics_batch": (c_int, [c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                                         ctypes.POINTER(c_void_p), c_int, c_void_p, c_void_p, c_void_p, ctypes.POINTER(ctypes.c_uint8),
                                         c_double, c_uint, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "himo_flow_metrics_batch_ex": (c_int, [c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                           ctypes.POINTER(c_void_p), c_int, c_int, c_void_p, c_void_p, c_void_p, ctypes.POINTER(ctypes.c_uint8),
+                                           c_double, c_uint, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "himo_box_label_batch": (c_int, [c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "himo_ground_seg_workspace_bytes": (c_size_t, [c_int, c_void_p]),
@@ -91,6 +94,7 @@ FLAG_F32_CHAIN = 0x1
 FLAG_RAW = 0x2
 FLAG_SCANIA = 0x4
 FLAG_POSE_IS_EGO = 0x8
+FLAG_EST_RESIDUAL = 0x10
 GT_HAS_CATEGORY, GT_HAS_INSTANCE, GT_MAX_COLUMNS = 0x1, 0x2, 10
 
 OK, ERR_INVALID_ARGUMENT, ERR_EMPTY_FRAME, ERR_WORKSPACE, ERR_SINGULAR_POSE, ERR_HIP, ERR_UNSUPPORTED = range(7)

@@ -5,7 +5,8 @@ The reference's ``.ckpt`` is a PyTorch-Lightning pickle of the absent ``OpenScen
 be known from this tree (PARITY UNPINNED).  This build's own container is a plain ``.npz``:
     every array of ``spec.param_shapes()`` under its own name (float32),
     optionally ``__adam_m__`` / ``__adam_v__`` (the trainer's flat moment buffers), ``__step__``, ``__epoch__``,
-    ``__val__`` (the validation figure ``save_top`` ranks by).
+    ``__val__`` (the validation figure ``save_top`` ranks by), ``__val_metric__`` (what that figure is when it is not the loss:
+    ``fit(val_metric=...)``; absent = the loss).
 ``from_state_dict`` is the adapter hook for the day the reference's weights are readable: it converts torch's layouts
 (conv ``[cout, cin, kh, kw]``, linear ``[out, in]``) to this build's (``[kh, kw, cin, cout]``, ``[in, out]``) through a
 caller-supplied name map and checks every shape against ``spec.param_shapes()``.
@@ -19,7 +20,13 @@ import numpy as np
 
 from . import spec
 
-_EXTRA = ("__adam_m__", "__adam_v__", "__step__", "__epoch__", "__val__")
+_EXTRA = ("__adam_m__", "__adam_v__", "__step__", "__epoch__", "__val__", "__val_metric__")
+
+
+def val_metric_of(path) -> str:
+    """the name of the figure a checkpoint's ``__val__`` holds: its ``val_metric`` extra, "loss" when it has none"""
+    with np.load(path) as z:
+        return str(z["__val_metric__"]) if "__val_metric__" in z.files else "loss"
 
 
 def check_params(params: dict) -> dict:

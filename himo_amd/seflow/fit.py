@@ -22,6 +22,14 @@ labelled frame carries ("DeFlow loss, v1", himo_amd/deflow_loss.py; parity unpin
 labels are generated or read, validation uses the same loss, and the samples are built on the launch thread inside the step loop
 (``make_supervised_sample``, the shape of ``num_workers=0``) -- ``feeder.TrainFeeder`` does not prefetch supervised samples (timing
 unmeasured).
+
+``val_metric="three_way"`` / ``"mean_dynamic"`` ranks the checkpoints by FLOW ERROR instead of the validation loss (which for the
+self-supervised loss is only a proxy for it): after a validated epoch every validation triplet of the rank goes through ONE
+``forward(training=False)`` pass and ONE ``eval_flow.flow_metrics`` launch in residual mode, straight on the head's residual rows
+and the sample's device arrays ("flow metrics, v1" with rules 3b and 9, himo_amd/eval_flow.py; parity unpinned) -- no labels are
+read or generated, nothing waits for the device per sample -- and ``FlowMetrics.gather()`` adds the ranks' integers.  The
+validation frames must carry ``flow``, ``flow_category_indices`` and ``gm0`` (Scania: ``flow_is_valid`` too).  ``val_every=k``
+(the launcher's ``val_every=3``, ssl-train-av2.sh:32; default 1) validates epoch e iff ``(e + 1) % k == 0`` or e is the last.
 """
 from __future__ import annotations
 
@@ -162,12 +170,72 @@ def make_supervised_sample(dataset, trip, device):
             np.asarray(f0["pose1"], np.float64), up(f0["flow"]), valid)
 
 
+VAL_METRICS = ("loss", "three_way", "mean_dynamic")
+
+# what a validation pass by flow error reads (``flow_is_valid`` where the file has it; Scania requires it)
+VAL_FLOW_FIELDS = ("pc0", "pose0", "pose1", "pc1", "flow", "flow_category_indices", "gm0", "flow_is_valid")
+
+
+def validates(epoch: int, epochs: int, val_every: int = 1) -> bool:
+    """whether the 0-based ``epoch`` of a run of ``epochs`` validates: every ``val_every``-th one and the last"""
+    if val_every < 1:
+        raise ValueError(f"val_every={val_every}: at least 1")
+    return (epoch + 1) % val_every == 0 or epoch == epochs - 1
+
+
+def validation_epochs(epochs: int, val_every: int = 1, start_epoch: int = 0) -> list:
+    """the 0-based epochs of a run that validate (and are offered to ``TopK``)"""
+    return [e for e in range(start_epoch, epochs) if validates(e, epochs, val_every)]
+
+
+def make_validation_sample(dataset, trip, device, scania: bool = False):
+    """((pch1, pc0, pc1, pose_h1, pose0, pose1), gt_flow, category, ground, valid_or_None) on ``device`` for one triplet: the
+    forward pass's sample and the ground-truth arrays "flow metrics, v1" reads (float32 [n0][3], uint8 [n0] each).  A frame
+    without one of them is a KeyError naming it."""
+    ih, i0, i1 = trip
+    f0 = dataset[i0]
+    fh = _frame(dataset, ih, ("pc0", "pose0")) if ih != i0 else f0
+    for key in ("flow", "flow_category_indices", "gm0") + (("flow_is_valid",) if scania else ()):
+        if f0.get(key) is None:
+            raise KeyError(f"{key}: validation by flow error reads it, and this validation frame does not hold it")
+    pc1 = f0["pc1"] if i1 is None else dataset[i1]["pc0"]
+    n0 = np.shape(f0["pc0"])[0]
+    if np.shape(f0["flow"]) != (n0, 3):
+        raise ValueError(f"flow has shape {np.shape(f0['flow'])} for {n0} points")
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(device)
+
+    def byte(key):
+        a = np.ascontiguousarray(f0[key]).reshape(-1)
+        if a.shape[0] != n0:
+            raise ValueError(f"{key} has {a.shape[0]} entries for {n0} points")
+        return torch.from_numpy(a.astype(np.uint8)).to(device)
+    valid = byte("flow_is_valid") if f0.get("flow_is_valid") is not None else None
+    fwd = (up(fh["pc0"]), up(f0["pc0"]), up(pc1), np.asarray(fh["pose0"], np.float64), np.asarray(f0["pose0"], np.float64),
+           np.asarray(f0["pose1"], np.float64))
+    return fwd, up(f0["flow"]), byte("flow_category_indices"), byte("gm0"), valid
+
+
+def validate_flow(tr, val_dataset, val_trips, rank: int = 0, world: int = 1, data_name: str = "av2") -> dict:
+    """One validation pass by flow error: triplet j of ``val_trips`` on rank j % world (keyed by j), one inference pass and one
+    residual-mode ``flow_metrics`` launch each, then ``gather()`` (EVERY rank calls this).  Returns ``results()["val"]``."""
+    from ..eval_flow import FlowBatch, FlowMetrics
+    metrics = FlowMetrics(["val"], data_name, device=tr.device, accuracy=True, residual=True)
+    for j in range(rank, len(val_trips), world):
+        fwd, gt, category, ground, valid = make_validation_sample(val_dataset, val_trips[j], tr.device, scania=data_name == "scania")
+        tr.forward(*fwd, training=False)
+        pc0, res = tr.flow_rows(0)
+        metrics.add_batch(FlowBatch.from_device(pc0, gt, [res], category, ground, fwd[4], fwd[5], valid=valid, keys=[j]))
+    metrics.gather()
+    return metrics.results()["val"]
+
+
 def fit(dataset, params: dict | None = None, out_dir=None, epochs: int = 12, batch_size: int = 8, lr: float = 6e-5,
         step_size: int = 3, gamma: float = 0.5, save_top: int = 3, val_dataset=None, resume=None, precision: str = "mixed",
         max_points: int = 140_000, device=None, seed: int = 0, max_steps: int | None = None, log=print,
         trainer: SeFlowTrainer | None = None, batchnorm: str = "batch", ssl_label: str = "seflow_auto",
         num_workers: int = 1, prefetch: int = 2, label_lanes: int = 1,
-        cache_labels: bool = True, loss_fn: str = "seflowppLoss") -> dict:
+        cache_labels: bool = True, loss_fn: str = "seflowppLoss", val_metric: str = "loss", val_every: int = 1,
+        val_data_name: str = "av2") -> dict:
     """Train for ``epochs`` passes over ``dataset``; returns {"trainer", "history", "best"}.
 
     ``num_workers`` > 0 (default; the launcher's ``num_workers=16``, ssl-train-av2.sh:32): the samples of an epoch come from
@@ -178,6 +246,14 @@ def fit(dataset, params: dict | None = None, out_dir=None, epochs: int = 12, bat
     ``loss_fn``: "seflowppLoss" (default) or "deflowLoss" = supervised on the frames' ``flow`` (module docstring): ``ssl_label``, the
     feeder options and the label cache are not used, every sample is built inside the step loop (``make_supervised_sample``).
 
+    ``val_metric``: what ``save_top`` ranks by -- "loss" (default: the validation loss, or the mean training loss without a validation
+    set) or a flow error of the validation set, "three_way" / "mean_dynamic" (module docstring; ``val_data_name`` "av2" | "scania"
+    selects the evaluation mask; works with either ``loss_fn``).  The history entries of such a run gain "val_flow" (the whole results
+    dict, accuracy included), "val_figure" and "val_seconds"; a non-finite figure is logged and never kept.  ``val_every``: with a
+    validation set only every k-th epoch and the last validate, and only those are offered to ``save_top``; ignored without one.
+    Checkpoints written under another metric than the loss carry ``val_metric`` in their extras, and ``resume`` under a different
+    metric than the checkpoint's is refused (``TopK`` would rank metres against loss units).
+
     Ranks (torch.distributed, initialised by the caller / ``distenv.process_group``): step s of an epoch takes the global
     samples [s * batch_size, (s + 1) * batch_size) of that epoch's seeded shuffle; rank r takes every world-th of them.
     ``max_steps`` bounds the optimiser steps of the whole run (tests)."""
@@ -185,6 +261,21 @@ def fit(dataset, params: dict | None = None, out_dir=None, epochs: int = 12, bat
     rank, world = (dist.get_rank(), dist.get_world_size()) if dist.is_available() and dist.is_initialized() else (0, 1)
     if loss_fn not in LOSS_FNS:
         raise ValueError(f"loss_fn={loss_fn!r}: one of {LOSS_FNS}")
+    if val_metric not in VAL_METRICS:
+        raise ValueError(f"val_metric={val_metric!r}: one of {VAL_METRICS}")
+    if val_every < 1:
+        raise ValueError(f"val_every={val_every}: at least 1")
+    by_flow = val_metric != "loss"
+    if by_flow and val_dataset is None:
+        raise ValueError(f"val_metric={val_metric!r} needs a validation set (val_dataset) whose frames carry flow, flow_category_indices and gm0")
+    if by_flow and val_data_name not in ("av2", "scania"):
+        raise ValueError(f"val_data_name {val_data_name!r}: 'av2' or 'scania'")
+    if resume is not None:
+        from .checkpoint import val_metric_of
+        had = val_metric_of(resume)
+        if had != val_metric:
+            raise ValueError(f"the checkpoint {resume} was ranked by val_metric={had!r}; resuming under val_metric={val_metric!r} would rank "
+                             f"its figures against another unit")
     supervised = loss_fn == "deflowLoss"
     if supervised and log is not None and rank == 0:
         log(f"loss_fn=deflowLoss: supervised on the frames' ground-truth flow; ssl_label={ssl_label!r} is ignored")
@@ -206,6 +297,9 @@ def fit(dataset, params: dict | None = None, out_dir=None, epochs: int = 12, bat
     if not trips:
         raise ValueError("the dataset has no frame with a successor in its scene")
     val_trips = triplets(val_dataset) if val_dataset is not None else []
+    if by_flow and not val_trips:
+        raise ValueError("the validation set has no frame with a successor in its scene")
+    ckpt_extra = {"val_metric": val_metric} if by_flow else {}
     steps_per_epoch = math.ceil(len(trips) / batch_size)
     history, steps_done = [], 0
     feed_stats = []
@@ -260,7 +354,12 @@ def fit(dataset, params: dict | None = None, out_dir=None, epochs: int = 12, bat
         t_epoch = time.perf_counter() - t_epoch
         tr.sync_running_stats()                              # validation and the checkpoint use rank 0's running statistics
         val_loss = None
-        if val_trips:
+        validated = bool(val_trips) and validates(epoch, epochs, val_every)
+        if validated and by_flow:
+            t_val = time.perf_counter()
+            val_flow = validate_flow(tr, val_dataset, val_trips, rank, world, val_data_name)      # (gather() waits for the pass)
+            t_val = time.perf_counter() - t_val
+        elif validated:
             vals = [tr.loss_only(*smp) for grp in samples_of(val_dataset, [val_trips[rank::world]]) for smp in grp]
             v = torch.stack(vals).sum() if vals else torch.zeros((), dtype=torch.float64, device=dev)
             cnt = torch.tensor([float(len(vals))], dtype=torch.float64, device=dev)
@@ -270,12 +369,24 @@ def fit(dataset, params: dict | None = None, out_dir=None, epochs: int = 12, bat
             val_loss = float((tot[0] / tot[1].clamp(min=1.0)).item())
         entry = {"epoch": epoch, "lr": lr_e, "train_loss": train_loss, "val_loss": val_loss, "steps": len(losses),
                  "samples": sum(len(g) for g in mine), "feeder": train_feed, "train_seconds": t_epoch}      # (feeder: host seconds per stage on its own threads)
+        line = f"  val loss {val_loss:.6f}" if val_loss is not None else ""
+        if validated and by_flow:
+            figure = float(val_flow[val_metric])
+            entry.update({"val_flow": val_flow, "val_figure": figure, "val_seconds": t_val})
+            line = (f"  val three-way {val_flow['three_way']:.6f}  FD {val_flow['FD']:.6f}  FS {val_flow['FS']:.6f}  BS {val_flow['BS']:.6f}"
+                    f"  mean_dynamic {val_flow['mean_dynamic']:.6f}  acc_strict ALL {val_flow['acc_strict']['ALL']:.6f}  ({t_val:.2f} s)")
+            if not math.isfinite(figure):
+                line += f"  [{val_metric} is not finite: nothing of its kind in the validation set; this epoch is not kept]"
         history.append(entry)
         if log is not None and rank == 0:
-            log(f"epoch {epoch}: lr {lr_e:.3g}  train loss {train_loss:.6f}" + (f"  val loss {val_loss:.6f}" if val_loss is not None else ""))
-        if top is not None and losses:
-            figure = val_loss if val_loss is not None else train_loss
-            top.offer(figure, epoch, tr.export_params(), adam_m=tr.flat_m.cpu().numpy(), adam_v=tr.flat_v.cpu().numpy(), step=tr.step_count)
+            log(f"epoch {epoch}: lr {lr_e:.3g}  train loss {train_loss:.6f}" + line)
+        if top is not None and losses and (validated or not val_trips):
+            if by_flow:
+                figure = entry["val_figure"]
+            else:
+                figure = val_loss if val_loss is not None else train_loss
+            top.offer(figure, epoch, tr.export_params(), adam_m=tr.flat_m.cpu().numpy(), adam_v=tr.flat_v.cpu().numpy(), step=tr.step_count,
+                      **ckpt_extra)
         if max_steps is not None and steps_done >= max_steps:
             break
     return {"trainer": tr, "history": history, "best": top.best() if top is not None else None}
@@ -304,24 +415,40 @@ def _parser():
                          "warm .h5 files and more of them only contend with the launch thread for the interpreter lock); 0: inside the step loop")
     ap.add_argument("--precision", default="mixed", choices=["mixed", "bf16x3", "f32"])
     ap.add_argument("--max_points", type=int, default=140_000, help="points per sweep the trainer's buffers are sized for")
+    ap.add_argument("--val_metric", default="loss", choices=list(VAL_METRICS),
+                    help="what --save_top_model ranks by: the validation loss, or a flow error of the validation set (flow metrics, v1; needs "
+                         "--val_path scenes with flow, flow_category_indices and gm0)")
+    ap.add_argument("--val_every", type=int, default=1, help="validate every N-th epoch and the last (the launcher's val_every=3)")
+    ap.add_argument("--data_name", default="auto", choices=["auto", "av2", "scania"],
+                    help="the evaluation mask of a flow --val_metric; auto: sniffed from --val_path")
     return ap
 
 
 def main(argv=None):
-    """``python -m himo_amd.seflow.fit --dataset_path <dir> [--checkpoint init.npz] [--out_dir ckpt] [--loss_fn deflowLoss]``; under
-    torchrun one rank per GPU (RCCL)."""
+    """``python -m himo_amd.seflow.fit --dataset_path <dir> [--checkpoint init.npz] [--out_dir ckpt] [--loss_fn deflowLoss]
+    [--val_path <dir> --val_metric three_way --val_every 3]``; under torchrun one rank per GPU (RCCL)."""
     from .. import distenv
     from ..dataset import open_dataset
     from .checkpoint import load_params
     a = _parser().parse_args(argv)
+    by_flow = a.val_metric != "loss"
+    if by_flow and not a.val_path:
+        raise ValueError(f"--val_metric {a.val_metric} needs --val_path")
+    data_name = a.data_name
+    if data_name == "auto":
+        from ..eval_flow import data_name_of
+        data_name = data_name_of(a.val_path) if by_flow else "av2"
     with distenv.process_group():
         opts = {"fields": loss_fields(a.loss_fn, a.ssl_label), "zero_copy": True}      # (h5 scene files; the npz container ignores them)
         ds = open_dataset(Path(a.dataset_path), **opts)
+        if by_flow:                                          # the union of what the loss and the metric read
+            opts = dict(opts, fields=opts["fields"] + tuple(k for k in VAL_FLOW_FIELDS if k not in opts["fields"]))
         val = open_dataset(Path(a.val_path), **opts) if a.val_path else None
         params = load_params(a.checkpoint) if a.checkpoint else None
         return fit(ds, params, out_dir=a.out_dir, epochs=a.epochs, batch_size=a.batch_size, lr=a.lr, save_top=a.save_top_model,
                    val_dataset=val, resume=a.resume or None, batchnorm=a.batchnorm, ssl_label=a.ssl_label, num_workers=a.num_workers,
-                   precision=a.precision, loss_fn=a.loss_fn, max_points=a.max_points)
+                   precision=a.precision, loss_fn=a.loss_fn, max_points=a.max_points, val_metric=a.val_metric, val_every=a.val_every,
+                   val_data_name=data_name)
 
 
 if __name__ == "__main__":

@@ -1454,6 +1454,14 @@ class SeFlowTrainer:
         self.backward_batch(dres_list, exchange=exchange)
         return terms_all, totals
 
+    def flow_rows(self, b: int = 0):
+        """(pc0, res) of sample slot b of the pass that has just run, both on the device: the raw float32 pc0 rows as the pass took
+        them and the head's residual rows, an [n0, 3] view of its pitch-4 ``RES`` buffer (zeros where the pillar stage dropped the
+        point: the fused head and ``himo_mask_rows`` both write them) -- what ``eval_flow.flow_metrics(residual=True)`` reads in place.
+        Valid until the next pass."""
+        n0 = self.n_pts_b[b][1]
+        return self._fwd_jobs[b][1][1], self.heads[b].RES[:n0, :3]
+
     def loss_only(self, pch1, pc0, pc1, pose_h1, pose0, pose1, label0, label1, n_labels: int | None = None):
         """forward + loss without a backward pass (validation): the total as a 0-d float64 device tensor.  ``loss="deflow"``: the two
         label arguments are ``gt_flow`` and ``valid`` (or None), as in that mode's sample tuples."""

@@ -277,6 +277,21 @@ int himo_flow_metrics_batch(int n_frames, int64_t total_points, const int64_t* d
                             const uint8_t* h_class_lut, double sensor_dt, unsigned flags,
                             int64_t* d_buckets, int64_t* d_threeway, int64_t* d_rejected,
                             void* d_workspace, void* stream);
+/* The same call with two additions to the rule (both PARITY UNPINNED: the package's own rule).  est_stride: floats per row of
+ * every estimate, >= 3 (rows of a wider buffer are read in place).  HIMO_FLAG_EST_RESIDUAL in flags: every non-NULL estimate is
+ * the ego-motion-free part of a result (a network's own output rows, before the pose flow is added): its error is
+ * (double)res - (gt - pose_flow); an all-zero residual is the "raw" result.  d_accuracy int64[R][4][3] = count, strict, relaxed
+ * of the groups ALL, FD, FS, BS over the counted, non-rejected points, ADDED to (strict: epe < 0.05 || epe < 0.05 |gt|;
+ * relaxed: 0.1 likewise; |gt| of the stored ground truth); NULL: the table is not computed.  est_stride < 3 is
+ * HIMO_ERR_INVALID_ARGUMENT and nothing is written.  himo_flow_metrics_batch is this call with est_stride 3, no flag, NULL. */
+#define HIMO_FLAG_EST_RESIDUAL 0x10u
+int himo_flow_metrics_batch_ex(int n_frames, int64_t total_points, const int64_t* d_offsets,
+                               const double* d_pose0, const double* d_pose1, const float* d_pc0, int pc_stride,
+                               const float* d_gt, const float* const* h_est, int n_results, int est_stride,
+                               const uint8_t* d_category, const uint8_t* d_ground, const uint8_t* d_valid,
+                               const uint8_t* h_class_lut, double sensor_dt, unsigned flags,
+                               int64_t* d_buckets, int64_t* d_threeway, int64_t* d_rejected, int64_t* d_accuracy,
+                               void* d_workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Scania extractor: the labelling of dataprocess/extract_sca.py:95-145 (compute_flow) for a packed batch of sweeps, one
