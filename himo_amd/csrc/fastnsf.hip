@@ -17,6 +17,7 @@
 //   adam_kernel            the optimiser step;
 //   chamfer_trunc_*        the objective and its gradient with respect to the moved points.
 #include "himo_common.h"
+#include "adam.h"
 #include <math.h>
 
 namespace himo {
@@ -577,12 +578,10 @@ __global__ __launch_bounds__(256) void adam_kernel(int64_t n, float* __restrict_
                                                    float eps, float bc1, float bc2_sqrt) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const float gi = g[i];
-    const float mi = b1 * m[i] + (1.f - b1) * gi;
-    const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+    float pi = p[i], mi = m[i], vi = v[i];
+    adam_update(pi, g[i], mi, vi, lr, b1, b2, eps, bc1, bc2_sqrt);      // csrc/adam.h: the bits of nsf_update_kernel's step
     m[i] = mi; v[i] = vi;
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    p[i] = p[i] - (lr / bc1) * (mi / denom);
+    p[i] = pi;
 }
 
 // truncated Chamfer: terms with squared distance above trunc2 are dropped (contribute neither loss nor gradient)

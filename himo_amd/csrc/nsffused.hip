@@ -29,6 +29,7 @@
 #include "bf16x3.h"
 #include "dtlookup.h"
 #include "lanetranspose.h"
+#include "adam.h"
 #include <math.h>
 
 namespace himo {
@@ -664,11 +665,9 @@ __global__ __launch_bounds__(256) void nsf_update_kernel(NsfUpdArgs a) {
     if (q != 0 || i >= a.total) return;
     const float gi = ((s_t[0][lane] + s_t[1][lane]) + (s_t[2][lane] + s_t[3][lane])) * inv;
     a.g[i] = gi;
-    const float mi = a.b1 * a.m[i] + (1.f - a.b1) * gi;          // Adam, torch.optim.Adam's update order (csrc/fastnsf.hip adam_kernel)
-    const float vi = a.b2 * a.v[i] + (1.f - a.b2) * gi * gi;
+    float pn = a.p[i], mi = a.m[i], vi = a.v[i];                // Adam: csrc/adam.h, the bits of csrc/fastnsf.hip adam_kernel
+    adam_update(pn, gi, mi, vi, a.lr, a.b1, a.b2, a.eps, a.bc1, a.bc2_sqrt);
     a.m[i] = mi; a.v[i] = vi;
-    const float denom = sqrtf(vi) / a.bc2_sqrt + a.eps;
-    const float pn = a.p[i] - (a.lr / a.bc1) * (mi / denom);
     a.p[i] = pn;
     // the packed copies of a hidden W (csrc/convbf.hip mlp_repack_kernel's layouts)
     for (int layer = 1; layer < a.n_layers - 1; ++layer) {
