@@ -85,6 +85,7 @@ extern "C" size_t himo_abi_sizeof(const char* struct_name) {
     if (!strcmp(struct_name, "himo_instance_record")) return sizeof(himo_instance_record);
     if (!strcmp(struct_name, "himo_ground_params")) return sizeof(himo_ground_params);
     if (!strcmp(struct_name, "himo_icp_params")) return sizeof(himo_icp_params);
+    if (!strcmp(struct_name, "himo_rigid_params")) return sizeof(himo_rigid_params);
     if (!strcmp(struct_name, "himo_raymap_params")) return sizeof(himo_raymap_params);
     if (!strcmp(struct_name, "himo_camera")) return sizeof(himo_camera);
     if (!strcmp(struct_name, "himo_shade")) return sizeof(himo_shade);

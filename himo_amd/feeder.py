@@ -482,6 +482,7 @@ class ReaderPool:
         # segmentation fault while "Garbage-collecting" under ``results.put``, forked from a process that had run many device tests)
         import gc
         gc.freeze()
+        gc.enable()                                               # (``_start`` forks with the collector off)
         tasks, results, maps = self._tasks[w], self._results, self._maps
         while True:
             t = tasks.get()
@@ -535,8 +536,18 @@ class ReaderPool:
                 stream.flush()
             except Exception:
                 pass
-        for p in self._procs:
-            p.start()
+        # the workers are born with the collector OFF and switch it on after ``gc.freeze()`` in ``_child``: multiprocessing's own
+        # bootstrap allocates before the target runs, and a collection started there finalises the parent's device-holding cycles too
+        # (observed: both readers died "Garbage-collecting" inside ``Process._bootstrap``, before ``_child`` had frozen anything)
+        import gc
+        collecting = gc.isenabled()
+        gc.disable()
+        try:
+            for p in self._procs:
+                p.start()
+        finally:
+            if collecting:
+                gc.enable()
         if self._on_slots is not None:
             self._on_slots(self.slots)
         self.stage_seconds["start"] += time.perf_counter() - t0

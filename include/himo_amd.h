@@ -502,6 +502,54 @@ int himo_icp_apply(int64_t n, const float* d_pts, int pitch, const int32_t* d_la
                    const int32_t* d_status, int mode, const float* d_base, int base_pitch, float* d_out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Cluster-rigid flow refinement (`python -m himo_amd.rigid_refine`, result key `<res_name>_rigid`): a stored flow is projected
+ * onto at most `models` rigid motions (yaw + 3-D translation) per cluster of the non-ground points of pc0; a motion that moves no
+ * claimed point by static_disp becomes the identity, i.e. the ego-motion flow.  The reference has no such stage: this one follows
+ * the build's own written rule, "cluster-rigid refinement, v1" (the module docstring of himo_amd/rigid_refine.py is normative):
+ * PARITY UNPINNED.
+ *
+ * One call runs rule 2 (every round of every cluster) and rules 2e / 3 (the flow of ALL n rows) on `stream`.
+ *   d_pc0 float[n][pitch] the sweep; d_flow float[n][3] the stored flow; d_moved float[n][3] the sweep in pc1's frame
+ *   (himo_rigid_transform); d_labels int32[n], 0 = no cluster (read for claimed rows only).
+ *   The clustered rows SORTED BY LABEL, as for himo_icp_*: d_rows int64[n_clustered] the sweep row of every sorted row; cluster k
+ *   (label k + 1) owns the sorted rows offsets[k] .. offsets[k + 1], given on the host (validation) and on the device; offsets that
+ *   do not end at n_clustered are refused.  Every row that is clustered takes part in the rule: the caller labels no ground row, no
+ *   row outside the range and no row whose flow is not finite.
+ * Outputs: d_status int32[C][models][4] = state, the inlier count of the round's last pass (its claim count when it claimed), the
+ * vote peak kx, ky; d_transform double[C][models][5] = c, s, tx, ty, tz (identity for a STATIC round and for a round not run);
+ * d_claim int8[n] = 0 or the round 1 .. models that claimed the row; d_out float[n][3] = float32(R a + t) - pc0 for a claimed row,
+ * the BYTES of d_flow for every other row.
+ * Refuse (HIMO_ERR_INVALID_ARGUMENT, nothing launched): a pitch other than 3 or 4, a negative count, n_clustered > n, clustered
+ * rows without clusters, offsets that are negative, decreasing, do not start at 0 or end at n_clustered, NULL or misaligned where
+ * data is required, parameters that are not finite and positive, half > 64, models > HIMO_RIGID_MAX_MODELS.  A short, NULL or
+ * misaligned (16 bytes) workspace: HIMO_ERR_WORKSPACE (himo_rigid_refine_workspace_bytes returns 0 for what it refuses).  n == 0:
+ * HIMO_OK, nothing launched; n_clusters == 0: d_out is the copy of d_flow.  The number of launches does not depend on the clusters;
+ * float64 sums take a fixed shape (no floating-point atomics): the same inputs give the same bytes on every run. */
+typedef struct himo_rigid_params {
+    float bin;             /* metres per vote bin */
+    int32_t half;          /* the vote covers |kx|, |ky| <= half */
+    float tol;             /* inlier radius, metres */
+    int32_t iters;         /* refit passes per round */
+    int32_t min_inliers;
+    float min_ratio;       /* a round is accepted iff inliers / cluster size >= min_ratio */
+    float static_disp;     /* a round whose claim moves by less than this everywhere is static */
+    int32_t models;        /* rounds per cluster */
+} himo_rigid_params;
+
+#define HIMO_RIGID_ACCEPTED 0
+#define HIMO_RIGID_FAILED 1
+#define HIMO_RIGID_REJECTED 2
+#define HIMO_RIGID_STATIC 3
+#define HIMO_RIGID_NOT_RUN 4
+#define HIMO_RIGID_MAX_MODELS 4
+
+size_t himo_rigid_refine_workspace_bytes(int64_t n_clustered, int n_clusters, int half, int models);
+int himo_rigid_refine(int64_t n, const float* d_pc0, int pitch, const float* d_flow, const float* d_moved, const int32_t* d_labels,
+                      int64_t n_clustered, const int64_t* d_rows, int n_clusters, const int64_t* h_offsets, const int64_t* d_offsets,
+                      const himo_rigid_params* params, int32_t* d_status, double* d_transform, int8_t* d_claim, float* d_out,
+                      void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * a10: scene-flow network (voxelise -> encoder/decoder -> per-point flow).
  * The reference's implementation is in the absent OpenSceneFlow submodule: these
  * entry points have NO reference lines to cite beyond the call sites README.md:50 (`save.py`) and the
