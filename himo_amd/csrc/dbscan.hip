@@ -8,17 +8,23 @@
 //   core      a point with >= min_pts points within eps;
 //   clusters  connected components of the core points under "within eps" -- unique, whatever the processing order;
 //   border    a non-core point with a core point within eps joins a cluster; DBSCAN leaves WHICH one to the processing order, this
-//             build fixes it: the cluster whose lowest-index member is lowest among the clusters of its core neighbours;
-//   noise     everything else: label 0.  Points flagged in `skip` (ground, static) take no part and get label 0.
-// Labels are 1 .. K in the order of each cluster's lowest point index: the result is a pure function of the input.
+//             build fixes it: the cluster whose lowest-index CORE point is lowest among the clusters of its core neighbours;
+//   noise     everything else: label 0.  Points flagged in `skip` (ground, static), rows with a NaN and rows with an infinite
+//             coordinate (no distance to them passes the test, their own included) take no part and get label 0.
+// "Within eps" is the float32 test (dx*dx + dy*dy) + dz*dz <= eps*eps, every operation rounded on its own (-ffp-contract=off in the
+// Makefile), as oracle/dbscan_oracle.py and oracle/dbscan_exact.py state it.
+// Labels are 1 .. K in the order of each cluster's lowest CORE index (the union-find runs on core points only: a border point of
+// lower index neither numbers its cluster nor decides where another border point goes): the result is a pure function of the input.
 //
-// Structure: the points are counting-sorted into BEV cells of edge >= eps (HBM-bound integer work: histogram with integer atomics,
-// one-block exclusive scan, scatter of xyz + original index as one 16-byte row), so a point's neighbours are in its 3 x 3 cells;
+// Structure: the points are counting-sorted into BEV cells (HBM-bound integer work: histogram with integer atomics, two-launch
+// exclusive scan, scatter of xyz + original index as one 16-byte row) whose edge is the caller's `cell` >= eps widened by 1/63, so
+// that a point's neighbours are in its 3 x 3 cells IN FLOAT32 TOO (the margin is derived at kDbMargin below);
 // core test = one pass over those cells with early exit; components = lock-free union-find on the original indices (hook the
 // larger root under the smaller with atomicMin: a component's root ends as its lowest index, deterministically; finds halve the
 // paths they walk; one wave per point shares the walk over its neighbours); labels = find.
 #include "himo_common.h"
 #include "unionfind.h"
+#include <float.h>
 #include <math.h>
 
 namespace himo {
@@ -28,7 +34,28 @@ struct DbGrid {
     int gw, gh;
 };
 
-__device__ inline int db_clamp(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
+// Why the 3 x 3 walk is enough.  A cell index is floor(u), u(v) = fl(fl(v - origin) * c) with the float c = inv_cell.  Against
+// T(v) = (v - origin) c in real arithmetic, |u - T| <= |T| (2^-23 + 2^-48) (two roundings), and u is monotone in v (every rounding is).
+// (Where the product underflows to a subnormal -- a huge cell -- its rounding is absolute instead, below 2^-149 of a cell: nothing
+// beside the margin.  The subtraction cannot underflow: a float difference that small is exact.)
+// With the caller's own cell, c = fl(1 / cell), two points exactly eps = cell apart can sit TWO cells apart (x0 = -52, cell = 0.5:
+// -20.000002 is in cell 63 and -19.500002 in cell 65, the difference rounds to 32.5), so the cells are made wider by a margin m:
+// c = fl((1 - m) / cell).  Two points p, q (p's coordinate the lower) that pass the distance test have fl(dx)^2 <= eps2 (1 + 2^-24)
+// -- a sum of rounded non-negative squares is no smaller than any of them, and eps2 = fl(eps * eps) is refused unless it is a normal
+// finite float, so the bound is relative -- hence dx <= eps (1 + 2^-22) and, as cell >= eps,
+//     T(q) - T(p) = dx c <= (1 - m)(1 + 2^-21).
+// If T(p) >= gw + 1 then u(p) >= gw - 1: p, and q above it, are both clamped into the last cell; if T(q) <= -1 both are in cell 0.
+// Otherwise -2 < T(p) <= T(q) < gw + 2, and
+//     u(q) - u(p) <= (1 - m)(1 + 2^-21) + 2 (gw + 2)(2^-23 + 2^-48) = 1 - 2^-7 + 2^-20 + ... < 1    for m = 2^-6, gw <= 2^15:
+// numbers less than 1 apart have floors at most 1 apart, and clamping cannot widen that.  The rounding term grows with the cell
+// COUNT along an axis, not with the coordinates, so a side of more than kDbMaxSide cells is refused (it would take m > 1 at 2^26).
+constexpr float kDbMargin = 1.0f / 64;
+constexpr int kDbMaxSide = 1 << 15;
+
+// the cell of coordinate v along one axis, clamped into [0, hi] while still a float (no out-of-range conversion; a NaN goes to cell 0)
+__device__ inline int db_cell(float v, float origin, float inv_cell, int hi) {
+    return (int)fminf(fmaxf(floorf((v - origin) * inv_cell), 0.f), (float)hi);
+}
 
 __global__ __launch_bounds__(256) void db_count_kernel(int n, const float* __restrict__ xyz, int pitch, const unsigned char* __restrict__ skip,
                                                        DbGrid g, int* __restrict__ count, int* __restrict__ cell_id) {
@@ -37,7 +64,7 @@ __global__ __launch_bounds__(256) void db_count_kernel(int n, const float* __res
     int c = -1;
     const float x = xyz[(int64_t)i * pitch], y = xyz[(int64_t)i * pitch + 1], z = xyz[(int64_t)i * pitch + 2];
     if (!(skip && skip[i]) && x == x && y == y && z == z) {                 // (NaN rows take no part)
-        const int cx = db_clamp((int)floorf((x - g.x0) * g.inv_cell), g.gw - 1), cy = db_clamp((int)floorf((y - g.y0) * g.inv_cell), g.gh - 1);
+        const int cx = db_cell(x, g.x0, g.inv_cell, g.gw - 1), cy = db_cell(y, g.y0, g.inv_cell, g.gh - 1);
         c = cy * g.gw + cx;
         atomicAdd(&count[c], 1);
     }
@@ -129,7 +156,7 @@ __global__ __launch_bounds__(256) void db_core_kernel(const float4* __restrict__
     const int lane = threadIdx.x & 63, n_waves = gridDim.x * 4;
     for (int s = blockIdx.x * 4 + (threadIdx.x >> 6); s < total; s += n_waves) {
         const float4 p = rows[s];
-        const int cx = db_clamp((int)floorf((p.x - g.x0) * g.inv_cell), g.gw - 1), cy = db_clamp((int)floorf((p.y - g.y0) * g.inv_cell), g.gh - 1);
+        const int cx = db_cell(p.x, g.x0, g.inv_cell, g.gw - 1), cy = db_cell(p.y, g.y0, g.inv_cell, g.gh - 1);
         int cnt = 0;
         for (int dy = -1; dy <= 1 && cnt < min_pts; ++dy) {
             const int y = cy + dy;
@@ -162,7 +189,7 @@ __global__ __launch_bounds__(256) void db_union_kernel(const float4* __restrict_
         const float4 p = rows[s];
         const int i = __float_as_int(p.w);
         if (!core[i]) continue;
-        const int cx = db_clamp((int)floorf((p.x - g.x0) * g.inv_cell), g.gw - 1), cy = db_clamp((int)floorf((p.y - g.y0) * g.inv_cell), g.gh - 1);
+        const int cx = db_cell(p.x, g.x0, g.inv_cell, g.gw - 1), cy = db_cell(p.y, g.y0, g.inv_cell, g.gh - 1);
         for (int dy = -1; dy <= 1; ++dy) {
             const int y = cy + dy;
             if (y < 0 || y >= g.gh) continue;
@@ -195,7 +222,7 @@ __global__ __launch_bounds__(256) void db_root_kernel(const float4* __restrict__
         if (core[i]) {
             r = db_find(parent, i);
         } else {
-            const int cx = db_clamp((int)floorf((p.x - g.x0) * g.inv_cell), g.gw - 1), cy = db_clamp((int)floorf((p.y - g.y0) * g.inv_cell), g.gh - 1);
+            const int cx = db_cell(p.x, g.x0, g.inv_cell, g.gw - 1), cy = db_cell(p.y, g.y0, g.inv_cell, g.gh - 1);
             for (int dy = -1; dy <= 1; ++dy) {
                 const int y = cy + dy;
                 if (y < 0 || y >= g.gh) continue;
@@ -258,17 +285,21 @@ static DbLayout db_layout(int n, int gw, int gh) {
 using namespace himo;
 
 extern "C" size_t himo_dbscan_workspace_bytes(int n, int grid_w, int grid_h) {
-    if (n < 0 || grid_w < 1 || grid_h < 1) return 0;
+    if (n < 0 || grid_w < 1 || grid_h < 1 || grid_w > kDbMaxSide || grid_h > kDbMaxSide) return 0;
     return db_layout(n, grid_w, grid_h).total + 256;
 }
 
 // d_xyz [n][pitch >= 3] float32; d_skip [n] bytes or NULL (non-zero = the point takes no part, label 0); BEV grid of `cell` >= eps
-// metre cells from (x0, y0), grid_w x grid_h of them (points beyond it are binned into the border cells: still exact, only slower
-// there); d_labels [n] int32: 0 noise / skipped, 1 .. K clusters ordered by their lowest point index; d_n_clusters: K (or NULL).
+// metre cells from (x0, y0), grid_w x grid_h of them, each side at most 2^15 cells and grid_w * grid_h at most 2^26 (points beyond it
+// are binned into the border cells: still exact, only slower there; inside the library the cells are 1/63 wider than `cell`, see
+// kDbMargin, so the last cells of a grid stay empty); eps * eps must be a normal finite float (about 1.1e-19 <= eps <= 1.8e19);
+// d_labels [n] int32: 0 noise / skipped, 1 .. K clusters ordered by their lowest core index; d_n_clusters: K (or NULL).
 extern "C" int himo_dbscan(int n, const float* d_xyz, int pitch, const unsigned char* d_skip, float eps, int min_pts, float x0, float y0,
                            float cell, int grid_w, int grid_h, int32_t* d_labels, int32_t* d_n_clusters, void* d_workspace,
                            size_t workspace_bytes, void* stream) {
-    if (n < 0 || pitch < 3 || !(eps > 0.f) || min_pts < 1 || !(cell >= eps) || grid_w < 1 || grid_h < 1 || (int64_t)grid_w * grid_h > (1 << 26))
+    const float eps2 = eps * eps;
+    if (n < 0 || pitch < 3 || !(eps > 0.f) || !(eps2 >= FLT_MIN && eps2 <= FLT_MAX) || min_pts < 1 || !(cell >= eps) || grid_w < 1 || grid_h < 1 ||
+        grid_w > kDbMaxSide || grid_h > kDbMaxSide || (int64_t)grid_w * grid_h > (1 << 26))
         return HIMO_ERR_INVALID_ARGUMENT;
     if (n > 0 && (!d_xyz || !d_labels)) return HIMO_ERR_INVALID_ARGUMENT;
     if (!d_workspace || workspace_bytes < himo_dbscan_workspace_bytes(n, grid_w, grid_h) || !aligned16(d_workspace)) return HIMO_ERR_WORKSPACE;
@@ -286,8 +317,7 @@ extern "C" int himo_dbscan(int n, const float* d_xyz, int pitch, const unsigned 
     int* tile_sum = reinterpret_cast<int*>(w + L.tile_sum);
     const int cells = grid_w * grid_h, nb = (n + 255) / 256;
     const int nw = nb < 4096 ? nb : 4096;                       // blocks of the wave-per-row kernels (grid-stride over the participating rows)
-    const DbGrid g{x0, y0, 1.0f / cell, grid_w, grid_h};
-    const float eps2 = eps * eps;
+    const DbGrid g{x0, y0, (float)((1.0 - (double)kDbMargin) / (double)cell), grid_w, grid_h};
     ProfScope ps("dbscan_kernels", s);
     HIMO_HIP(hipMemsetAsync(count, 0, ((size_t)cells + 1) * 4, s));
     HIMO_HIP(hipMemsetAsync(cursor, 0, (size_t)cells * 4, s));

@@ -16,7 +16,7 @@ specification, chosen so that every step is exact and order-independent:
      LiDAR exceeds 0.35 m, so the bar grows with range instead of declaring most far static returns candidates).
      Exact nearest neighbours through the BEV cell grid (csrc/nngrid.hip).
   2. clusters: DBSCAN(``eps``, ``min_pts``) over the candidates (csrc/dbscan.hip: labels are a pure function of the input --
-     clusters numbered by their lowest point index, a border point joins the neighbouring cluster of lowest such index).
+     clusters numbered by their lowest CORE point index, a border point joins the neighbouring cluster of lowest such index).
      ``cluster="hdbscan"`` takes them from ``hdbscan`` ("HDBSCAN, v1", csrc/hdbscan.hip; its rule is in that function's docstring)
      instead, for objects too sparse at range for one radius; the default is DBSCAN.
   3. everything else -- ground, static, noise -- is label 0.

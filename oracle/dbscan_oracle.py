@@ -10,7 +10,7 @@ from scipy.spatial import cKDTree
 
 
 def dbscan(points: np.ndarray, eps: float, min_pts: int, skip: np.ndarray | None = None) -> np.ndarray:
-    """int32 labels: 0 noise / skipped, 1 .. K clusters in the order of their lowest point index; border points join the
+    """int32 labels: 0 noise / skipped, 1 .. K clusters in the order of their lowest CORE point index; border points join the
     neighbouring cluster of lowest such index.  Distances in float32 arithmetic like the product (dx*dx + dy*dy + dz*dz <= eps*eps)."""
     from sklearn.cluster import DBSCAN
     pts = np.ascontiguousarray(points[:, :3], dtype=np.float32)

@@ -1,4 +1,5 @@
-"""Guarded operands for the GPU conformance suites (tests/test_conv_conformance_gpu.py, tests/test_train_conformance_gpu.py).
+"""Guarded operands for the GPU conformance suites (tests/test_conv_conformance_gpu.py, tests/test_train_conformance_gpu.py,
+tests/test_dbscan_conformance_gpu.py).
 
 Every operand lives inside a larger buffer with guard regions before and after it.  Everything that is not an operand --
 pitch padding, gaps between images, the guards -- holds a fixed NaN bit pattern: a read of it poisons a result, and a
@@ -8,6 +9,7 @@ import torch
 
 NAN_BITS = 0x7FC0BEEF                 # a quiet NaN with a payload no kernel produces
 GUARD = 1 << 16                       # floats of guard on each side of an operand
+BYTE_FILL = 0xA5                      # what GuardedBytes holds outside its view
 
 
 def layout(n_img, n_inner, bs, outer, pixels, pitch, c):
@@ -53,3 +55,25 @@ class Guarded:
 
     def reset(self):
         self.buf.fill_(NAN_BITS)
+
+
+class GuardedBytes:
+    """``nbytes`` bytes, ``off`` bytes past a 256-byte boundary, inside a buffer of BYTE_FILL with GUARD bytes on both sides: byte
+    operands (flags) and workspaces, whose size is no multiple of a word"""
+
+    def __init__(self, nbytes, device, off=0):
+        self.nbytes, self.base = int(nbytes), GUARD + off
+        self.buf = torch.full((self.base + self.nbytes + GUARD,), BYTE_FILL, dtype=torch.uint8, device=device)
+
+    @property
+    def ptr(self):
+        return self.buf.data_ptr() + self.base
+
+    def put(self, values):
+        self.buf[self.base:self.base + self.nbytes] = values.reshape(-1).to(device=self.buf.device, dtype=torch.uint8)
+
+    def bytes(self):
+        return self.buf[self.base:self.base + self.nbytes].cpu()
+
+    def untouched_outside(self):
+        return bool(torch.all(self.buf[:self.base] == BYTE_FILL)) and bool(torch.all(self.buf[self.base + self.nbytes:] == BYTE_FILL))

@@ -49,7 +49,7 @@ def participates(pts, ground):
 # ---- rule 1 -------------------------------------------------------------------------------------------------------------------------
 def dbscan(pts, eps=EPS, min_pts=MIN_PTS, skip=None):
     """brute-force DBSCAN by the package's rule (csrc/dbscan.hip): float32 distances dx*dx + dy*dy + dz*dz <= eps*eps, min_pts counts
-    the point itself, clusters numbered by their lowest point index, a border point joins the neighbouring cluster of lowest such index"""
+    the point itself, clusters numbered by their lowest core point index, a border point joins the neighbouring cluster of lowest such index"""
     pts = np.asarray(pts, f32).reshape(-1, 3)
     n = len(pts)
     labels = np.zeros(n, np.int32)

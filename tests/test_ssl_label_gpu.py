@@ -2,7 +2,7 @@
 assets/slurm/ssl-train-av2.sh:32) against the CPU oracle (oracle/dbscan_oracle.py: sklearn.cluster.DBSCAN for the core points and
 their partition, this build's border rule restated with cKDTree).  PARITY UNPINNED vs the reference (generator absent); the
 clustering itself is pinned against sklearn: labels must be EQUAL, not just equal up to renumbering -- both number clusters by
-their lowest point index."""
+their lowest core point index."""
 import numpy as np
 import pytest
 import torch
