@@ -12,13 +12,14 @@
 //                           target frame, cell index, integer histogram of points per cell
 //   cell_scan_*_kernel      two-level exclusive scan of the 262,144 cell counts
 //   pillar_fill_kernel      counting-sort scatter of point indices into per-cell lists
-//   pillar_feature_kernel   half a wavefront (32 lanes = 32 channels) per cell: the cell's point
-//                           list is held in registers (through global memory for cells with more
-//                           than 32 points) and put in ascending point order with wavefront shuffles
-//                           (so sums are order-deterministic and match a sequential CPU scatter), then
-//                           mean -> 9 features -> Linear(9,32) -> BN -> ReLU -> mean over the cell,
-//                           one 128-byte NHWC store per cell; empty cells are written as zeros
-//                           (so no separate memset of the 32 MB image).
+//   pillar_feature_kernel   cells of 1 .. kLaneK points: ONE LANE per cell, 64 cells per wave -- the cell's records loaded at
+//                           once, ordered by point index in registers, rows transposed through LDS into 128-byte stores; cells
+//                           of more points: half a wavefront (32 lanes = 32 channels) per cell, the point list in registers
+//                           (through global memory beyond 32 points), put in ascending point order with wavefront shuffles.
+//                           Either way the sums are sequential in ascending point order (order-deterministic, matching a
+//                           sequential CPU scatter): mean -> 9 features -> Linear(9,32) -> BN -> ReLU -> mean over the cell,
+//                           128 bytes NHWC per cell; empty cells are written as zeros (no separate memset of the 32 MB image).
+//                           HIMO_PILLAR_NO_LISTS: the ascending lists and NULL-offset sweeps' offsets are not written.
 // Only integer atomics are used; the output is bit-deterministic.
 #include "himo_common.h"
 #include "bf16x3.h"
@@ -98,7 +99,7 @@ __global__ __launch_bounds__(256) void pillar_assign_kernel(PillarBatch m) {
         // (kept in order2 until the feature kernel, which runs after the scatter, writes the ascending order there)
         a.order2[i] = atomicAdd(&a.cell_count[cell], 1);
     } else {
-        a.offsets[i * 3] = 0.f; a.offsets[i * 3 + 1] = 0.f; a.offsets[i * 3 + 2] = 0.f;
+        if (a.offsets) { a.offsets[i * 3] = 0.f; a.offsets[i * 3 + 1] = 0.f; a.offsets[i * 3 + 2] = 0.f; }
     }
     a.pid[i] = cell;
 }
@@ -169,61 +170,246 @@ __global__ __launch_bounds__(256) void pillar_fill_kernel(PillarBatch m) {
 
 constexpr int kCellsPerBlock = 8;     // 8 cells x 32 lanes = 256 threads
 
-constexpr int kFeatCells = 64;        // cells per block of the feature kernel
+constexpr int kFeatCells = 1024;      // cells per block of the feature kernel: four per thread, sixteen occupancy words
+constexpr int kFeatRounds = kFeatCells / 256;
+#ifndef HIMO_PILLAR_LANE_K
+#define HIMO_PILLAR_LANE_K 4
+#endif
+constexpr int kLaneK = HIMO_PILLAR_LANE_K;       // cells of up to kLaneK points take the lane path (table: profiles/pillar_lanes.txt)
+constexpr int kStgPitch = 32;         // words per staged row; its eight 16-byte pieces are swizzled by the row number (stg_piece)
+constexpr int kFeatNoLists = 1, kFeatHalfwaveOnly = 2;       // HIMO_PILLAR_NO_LISTS / HIMO_PILLAR_HALFWAVE_ONLY as the kernel sees them
 
-// A block owns 64 consecutive cells.  Most cells of a sweep are empty (120k points over 262k cells): their 128-byte
-// rows are zero-filled cooperatively, and the non-empty ones are compacted into a short list that the block's eight
-// half-waves (32 lanes = 32 channels) work through INDEPENDENTLY: a cell's points live in the half-wave's registers
-// (lane j = point j), are ranked and permuted into ascending point order with wavefront shuffles, and the sequential
-// (order-deterministic) sums broadcast one point at a time -- no LDS, no barrier after the prologue.  Cells with more
-// than 32 points rank in 32-point chunks and go through the order2 array in global memory.
 __device__ inline float shfl32(float v, int src) { return __shfl(v, src, 32); }
 __device__ inline int shfl32(int v, int src) { return __shfl(v, src, 32); }
 
-__global__ __launch_bounds__(256) void pillar_feature_kernel(PillarBatch m) {
-    const PillarArgs& a = m.s[blockIdx.y];
-    __shared__ int s_beg[kFeatCells + 1];
-    __shared__ int s_list[kFeatCells];
-    __shared__ int s_nlist;
-    const int sub = threadIdx.x >> 5, c = threadIdx.x & 31;
-    const int n_cells = a.g.W * a.g.H;
-    const int cell0 = blockIdx.x * kFeatCells;
-    static_assert(kFeatCells == 64, "one 64-bit occupancy word per block");
-    // incremental images: the cells of this block that held data after the previous pass over this image (all of them the
-    // first time); read by every thread BEFORE the barrier, replaced by thread 0 after it
-    const unsigned long long was = a.occ ? a.occ[blockIdx.x] : ~0ull;
-    if (threadIdx.x <= kFeatCells) s_beg[threadIdx.x] = cell_offset(a, min(cell0 + (int)threadIdx.x, n_cells));
-    __syncthreads();
-    if (threadIdx.x < 64) {
-        // wave 0 compacts the non-empty cells: the single-point ones first, then the others.  The two half-waves of a wave work
-        // on neighbouring list entries, and a wave runs the (shuffle-heavy) multi-point path whenever EITHER half needs it: with
-        // the kinds grouped a wave meets it for 22 % of its cell pairs instead of 39 % (uniform 120k-point sweep)
-        const int cnt = cell0 + (int)threadIdx.x < n_cells ? s_beg[threadIdx.x + 1] - s_beg[threadIdx.x] : 0;
-        const unsigned long long one = __ballot(cnt == 1), many = __ballot(cnt > 1);
-        const unsigned long long below = (1ull << threadIdx.x) - 1ull;
-        if (cnt == 1) s_list[__popcll(one & below)] = threadIdx.x;
-        if (cnt > 1) s_list[__popcll(one) + __popcll(many & below)] = threadIdx.x;
-        if (threadIdx.x == 0) {
-            s_nlist = __popcll(one | many);
-            if (a.occ) a.occ[blockIdx.x] = one | many;
-            if (a.occ_out) a.occ_out[blockIdx.x] = one | many;
+// The lane path: up to 64 cells of 1 .. KK points each, ONE CELL PER LANE (`list`: their block-local cell numbers).  A lane issues
+// all of its cell's cell_rec loads before it uses any, puts the points in ascending point order in registers (odd-even transposition
+// network), and forms exactly the sequential sums of the half-wave path below -- from 0.f in ascending order, mean = sum / count,
+// v = f0 w0 then eight fmaf, v * scale + shift as two roundings, acc += max(v, 0), feature = acc / count -- so every output keeps
+// its bits.  A channel's nine weights and its scale / shift are wave-uniform: three 16-byte LDS broadcasts (s_w).  Four channels at
+// a time go into the wave's staging rows (float32, or the words of the split record), and the rows leave as full 128-byte stores,
+// eight rows per instruction.  KK == 1: the mean IS the point, so the three offset-to-mean features are x - x as in the half-wave
+// path's shortcut, acc = 0.f + max(v, 0), and the division by 1.0f is dropped (x / 1.0f == x for every finite x and both zeros).
+// word offset of 16-byte piece `piece` of staged row `r`: piece ^ (r & 7), so that the 16-byte writes of eight neighbouring rows
+// to one piece, and the reads of a row's eight pieces, both spread over all the banks
+__device__ inline int stg_piece(int r, int piece) { return r * kStgPitch + ((piece ^ (r & 7)) << 2); }
+
+template <int KK>
+__device__ inline void lane_cells(const PillarArgs& a, int flags, const float4* s_w, unsigned* stg, const unsigned short* list, int n_ent,
+                                  const int* s_beg, int cell0, int lane) {
+    const bool act = lane < n_ent;
+    const int lc = act ? list[lane] : 0;
+    const int beg = s_beg[lc];
+    const int cnt = act ? s_beg[lc + 1] - beg : 0;
+    const int cell = cell0 + lc;
+    float px[KK], py[KK], pz[KK];
+    int pi[KK];
+#pragma unroll
+    for (int j = 0; j < KK; ++j) {
+        float4 rc = make_float4(0.f, 0.f, 0.f, __int_as_float(0x7fffffff));       // padding sorts behind every point
+        if (j < cnt) rc = a.cell_rec[beg + j];
+        px[j] = rc.x; py[j] = rc.y; pz[j] = rc.z; pi[j] = __float_as_int(rc.w);
+    }
+#pragma unroll
+    for (int r = 0; r < KK; ++r) {
+#pragma unroll
+        for (int i = r & 1; i + 1 < KK; i += 2) {
+            const bool sw = pi[i] > pi[i + 1];
+            const float tx = px[i], ty = py[i], tz = pz[i];
+            const int ti = pi[i];
+            px[i] = sw ? px[i + 1] : tx; py[i] = sw ? py[i + 1] : ty; pz[i] = sw ? pz[i + 1] : tz; pi[i] = sw ? pi[i + 1] : ti;
+            px[i + 1] = sw ? tx : px[i + 1]; py[i + 1] = sw ? ty : py[i + 1]; pz[i + 1] = sw ? tz : pz[i + 1]; pi[i + 1] = sw ? ti : pi[i + 1];
         }
     }
-    // zero rows of the empty cells (those that are not zero already): 16 bytes per lane, 8 lanes per 128-byte row, 32 rows per pass
+    const int iy = cell / a.g.W, ix = cell - iy * a.g.W;
+    const float ccx = (float)ix * a.g.vx + a.g.cx0, ccy = (float)iy * a.g.vy + a.g.cy0, ccz = 0.f * a.g.vz + a.g.cz0;
+    const float fc = act ? (float)cnt : 1.f;
+    float mx, my, mz;
+    if (KK == 1) {
+        mx = px[0]; my = py[0]; mz = pz[0];
+    } else {
+        float sx = 0.f, sy = 0.f, sz = 0.f;
 #pragma unroll
-    for (int i = 0; i < kFeatCells / 32; ++i) {
-        const int lc = i * 32 + (threadIdx.x >> 3);
-        if (cell0 + lc < n_cells && s_beg[lc + 1] == s_beg[lc] && ((was >> lc) & 1ull))
-            *reinterpret_cast<float4*>(a.image + (int64_t)(cell0 + lc) * a.image_pitch + (threadIdx.x & 7) * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int j = 0; j < KK; ++j)
+            if (j < cnt) { sx += px[j]; sy += py[j]; sz += pz[j]; }
+        mx = sx / fc; my = sy / fc; mz = sz / fc;
+    }
+    float dx[KK], dy[KK], dz[KK], ox[KK], oy[KK], oz[KK];
+#pragma unroll
+    for (int j = 0; j < KK; ++j) {
+        dx[j] = px[j] - mx; dy[j] = py[j] - my; dz[j] = pz[j] - mz;
+        ox[j] = px[j] - ccx; oy[j] = py[j] - ccy; oz[j] = pz[j] - ccz;
+        if (j < cnt) {
+            if (!(flags & kFeatNoLists)) a.order2[beg + j] = pi[j];               // the ascending list, kept for the training backward pass
+            if (a.offsets) {
+                float* o = a.offsets + (int64_t)pi[j] * 3;
+                o[0] = ox[j]; o[1] = oy[j]; o[2] = oz[j];
+            }
+        }
+    }
+    int maxcnt = 1;                                  // the most points any lane of this wave holds
+#pragma unroll
+    for (int j = 1; j < KK; ++j)
+        if (__ballot(cnt > j)) maxcnt = j + 1;
+#pragma unroll 1
+    for (int g = 0; g < 8; ++g) {
+        float o[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const float4 wa = s_w[(g * 4 + u) * 3], wb = s_w[(g * 4 + u) * 3 + 1], wc = s_w[(g * 4 + u) * 3 + 2];
+            float acc = 0.f;
+#pragma unroll
+            for (int j = 0; j < KK; ++j) {
+                if (j < maxcnt) {
+                    float v = px[j] * wa.x;
+                    v = fmaf(py[j], wa.y, v); v = fmaf(pz[j], wa.z, v);
+                    v = fmaf(dx[j], wa.w, v); v = fmaf(dy[j], wb.x, v); v = fmaf(dz[j], wb.y, v);
+                    v = fmaf(ox[j], wb.z, v); v = fmaf(oy[j], wb.w, v); v = fmaf(oz[j], wc.x, v);
+                    v = v * wc.y + wc.z;
+                    const float r = acc + fmaxf(v, 0.f);
+                    acc = j < cnt ? r : acc;
+                }
+            }
+            o[u] = KK == 1 ? acc : acc / fc;
+        }
+        if (a.image_split) {       // channels 4 (g & 3) .. + 3 of record g >> 2: two words of fp16 highs, two of lows (see the half-wave store)
+            unsigned h[4], l[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) split2_rounded(o[u], h[u], l[u]);
+            const int piece = (g >> 2) * 4 + ((g & 3) >> 1), at = (g & 1) * 2;      // words 2 (g & 3), + 1 of the record; lows 8 words on
+            *reinterpret_cast<uint2*>(stg + stg_piece(lane, piece) + at) = make_uint2(h[0] | (h[1] << 16), h[2] | (h[3] << 16));
+            *reinterpret_cast<uint2*>(stg + stg_piece(lane, piece + 2) + at) = make_uint2(l[0] | (l[1] << 16), l[2] | (l[3] << 16));
+        } else {
+            *reinterpret_cast<float4*>(stg + stg_piece(lane, g)) = make_float4(o[0], o[1], o[2], o[3]);
+        }
+    }
+    __builtin_amdgcn_wave_barrier();                 // DS operations of a wave execute in order: its reads below see the rows
+    for (int r0 = 0; r0 < n_ent; r0 += 8) {
+        const int r = r0 + (lane >> 3);
+        if (r < n_ent) {
+            const uint4 d = *reinterpret_cast<const uint4*>(stg + stg_piece(r, lane & 7));
+            *reinterpret_cast<uint4*>(a.image + (int64_t)(cell0 + list[r]) * a.image_pitch + (lane & 7) * 4) = d;
+        }
+    }
+    __builtin_amdgcn_wave_barrier();                 // the next chunk rewrites the rows
+}
+
+// A block owns 1024 consecutive cells (one block of the cell scan), a thread looks at four of them (t, t + 256, ...), a wave at
+// the 64 of one occupancy word at a time.  Most cells of a sweep are empty (120k points over 262k cells): each wave zero-fills the
+// 128-byte rows of its own empty cells (those that are not zero already), and the non-empty ones are compacted into lists by kind:
+//   single (1 point), two (2 points), few (3 .. kLaneK points)   64 list entries per wave, one cell per lane (lane_cells above;
+//     the twos stand in front of the other few-point cells, so most chunks run two rounds of the per-point arithmetic only);
+//   crowded (> kLaneK points)                       the block's eight half-waves (32 lanes = 32 channels) work through them
+//     INDEPENDENTLY: a cell's points live in the half-wave's registers (lane j = point j), are ranked and permuted into ascending
+//     point order with wavefront shuffles, and the sequential (order-deterministic) sums broadcast one point at a time.  Cells
+//     with more than 32 points rank in 32-point chunks and go through the order2 array in global memory.
+// A uniform 120k-point sweep has 76k single cells, 20k of two or more points and a few dozen of more than four: with a half-wave per
+// cell the kernel was a latency chain per cell (2.4 us per iteration), not a bandwidth or an arithmetic problem.  With a lane per
+// cell it is arithmetic, so lanes must not idle: 1024 cells fill the chunks (a 256-cell block left 8 of 64 lanes busy in its second
+// single-point chunk, 19 of 64 in its few-point chunk), and the first chunks are dealt to the waves starting at wave blockIdx.x & 3
+// -- the waves of a CU's blocks share its four SIMDs by wave number, and with every block's long chunk on wave 0 one SIMD did them
+// all (190 -> 187 us per 12-sweep launch only; 138 us with both) -- the others to the waves as they come free.
+// kFeatHalfwaveOnly sends EVERY non-empty cell down the half-wave path (single-point cells first: the two half-waves of a wave work
+// on neighbouring entries and a wave runs the shuffle-heavy path whenever either half needs it); kFeatNoLists: nobody reads the
+// ascending lists afterwards, so only the > 32-point path, which needs them as scratch, writes order2.  No barrier after the prologue.
+__global__ __launch_bounds__(256) void pillar_feature_kernel(PillarBatch m, int flags) {
+    const PillarArgs& a = m.s[blockIdx.y];
+    __shared__ int s_beg[kFeatCells + 1];
+    __shared__ unsigned short s_list[kFeatCells];    // lane path: [single | two | few | crowded]; half-wave only: [single | others]
+    __shared__ int s_wn[4][kFeatRounds * 4];         // [kind][round * 4 + wave] entries
+    __shared__ int s_next;                           // the next chunk nobody has taken
+    __shared__ float4 s_w[32 * 3];                   // per channel: w0 .. w8, scale, shift, 0
+    __shared__ __attribute__((aligned(16))) unsigned s_stg[4][64 * kStgPitch];
+    static_assert(kFeatCells == kScanBlock && kLaneK >= 1 && kLaneK <= 16, "a block of the scan per block");
+    const int sub = threadIdx.x >> 5, c = threadIdx.x & 31, wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int n_cells = a.g.W * a.g.H;
+    const int cell0 = blockIdx.x * kFeatCells;
+    // incremental images: the cells of this wave's words that held data after the previous pass over this image (all of them the
+    // first time); the wave replaces each word below, after its zero fill has used it
+    unsigned long long was[kFeatRounds];
+#pragma unroll
+    for (int u = 0; u < kFeatRounds; ++u) {
+        const bool word_ok = cell0 + u * 256 + wv * 64 < n_cells;                 // this occupancy word exists
+        was[u] = a.occ && word_ok ? a.occ[blockIdx.x * (kFeatCells / 64) + u * 4 + wv] : ~0ull;
+        s_beg[u * 256 + threadIdx.x] = cell_offset(a, min(cell0 + u * 256 + (int)threadIdx.x, n_cells));
+    }
+    if (threadIdx.x == 0) { s_beg[kFeatCells] = cell_offset(a, min(cell0 + kFeatCells, n_cells)); s_next = 4; }
+    for (int i = threadIdx.x; i < 32 * 12; i += 256) {
+        const int ch = i / 12, q = i - ch * 12;
+        reinterpret_cast<float*>(s_w)[i] = q < 9 ? a.pfn_w[q * 32 + ch] : q == 9 ? a.pfn_scale[ch] : q == 10 ? a.pfn_shift[ch] : 0.f;
     }
     __syncthreads();
-    const int nlist = s_nlist;
+    const bool hw_only = (flags & kFeatHalfwaveOnly) != 0;
+    int kind[kFeatRounds];
+    unsigned long long mine[kFeatRounds];            // the cells of my kind in my wave's word of round u
+#pragma unroll
+    for (int u = 0; u < kFeatRounds; ++u) {
+        const int lc = u * 256 + threadIdx.x;
+        const int cnt = cell0 + lc < n_cells ? s_beg[lc + 1] - s_beg[lc] : 0;
+        kind[u] = cnt == 0 ? -1 : hw_only ? (cnt == 1 ? 0 : 3) : cnt == 1 ? 0 : cnt > kLaneK ? 3 : cnt == 2 ? 1 : 2;
+        mine[u] = 0ull;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const unsigned long long b = __ballot(kind[u] == q);
+            if (lane == 0) s_wn[q][u * 4 + wv] = __popcll(b);
+            if (kind[u] == q) mine[u] = b;
+        }
+        const unsigned long long occw = __ballot(cnt > 0);
+        // zero rows of this word's empty cells that are not zero already: 16 bytes per lane, 8 lanes per 128-byte row, 8 rows per pass
+        const unsigned long long dirty = was[u] & ~occw;
+        for (int r0 = 0; r0 < 64 && (dirty >> r0); r0 += 8) {
+            const int row = u * 256 + wv * 64 + r0 + (lane >> 3);
+            if (((dirty >> (r0 + (lane >> 3))) & 1ull) && cell0 + row < n_cells)
+                *reinterpret_cast<float4*>(a.image + (int64_t)(cell0 + row) * a.image_pitch + (lane & 7) * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        if (lane == 0 && cell0 + u * 256 + wv * 64 < n_cells) {
+            if (a.occ) a.occ[blockIdx.x * (kFeatCells / 64) + u * 4 + wv] = occw;
+            if (a.occ_out) a.occ_out[blockIdx.x * (kFeatCells / 64) + u * 4 + wv] = occw;
+        }
+    }
+    __syncthreads();
+    int n_kind[4], before[4][kFeatRounds];           // before[q][u]: entries of kind q in the words in front of mine of round u
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        int run = 0;
+#pragma unroll
+        for (int i = 0; i < kFeatRounds * 4; ++i) {
+            if ((i & 3) == wv) before[q][i >> 2] = run;
+            run += s_wn[q][i];
+        }
+        n_kind[q] = run;
+    }
+#pragma unroll
+    for (int u = 0; u < kFeatRounds; ++u) {
+        if (kind[u] < 0) continue;
+        int at = 0;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) at += q < kind[u] ? n_kind[q] : q == kind[u] ? before[q][u] : 0;
+        s_list[at + __popcll(mine[u] & ((1ull << lane) - 1ull))] = (unsigned short)(u * 256 + threadIdx.x);
+    }
+    __syncthreads();
+    const int n_single = hw_only ? 0 : n_kind[0], n_few = hw_only ? 0 : n_kind[1] + n_kind[2];
+    const int nlist = n_kind[0] + n_kind[1] + n_kind[2] + n_kind[3];
+    {   // the chunks, longest first: the few-point ones from the back of their list (3 .. kLaneK points), then the twos, then the
+        // single-point ones.  The first four are dealt to the waves from wave blockIdx.x & 3 on, the rest go to whoever is free
+        const int ch_few = (n_few + 63) >> 6, ch_single = (n_single + 63) >> 6;
+        for (int t = __builtin_amdgcn_readfirstlane((wv - (int)blockIdx.x) & 3); t < ch_few + ch_single;) {
+            const int f = ch_few - 1 - t, o = t - ch_few;
+            if (t < ch_few) lane_cells<kLaneK>(a, flags, s_w, s_stg[wv], s_list + n_single + f * 64, min(64, n_few - f * 64), s_beg, cell0, lane);
+            else lane_cells<1>(a, flags, s_w, s_stg[wv], s_list + o * 64, min(64, n_single - o * 64), s_beg, cell0, lane);
+            int nxt = 0;
+            if (lane == 0) nxt = atomicAdd(&s_next, 1);
+            t = __builtin_amdgcn_readfirstlane(nxt);
+        }
+    }
+    if (n_single + n_few == nlist) return;
     float w[9];
 #pragma unroll
-    for (int k = 0; k < 9; ++k) w[k] = a.pfn_w[k * 32 + c];
-    const float scale = a.pfn_scale[c], shift = a.pfn_shift[c];
+    for (int k = 0; k < 9; ++k) w[k] = reinterpret_cast<const float*>(s_w)[c * 12 + k];
+    const float scale = reinterpret_cast<const float*>(s_w)[c * 12 + 9], shift = reinterpret_cast<const float*>(s_w)[c * 12 + 10];
+    const bool keep_lists = !(flags & kFeatNoLists);
 
-    for (int k = sub; k < nlist; k += kCellsPerBlock) {
+    for (int k = n_single + n_few + sub; k < nlist; k += kCellsPerBlock) {
         const int lc = s_list[k];
         const int cell = cell0 + lc;
         const int beg = s_beg[lc];
@@ -238,7 +424,7 @@ __global__ __launch_bounds__(256) void pillar_feature_kernel(PillarBatch m) {
             const float4 rc = a.cell_rec[beg];
             const int pj = __float_as_int(rc.w);
             const float x = rc.x, y = rc.y, z = rc.z;
-            if (c == 0) a.order2[beg] = pj;
+            if (c == 0 && keep_lists) a.order2[beg] = pj;
             const float f6[3] = {x - ccx, y - ccy, z - ccz};
             float v = x * w[0];
             v = fmaf(y, w[1], v); v = fmaf(z, w[2], v);
@@ -246,7 +432,7 @@ __global__ __launch_bounds__(256) void pillar_feature_kernel(PillarBatch m) {
             v = fmaf(f6[0], w[6], v); v = fmaf(f6[1], w[7], v); v = fmaf(f6[2], w[8], v);
             v = v * scale + shift;
             acc = 0.f + fmaxf(v, 0.f);
-            if (c < 3) a.offsets[(int64_t)pj * 3 + c] = f6[c];
+            if (c < 3 && a.offsets) a.offsets[(int64_t)pj * 3 + c] = f6[c];
         } else if (cnt <= 32) {
             // lane j holds point j of the cell's (scatter-ordered) list; rank by point index, permute into ascending order
             const bool have = c < cnt;
@@ -260,7 +446,7 @@ __global__ __launch_bounds__(256) void pillar_feature_kernel(PillarBatch m) {
                 if (shfl32(rank, j) == c) src = j;
             const int sidx = shfl32(idx, src);
             const float px = shfl32(ux, src), py = shfl32(uy, src), pz = shfl32(uz, src);
-            if (have) a.order2[beg + c] = sidx;               // kept for the training backward pass
+            if (have && keep_lists) a.order2[beg + c] = sidx;               // kept for the training backward pass
             float sx = 0.f, sy = 0.f, sz = 0.f;
             for (int j = 0; j < cnt; ++j) { sx += shfl32(px, j); sy += shfl32(py, j); sz += shfl32(pz, j); }
             const float mx = sx / fc, my = sy / fc, mz = sz / fc;
@@ -273,7 +459,7 @@ __global__ __launch_bounds__(256) void pillar_feature_kernel(PillarBatch m) {
                 for (int q = 1; q < 9; ++q) v = fmaf(f[q], w[q], v);
                 v = v * scale + shift;
                 acc += fmaxf(v, 0.f);
-                if (c < 3) a.offsets[(int64_t)pj * 3 + c] = f[6 + c];
+                if (c < 3 && a.offsets) a.offsets[(int64_t)pj * 3 + c] = f[6 + c];
             }
         } else {
             // crowded cell: rank every point against the list in 32-point chunks held in registers, ascending order
@@ -316,7 +502,7 @@ __global__ __launch_bounds__(256) void pillar_feature_kernel(PillarBatch m) {
                     for (int q = 1; q < 9; ++q) v = fmaf(f[q], w[q], v);
                     v = v * scale + shift;
                     acc += fmaxf(v, 0.f);
-                    if (c < 3) a.offsets[(int64_t)pj * 3 + c] = f[6 + c];
+                    if (c < 3 && a.offsets) a.offsets[(int64_t)pj * 3 + c] = f[6 + c];
                 }
             }
         }
@@ -646,12 +832,13 @@ extern "C" int himo_pillar_occupancy_reset(void* d_workspace, size_t workspace_b
 static int pillar_args(PillarArgs& a, int64_t n, const float* d_pts, int pc_stride, const float* h_transform, const float* h_range,
                        const float* h_voxel, const float* h_centre_offset, int grid_w, int grid_h, const float* d_pfn_weight,
                        const float* d_pfn_scale, const float* d_pfn_shift, float* d_xyz_t, int32_t* d_pid, float* d_offsets,
-                       float* d_image, int image_pitch, void* d_workspace, size_t workspace_bytes, bool incremental = false) {
+                       float* d_image, int image_pitch, void* d_workspace, size_t workspace_bytes, bool incremental = false,
+                       bool offsets_optional = false) {
     // the order of the refusals is the one include/himo_amd.h states: INVALID_ARGUMENT, UNSUPPORTED, WORKSPACE
     if (n < 0 || pc_stride < 3 || grid_w < 1 || grid_h < 1 || !h_transform || !h_range || !h_voxel || !h_centre_offset)
         return HIMO_ERR_INVALID_ARGUMENT;
     if (!d_pfn_weight || !d_pfn_scale || !d_pfn_shift || !d_image || !d_workspace) return HIMO_ERR_INVALID_ARGUMENT;
-    if (n > 0 && (!d_pts || !d_xyz_t || !d_pid || !d_offsets)) return HIMO_ERR_INVALID_ARGUMENT;
+    if (n > 0 && (!d_pts || !d_xyz_t || !d_pid || (!d_offsets && !offsets_optional))) return HIMO_ERR_INVALID_ARGUMENT;
     if (n > 0x7fffffff || image_pitch < 32) return HIMO_ERR_UNSUPPORTED;
     if ((image_pitch & 3) || (reinterpret_cast<uintptr_t>(d_image) & 15)) return HIMO_ERR_UNSUPPORTED;     // 16-byte row stores
     if (grid_cells(grid_w, grid_h) > kMaxCells) return HIMO_ERR_UNSUPPORTED;         // grids beyond 1M cells need a third scan level
@@ -691,8 +878,13 @@ static int sweeps_status(int n_sweeps, const himo_sweep* h_sweeps, int image_pit
     return HIMO_OK;
 }
 
+// bits 2 and 3 of the image_split word (HIMO_PILLAR_NO_LISTS, HIMO_PILLAR_HALFWAVE_ONLY) as the feature kernel takes them
+static int feature_flags(int image_split) {
+    return ((image_split & HIMO_PILLAR_NO_LISTS) ? kFeatNoLists : 0) | ((image_split & HIMO_PILLAR_HALFWAVE_ONLY) ? kFeatHalfwaveOnly : 0);
+}
+
 // the stage's five launches over `count` sweeps (same grid size for all of them)
-static int pillar_launch(const PillarBatch& m, int count, hipStream_t s) {
+static int pillar_launch(const PillarBatch& m, int count, int feat_flags, hipStream_t s) {
     const int cells = m.s[0].g.W * m.s[0].g.H;
     const int nblk = (cells + kScanBlock - 1) / kScanBlock;
     int64_t nmax = 0;
@@ -722,7 +914,7 @@ static int pillar_launch(const PillarBatch& m, int count, hipStream_t s) {
     HIMO_LAUNCH_CHECK("pillar_fill_kernel");
     {
         ProfScope ps("pillar_feature_kernel", s);
-        hipLaunchKernelGGL(pillar_feature_kernel, dim3((cells + kFeatCells - 1) / kFeatCells, count), dim3(256), 0, s, m);
+        hipLaunchKernelGGL(pillar_feature_kernel, dim3((cells + kFeatCells - 1) / kFeatCells, count), dim3(256), 0, s, m, feat_flags);
     }
     HIMO_LAUNCH_CHECK("pillar_feature_kernel");
     return HIMO_OK;
@@ -738,7 +930,7 @@ extern "C" int himo_pillarize(int64_t n, const float* d_pts, int pc_stride, cons
     const int st = pillar_args(m.s[0], n, d_pts, pc_stride, h_transform, h_range, h_voxel, h_centre_offset, grid_w, grid_h, d_pfn_weight,
                                d_pfn_scale, d_pfn_shift, d_xyz_t, d_pid, d_offsets, d_image, image_pitch, d_workspace, workspace_bytes);
     if (st != HIMO_OK) return st;
-    return pillar_launch(m, 1, (hipStream_t)stream);
+    return pillar_launch(m, 1, 0, (hipStream_t)stream);
 }
 
 // several sweeps of one sample (history, pc0, pc1) in the same five launches; every sweep has its own outputs, image
@@ -756,6 +948,7 @@ extern "C" int himo_pillarize_multi_ex(int n_sweeps, const himo_sweep* h_sweeps,
                                        const float* d_pfn_scale, const float* d_pfn_shift, int image_pitch, size_t workspace_bytes,
                                        int image_split, void* stream) {
     const bool incremental = (image_split & 2) != 0;                  // HIMO_IMAGE_INCREMENTAL
+    const int feat_flags = feature_flags(image_split);
     image_split &= 1;
     const int st0 = sweeps_status(n_sweeps, h_sweeps, image_pitch, image_split, true);
     if (st0 != HIMO_OK) return st0;
@@ -764,12 +957,12 @@ extern "C" int himo_pillarize_multi_ex(int n_sweeps, const himo_sweep* h_sweeps,
         const himo_sweep& w = h_sweeps[i];
         const int st = pillar_args(m.s[i], w.n, w.d_pts, w.pc_stride, w.transform, h_range, h_voxel, h_centre_offset, grid_w, grid_h,
                                    d_pfn_weight, d_pfn_scale, d_pfn_shift, w.d_xyz_t, w.d_pid, w.d_offsets, w.d_image, image_pitch,
-                                   w.d_workspace, workspace_bytes, incremental);
+                                   w.d_workspace, workspace_bytes, incremental, (feat_flags & kFeatNoLists) != 0);
         if (st != HIMO_OK) return st;
         m.s[i].image_split = image_split ? 1 : 0;
         m.s[i].occ_out = reinterpret_cast<unsigned long long*>(w.d_occupancy);
     }
-    return pillar_launch(m, n_sweeps, (hipStream_t)stream);
+    return pillar_launch(m, n_sweeps, feat_flags, (hipStream_t)stream);
 }
 
 static void carve_bwd(PillarBwdArgs& a, int64_t n, int cells, void* d_workspace) {
@@ -916,6 +1109,7 @@ extern "C" int himo_pillar_features_multi(int n_sweeps, const himo_sweep* h_swee
                                           const float* d_scale, const float* d_shift, int image_pitch, size_t workspace_bytes,
                                           int image_split, void* stream) {
     const bool incremental = (image_split & 2) != 0;
+    const int feat_flags = feature_flags(image_split);
     image_split &= 1;
     if (!d_scale || !d_shift) return HIMO_ERR_INVALID_ARGUMENT;
     const int st0 = sweeps_status(n_sweeps, h_sweeps, image_pitch, image_split, false);
@@ -925,7 +1119,7 @@ extern "C" int himo_pillar_features_multi(int n_sweeps, const himo_sweep* h_swee
         const himo_sweep& w = h_sweeps[i];
         const int st = pillar_args(m.s[i], w.n, w.d_pts, w.pc_stride, w.transform, h_range, h_voxel, h_centre_offset, grid_w, grid_h,
                                    d_pfn_weight, d_scale + 32 * i, d_shift + 32 * i, w.d_xyz_t, w.d_pid, w.d_offsets, w.d_image, image_pitch,
-                                   w.d_workspace, workspace_bytes, incremental);
+                                   w.d_workspace, workspace_bytes, incremental, (feat_flags & kFeatNoLists) != 0);
         if (st != HIMO_OK) return st;
         m.s[i].image_split = image_split ? 1 : 0;
         m.s[i].occ_out = reinterpret_cast<unsigned long long*>(w.d_occupancy);
@@ -934,7 +1128,7 @@ extern "C" int himo_pillar_features_multi(int n_sweeps, const himo_sweep* h_swee
     const int cells = grid_w * grid_h;
     {
         ProfScope ps("pillar_feature_kernel", s);
-        hipLaunchKernelGGL(pillar_feature_kernel, dim3((cells + kFeatCells - 1) / kFeatCells, n_sweeps), dim3(256), 0, s, m);
+        hipLaunchKernelGGL(pillar_feature_kernel, dim3((cells + kFeatCells - 1) / kFeatCells, n_sweeps), dim3(256), 0, s, m, feat_flags);
     }
     HIMO_LAUNCH_CHECK("pillar_feature_kernel");
     return HIMO_OK;

@@ -134,6 +134,10 @@ class HiMoPipeline:
         net = self.net
         if hasattr(net, "sparse_dec4"):
             net.sparse_dec4 = bool(net.precision == "f16x2" and net.fused_head and net.split_acts)
+            # the same reader, the fused head at pc0's points, is all that reads the pillar stage's per-point offsets: the other
+            # sweeps' offsets and the ascending cell lists (training only) are not written
+            if hasattr(net, "head_offsets_only"):
+                net.head_offsets_only = net.sparse_dec4
 
     def _fall_back(self):
         """precision="auto": leave the fp16 split for the bf16 split (float32 range) for good"""

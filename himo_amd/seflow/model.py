@@ -40,6 +40,7 @@ ACT_SPLIT_IN, ACT_SPLIT_OUT = 1, 2      # himo_conv_desc.act_layout: x / y in th
 ACT_ROW_MASK = 32                       # with ACT_SPLIT_IN: only the output pixels whose bit is set in ``mask`` are formed and written
 ACT_ACCUMULATE = 8                      # y += result (two-term bf16 3x3 kernel, float32 maps)
 ACT_STUFFED_2X = 16                     # x is a compact [H/2][W/2] map read as its zero-stuffed x2 image (same kernel)
+PILLAR_NO_LISTS, PILLAR_HALFWAVE_ONLY = 4, 8   # himo_pillarize_multi_ex image_split bits 2 and 3 (HIMO_PILLAR_*, include/himo_amd.h)
 
 
 _lib.register({
@@ -179,6 +180,10 @@ class SeFlowNet:
         # dec4 formed only at the cells that hold a point of the sweep the head gathers at (csrc/convsg.hip, ACT_ROW_MASK); off
         # by default -- DEC's other cells then keep whatever they held.  pipeline.HiMoPipeline switches it on
         self._sparse_dec4 = False
+        # pillar stage (csrc/pillar.hip, HIMO_PILLAR_NO_LISTS): only the per-point outputs somebody reads -- the offsets of frame slot
+        # HEAD_SLOT, which the head gathers with; the other sweeps' offsets and every sweep's ascending cell lists (the training
+        # backward pass reads those) are not written.  Off by default; pipeline.HiMoPipeline switches it on, the trainer never does
+        self.head_offsets_only = False
         self.tiles = {}
         self.lib = _lib.load()
         self.device = device if device is not None else _lib.require_gpu()
@@ -632,6 +637,8 @@ class SeFlowNet:
         p, pk, F = self.p, self.packed, self.F
         if self._sparse_dec4 and slot0 != self.HEAD_SLOT:
             raise ValueError("sparse_dec4: DEC is defined at the cells of frame slot HEAD_SLOT only")
+        if self.head_offsets_only and slot0 != self.HEAD_SLOT:
+            raise ValueError("head_offsets_only: the pillar stage wrote the offsets of frame slot HEAD_SLOT only")
         samples = list(range(len(pc0s))) if samples is None else list(samples)
         for lo in range(0, len(pc0s), self.MAX_HEAD_SAMPLES):
             grp = range(lo, min(lo + self.MAX_HEAD_SAMPLES, len(pc0s)))
@@ -674,6 +681,7 @@ class SeFlowNet:
             for t in sweeps:
                 self._reserve_points(t.shape[0])
         per_call = self.MAX_SWEEPS // self.F
+        lean = self.head_offsets_only and not self.keep_cell_lists
         for lo in range(0, len(jobs), per_call):
             grp = jobs[lo:lo + per_call]
             arr = (HimoSweep * (len(grp) * self.F))()
@@ -684,13 +692,16 @@ class SeFlowNet:
                     w.n, w.d_pts, w.pc_stride = pts.shape[0], pts.data_ptr(), pts.shape[1]
                     w.transform = _f32x(np.asarray(T, dtype=np.float32).reshape(-1))
                     w.d_xyz_t, w.d_pid, w.d_offsets = st["xyz_t"][slot].data_ptr(), st["pid"][slot].data_ptr(), st["offsets"][slot].data_ptr()
+                    if lean and slot != self.HEAD_SLOT:
+                        w.d_offsets = None
                     w.d_image = self.B0[sample].data_ptr() + 4 * 32 * slot
                     w.d_workspace = st["ws_slots"][slot].data_ptr()
                     w.d_occupancy = self.occ0[sample].data_ptr() if slot == self.HEAD_SLOT else None
             status = self.lib.himo_pillarize_multi_ex(len(arr), ctypes.addressof(arr), self._range, self._voxel, self._centre, self.W, self.H,
                                                       self.p["pfn.weight"].data_ptr(), self.p["pfn.scale"].data_ptr(),
                                                       self.p["pfn.shift"].data_ptr(), 32 * self.F, self._pt[0]["ws_slots"][0].numel(),
-                                                      (1 if self.split_acts else 0) | (2 if self.incremental_images else 0), _lib.stream_handle())
+                                                      (1 if self.split_acts else 0) | (2 if self.incremental_images else 0) |
+                                                      (PILLAR_NO_LISTS if lean else 0), _lib.stream_handle())
             _lib.check(status, "himo_pillarize_multi_ex")
 
     def pillar_features(self, sweeps, transforms, scale: torch.Tensor, shift: torch.Tensor):

@@ -605,6 +605,13 @@ int himo_pillarize_multi(int n_sweeps, const himo_sweep* h_sweeps, const float* 
  * previous call"; an empty cell that was empty then is already zero and is skipped -- two thirds of the zero rows of a
  * 120k-point sweep.  Contract: himo_pillar_occupancy_reset() once after allocating the workspace / image (marks every cell
  * dirty), and nobody else writes this sweep's image channels in between.
+ * bit 2 (HIMO_PILLAR_NO_LISTS): nobody reads the per-cell ascending point lists of the workspace after this call (the training
+ * backward pass and himo_head_scatter do; inference does not), so they need not be left there -- the workspace is still written.
+ * With it a sweep may pass d_offsets == NULL and then gets no offsets written, by any kernel; d_xyz_t and d_pid stay required.
+ * Without the bit a NULL d_offsets with n > 0 is refused as in himo_pillarize (step 1).  Every other output keeps its bits.
+ * bit 3 (HIMO_PILLAR_HALFWAVE_ONLY): every non-empty cell takes the feature kernel's half-wave path (32 lanes = 32 channels per
+ * cell) instead of one lane per cell for the cells of few points; same bits either way -- an A/B and test switch.
+ * himo_pillarize and himo_pillarize_multi pass 0 for both.
  * Refusals of the multi-sweep forms (himo_pillar_features_multi included), in the order they are checked, nothing launched:
  *   1. HIMO_ERR_INVALID_ARGUMENT  n_sweeps outside [1, 12], h_sweeps NULL (himo_pillar_features_multi: d_scale / d_shift NULL);
  *                                 HIMO_IMAGE_SPLIT with image_pitch not a multiple of 16 or a sweep's d_image not 64-byte
@@ -616,6 +623,8 @@ int himo_pillarize_multi(int n_sweeps, const himo_sweep* h_sweeps, const float* 
  * 1,048,576 cells, HIMO_ERR_INVALID_ARGUMENT for a workspace shorter than the occupancy words; in that order. */
 #define HIMO_IMAGE_SPLIT 1
 #define HIMO_IMAGE_INCREMENTAL 2
+#define HIMO_PILLAR_NO_LISTS 4
+#define HIMO_PILLAR_HALFWAVE_ONLY 8
 int himo_pillar_occupancy_reset(void* d_workspace, size_t workspace_bytes, int grid_w, int grid_h, void* stream);
 int himo_pillarize_multi_ex(int n_sweeps, const himo_sweep* h_sweeps, const float* h_range, const float* h_voxel,
                          const float* h_centre_offset, int grid_w, int grid_h, const float* d_pfn_weight,
