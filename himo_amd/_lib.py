@@ -88,6 +88,11 @@ SIGNATURES = {
     "himo_raymap_carve": (c_int, [c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "himo_raymap_query": (c_int, [c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "himo_raymap_status": (c_int, [c_void_p]),
+    "himo_accum_table_bytes": (c_size_t, [c_int64]),
+    "himo_accum_clear": (c_int, [c_void_p, c_int64, c_void_p]),
+    "himo_accum_insert": (c_int, [c_int64, c_void_p, c_int, c_void_p, ctypes.POINTER(c_float), c_int, c_void_p, c_void_p, c_int64, c_void_p]),
+    "himo_accum_emit": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "himo_accum_status": (c_int, [c_void_p]),
     "himo_render_clear": (c_int, [c_void_p, c_int, c_int, c_void_p]),
     "himo_render_splat": (c_int, [c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, ctypes.c_uint32, c_void_p, c_void_p]),
     "himo_render_resolve": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),

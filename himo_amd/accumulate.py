@@ -1,0 +1,404 @@
+"""Multi-sweep accumulation: the compensated sweeps ``t - window .. t`` of a scene moved into the frame of sweep ``t`` and reduced to
+one centroid per occupied voxel, each carrying the least time lag of its rows -- the input TransFusion-L (nuScenes style) and the
+WaffleIron runs of the reference's ``downstream/README.md`` consume, and, with ground and dynamic rows skipped, a static cloud for
+mapping.  ``comp_dis`` matters most here: an uncompensated vehicle is laid over itself once per sweep.
+
+PARITY UNPINNED.  The reference has no such program in its tree (``h5sf.py`` and ``eval_h5.py`` live in absent forks).  This stage
+follows the build's own written rule, below, and is checked bit for bit against a numpy restatement of it
+(``tests/accumulate_ref.py``), never against the reference.
+
+The rule -- "sweep accumulation, v1" (normative)
+================================================
+All float arithmetic rounds after every operation (``himo_amd/csrc/accumulate.hip`` is built with ``-ffp-contract=off``; the two
+fused multiply-adds of rule B are written as such); everything after rule C is integer, so the result does not depend on the order
+in which rows arrive.
+
+Parameters (``AccumParams``, mirrored as ``himo_accum_params``): grid minimum ``(x0, y0, z0)`` (-51.2, -51.2, -3.0), ``voxel`` 0.1 m,
+``nx, ny, nz`` 1024, 1024, 80, the ego box ``ego_min``, ``ego_max`` (``compdis.EGO_BOX`` of the data set).  The struct carries
+``scale = (float)(256.0 / voxel)``, computed in double on the host, as ``RaymapParams`` does.  Admitted: every float finite,
+voxel > 0, scale equal to that expression and finite, 1 <= nx, ny <= 4096, 1 <= nz <= 256; anything else is refused with a non-zero
+status and no launch.  A voxel key is ``(iz << 24) | (iy << 12) | ix``, 32 bits.
+
+A. Input rows.  A source sweep is ``float[n][pitch]``, pitch 3 or 4 (x, y, z first), with an optional skip byte per row, a row-major
+   4x4 float32 transform ``T`` from the source's frame to the target's and an integer ``lag`` in 0..255.  A row takes part iff its skip
+   byte is 0, its three coordinates are finite, and it is not strictly inside the ego box: the six strict inequalities of
+   ``utils.ego_pts_mask``, tested on the row as given (in the SOURCE's frame: the vehicle's own returns, wherever it was).
+B. Move.  ``q = R p + t`` with the arithmetic of ``himo_rigid_transform`` -- one device function for both (``csrc/rigid_math.h``):
+   ``q0 = fma(z, T02, fma(y, T01, x * T00)) + T03``, ``q1 = fma(z, T12, fma(x, T10, y * T11)) + T13``,
+   ``q2 = fma(z, T22, fma(x, T20, y * T21)) + T23``; a product, two fused multiply-adds and a sum, each rounding once.
+C. Quantise: raymap rule A on this grid.  ``f = (c - m) * scale``; the row is unusable if any ``f`` is non-finite or
+   ``|f| >= 4194304.0f``; ``u = (int)floorf(f)``, the voxel index is ``u >> 8`` and the sub-voxel offset ``u & 255``.  A row whose voxel
+   is outside ``[0, n)`` on any axis is dropped.
+D. Reduce.  Every occupied voxel carries ``count`` (its rows), ``Sx, Sy, Sz`` (the integer sums of their sub-voxel offsets) and
+   ``lag`` (the least lag of its rows).  Successive insert calls accumulate until the table is cleared.  At most 2^24 rows may be
+   inserted between two clears, so that the 32-bit sums cannot overflow (255 * 2^24 < 2^32); ``Accumulator`` counts them and refuses
+   more.
+E. Emit.  One output row per occupied voxel, in ascending key order.  The centroid per axis in float64, every operation rounding on
+   its own, then one rounding to float32:
+   ``x = (float)((double)x0 + (((double)(256 * ix) + 0.5) + (double)Sx / (double)count) * ((double)voxel / 256.0))`` with ``x0`` and
+   ``voxel`` the float32 values of the struct; beside it ``lag`` (uint8), ``count`` (int32) and the key.  (``voxel`` 1, minimum 0, one
+   point at 0.5: ``u = 128``, ``x = 0.501953125``.)
+G. The cloud of a target sweep ``t`` of a scene (``accumulate_target``).  The sources are the sweeps ``k = max(0, t - window) .. t``
+   of the same scene, ``0 <= window <= 31``.  Source ``k`` is moved with ``T = inv(pose_t) @ pose_k``, computed in float64 on the host
+   and rounded to float32 (as raymap rule G), and inserted with ``lag = t - k``.  The table's capacity is the next power of two at or
+   above twice the window's row count (16 at least).
+
+The container is an open-addressing hash table in device memory (``himo_accum_*`` in include/himo_amd.h; the layout and the hash are
+in the header of the ``.hip`` file).  Its probe loop is bounded: a table too small for the voxels offered is a refusal reported by
+``himo_accum_status`` -- ``Accumulator.result`` raises ``ValueError`` -- never a hang.  The ascending-key order is a ``torch.sort`` of
+the emitted key column and gathers by its permutation: rows are moved, no arithmetic is done on point data in Python.
+
+The program: ``python -m himo_amd.accumulate --data_dir D --out_dir O [--res_name seflowpp_best | raw] [--window 10] [--voxel 0.1]
+[--drop_ground] [--drop_label KEY] [--data_name av2|scania] [--overwrite]``.  For every scene file of ``D`` the targets are the sweeps
+that have a successor (their flow is defined).  Source ``k`` is compensated by the pinned path, ``CompDisEngine.run_frame(...,
+refined=True)`` with the stored ``<res_name>`` (``raw``: the points as recorded; a missing key is the ``KeyError`` the other programs
+raise), then rule G.  ``--drop_ground`` skips rows whose ``ground_mask`` is set, ``--drop_label KEY`` rows whose stored integer label
+``KEY`` (``ray_label``, say) is non-zero: together a static, ground-free cloud; a missing mask or label is a ``KeyError`` naming the
+program that writes it.  Output: ``O/<scene>.h5`` (refused if it exists, without ``--overwrite``) and ``O/index_total.pkl``, ordinary
+scene files the package's loader reads; per target ``<timestamp>/lidar`` float32 [M, 4] (x, y, z, ``lag * 0.1`` s),
+``<timestamp>/pose`` (the target's, bytes unchanged), ``<timestamp>/lidar_dt`` (zeros [M]: an accumulated cloud is already
+compensated) and ``<timestamp>/acc_count`` int32 [M]; beside them ``<timestamp>/ground_mask``, all False (v1 marks no centroid as
+ground; the viewer and the evaluators ask every sweep for a mask).  ``python -m himo_amd.view --data_dir O --res_names raw --color_by
+label:acc_count`` shows such a cloud coloured by rows per voxel (the default ``--color_by lidar`` wants a ``lidar_id`` per point, which
+a centroid has not).
+Under ``torchrun`` the scenes are dealt round-robin to the ranks.  There is no CPU path.
+
+Not part of v1: moving dynamic points along their flow to the target's time; intensity or any other per-point attribute in the
+output; future sweeps as sources; a map that persists along a drive; a world-frame output; an in-line switch of ``save``.
+"""
+from __future__ import annotations
+
+import ctypes
+import time
+from pathlib import Path
+
+import numpy as np
+
+MAX_WINDOW = 31
+MAX_ROWS = 1 << 24                  # rule D: rows between two clears
+MIN_CAPACITY, MAX_CAPACITY = 1 << 4, 1 << 26
+LAG_SECONDS = 0.1                   # the sweep period the lag column is written in
+
+
+class AccumParams(ctypes.Structure):
+    """mirror of ``himo_accum_params`` (include/himo_amd.h); ``scale`` follows from ``voxel``.  ``check()`` raises for what the library
+    refuses."""
+    _fields_ = [("x0", ctypes.c_float), ("y0", ctypes.c_float), ("z0", ctypes.c_float), ("voxel", ctypes.c_float), ("scale", ctypes.c_float),
+                ("nx", ctypes.c_int32), ("ny", ctypes.c_int32), ("nz", ctypes.c_int32), ("ego_min", ctypes.c_float * 3),
+                ("ego_max", ctypes.c_float * 3)]
+
+    def __init__(self, x0=-51.2, y0=-51.2, z0=-3.0, voxel=0.1, nx=1024, ny=1024, nz=80, ego_min=None, ego_max=None, data_name="av2"):
+        from .compdis import EGO_BOX
+        lo, hi = EGO_BOX["scania" if data_name == "scania" else "av2"]
+        v = float(np.float32(voxel))
+        with np.errstate(all="ignore"):
+            scale = float(np.float32(np.float64(256.0) / np.float64(v))) if v != 0.0 else float("inf")
+        three = lambda a: (ctypes.c_float * 3)(*[float(x) for x in a])        # noqa: E731
+        super().__init__(x0, y0, z0, voxel, scale, nx, ny, nz, three(lo if ego_min is None else ego_min), three(hi if ego_max is None else ego_max))
+
+    def check(self) -> "AccumParams":
+        floats = [self.x0, self.y0, self.z0, self.voxel, self.scale, *self.ego_min, *self.ego_max]
+        ok = all(np.isfinite(f) for f in floats) and self.voxel > 0
+        if ok:
+            with np.errstate(all="ignore"):
+                ok = np.float32(self.scale) == np.float32(np.float64(256.0) / np.float64(np.float32(self.voxel)))
+        ok = ok and 1 <= self.nx <= 4096 and 1 <= self.ny <= 4096 and 1 <= self.nz <= 256
+        if not ok:
+            raise ValueError("accumulate: parameters outside finite floats, voxel > 0, scale == (float)(256.0 / voxel), 1 <= nx, ny <= 4096, "
+                             "1 <= nz <= 256")
+        return self
+
+
+def capacity_for(rows: int) -> int:
+    """rule G: the next power of two at or above twice ``rows``, inside what the library admits"""
+    cap = MIN_CAPACITY
+    while cap < 2 * int(rows) and cap < MAX_CAPACITY:
+        cap <<= 1
+    return cap
+
+
+def sources(t: int, n_sweeps: int, window: int = 10) -> list:
+    """rule G: the source sweeps of target ``t``, oldest first"""
+    if not 0 <= int(window) <= MAX_WINDOW:
+        raise ValueError(f"window={window}: 0..{MAX_WINDOW}")
+    if not 0 <= t < n_sweeps:
+        raise IndexError(f"target sweep {t} of {n_sweeps}")
+    return list(range(max(0, t - int(window)), t + 1))
+
+
+class Accumulator:
+    """A voxel table on ``device``: ``clear()``, ``add(points, T, lag, skip=None)`` any number of times, ``result()``.  ``capacity``: a
+    power of two in 2^4 .. 2^26, at least the number of voxels that will be occupied (``capacity_for``).  Everything is asynchronous on
+    the current stream but ``result()``, which waits once."""
+
+    def __init__(self, device=None, params: AccumParams | None = None, capacity: int = 1 << 22):
+        import torch
+        from . import _lib
+        self.params = (params if params is not None else AccumParams()).check()
+        self.lib = _lib.load()
+        self.capacity = int(capacity)
+        nbytes = int(self.lib.himo_accum_table_bytes(self.capacity))
+        if nbytes == 0:
+            raise ValueError(f"accumulate: capacity {capacity} is not a power of two in 2^4 .. 2^26")
+        self.device = device if device is not None else _lib.require_gpu()
+        self.table = torch.empty(nbytes // 4, dtype=torch.int32, device=self.device)
+        self._n_rows = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._host = _lib.pinned_empty(1, torch.int32)
+        self.rows = 0
+        self.clear()
+
+    def clear(self) -> None:
+        from . import _lib
+        _lib.check(self.lib.himo_accum_clear(_lib.ptr(self.table), self.capacity, _lib.stream_handle()), "himo_accum_clear")
+        self.rows = 0
+
+    def add(self, points, T, lag: int, skip=None) -> None:
+        """insert one source sweep: ``points`` device float32 [n, 3 or 4] in its own frame, ``T`` its 4x4 transform into the target's
+        frame (rounded to float32 here), ``lag`` 0..255, ``skip`` device uint8 / bool [n] (non-zero = the row takes no part)"""
+        import torch
+        from . import _lib
+        if points.dim() != 2 or points.shape[1] not in (3, 4) or points.dtype != torch.float32 or not points.is_contiguous():
+            raise ValueError(f"points are contiguous float32 rows of 3 or 4 columns, not {tuple(points.shape)} {points.dtype}")
+        n = int(points.shape[0])
+        if skip is not None:
+            skip = skip.to(torch.uint8).contiguous()
+            if skip.shape != (n,):
+                raise ValueError(f"skip is [{n}], not {tuple(skip.shape)}")
+        if self.rows + n > MAX_ROWS:
+            raise ValueError(f"accumulate: {self.rows} + {n} rows since the last clear() exceed 2^24 (the 32-bit sums of rule D)")
+        T32 = np.ascontiguousarray(np.asarray(T).astype(np.float32)).reshape(16)
+        st = self.lib.himo_accum_insert(n, _lib.ptr(points), int(points.shape[1]), _lib.ptr(skip), T32.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+                                        int(lag), ctypes.addressof(self.params), _lib.ptr(self.table), self.capacity, _lib.stream_handle())
+        _lib.check(st, "himo_accum_insert")
+        self.rows += n
+
+    def result(self):
+        """(xyz float32 [M, 3], lag uint8 [M], count int32 [M], keys int64 [M]): device tensors, one row per occupied voxel in
+        ascending key order.  Waits for the stream once, for the row count and the status; raises ValueError if the table was full."""
+        import torch
+        from . import _lib
+        room = min(self.rows, self.capacity + 1)
+        dev = self.device
+        keys = torch.empty(room, dtype=torch.int32, device=dev)
+        xyz = torch.empty((room, 3), dtype=torch.float32, device=dev)
+        lag = torch.empty(room, dtype=torch.uint8, device=dev)
+        count = torch.empty(room, dtype=torch.int32, device=dev)
+        st = self.lib.himo_accum_emit(_lib.ptr(self.table), self.capacity, ctypes.addressof(self.params), room, _lib.ptr(self._n_rows),
+                                      _lib.ptr(keys) if room else None, _lib.ptr(xyz) if room else None, _lib.ptr(lag) if room else None,
+                                      _lib.ptr(count) if room else None, _lib.stream_handle())
+        _lib.check(st, "himo_accum_emit")
+        self._host.copy_(self._n_rows, non_blocking=True)
+        _lib.check(self.lib.himo_accum_status(_lib.stream_handle()),                      # (waits for the stream: the count has arrived too)
+                   f"himo_accum_insert: the table of capacity {self.capacity} was full")
+        m = int(self._host[0])
+        keys64 = keys[:m].to(torch.int64) & 0xFFFFFFFF
+        keys64, order = torch.sort(keys64)
+        return xyz[:m][order], lag[:m][order], count[:m][order], keys64
+
+
+def _device_rows(pc, dev):
+    import torch
+    t = pc if isinstance(pc, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(pc, dtype=np.float32))
+    if t.dim() != 2 or t.shape[1] < 3:
+        raise ValueError(f"points are rows of x, y, z[, ...], not {tuple(t.shape)}")
+    t = t.to(device=dev, dtype=torch.float32)
+    return t.contiguous() if t.shape[1] in (3, 4) else t[:, :3].contiguous()
+
+
+def accumulate_target(sweeps, poses, t: int, window: int = 10, params: AccumParams | None = None, skips=None, acc: Accumulator | None = None):
+    """Rule G for target sweep ``t`` of one scene: what ``Accumulator.result`` returns.  ``sweeps``: the scene's (compensated) sweeps in
+    order, (n, >= 3) float32 arrays or device tensors in their own frames (only the sources are touched); ``poses``: their 4x4 world
+    poses; ``skips``: per sweep None or a uint8 / bool mask of rows to leave out; ``acc``: a table to clear and use (its capacity must
+    do), else one of ``capacity_for`` the window's rows."""
+    import torch
+    from . import _lib
+    dev = acc.device if acc is not None else _lib.require_gpu()
+    src = sources(int(t), len(sweeps), window)
+    pts = {k: _device_rows(sweeps[k], dev) for k in src}
+    if acc is None:
+        acc = Accumulator(dev, params, capacity_for(sum(int(p.shape[0]) for p in pts.values())))
+    else:
+        acc.clear()
+    inv_t = np.linalg.inv(np.asarray(poses[t], dtype=np.float64))
+    for k in src:
+        T = (inv_t @ np.asarray(poses[k], dtype=np.float64)).astype(np.float32)
+        s = None if skips is None or skips[k] is None else skips[k]
+        if s is not None and not isinstance(s, torch.Tensor):
+            s = torch.from_numpy(np.ascontiguousarray(s).astype(np.uint8))
+        acc.add(pts[k], T, t - k, None if s is None else s.to(dev))
+    return acc.result()
+
+
+# --------------------------------------------------------------------------------------------------------------------------
+# the program
+# --------------------------------------------------------------------------------------------------------------------------
+def _writers(key: str) -> str:
+    return "`python -m himo_amd.ground_seg` writes the masks" if key == "ground_mask" else \
+        "`python -m himo_amd.raymap` writes ray_label / ray_dynamic"
+
+
+def accumulate_scene(dataset, items: list, out_path, res_name: str = "seflowpp_best", window: int = 10, params: AccumParams | None = None,
+                     drop_ground: bool = False, drop_label: str | None = None, opener=None) -> dict:
+    """One scene: ``items`` are the dataset's indices of its sweeps that have a successor, in order (the targets, and the sources).
+    Compensates every sweep once, accumulates every target, then writes ``out_path``.  Returns {"sweeps", "rows_in", "rows_out",
+    "seconds"} (seconds: upload, compensation, accumulation and the copy back; no file time)."""
+    import torch
+    from . import _lib
+    from .compdis import CompDisEngine
+    params = (params if params is not None else AccumParams()).check()
+    sources(0, 1, window)
+    dev = _lib.require_gpu()
+    frames = [dataset[i] for i in items]
+    scene = frames[0]["scene_id"] if frames else Path(out_path).stem
+    for f in frames:
+        if res_name != "raw" and res_name not in f:
+            raise KeyError(res_name)                                              # as save_zip / eval on a scene without the result
+        if drop_ground and "gm0" not in f:
+            raise KeyError(f"ground_mask: {scene} sweep {f['timestamp']} has no ground mask ({_writers('ground_mask')})")
+        if drop_label and drop_label not in f:
+            raise KeyError(f"{drop_label}: {scene} sweep {f['timestamp']} has no such label ({_writers(drop_label)})")
+    t0 = time.perf_counter()
+    out, rows_in = [], 0
+    with torch.cuda.device(dev):
+        engine = CompDisEngine()
+        moved, skips = [], []
+        for f in frames:
+            pc0 = _device_rows(f["pc0"], dev)
+            if res_name == "raw":
+                moved.append(pc0)
+            else:
+                flow = torch.from_numpy(np.ascontiguousarray(f[res_name], dtype=np.float32)).to(dev)
+                dt = torch.from_numpy(np.ascontiguousarray(f["lidar_dt"], dtype=np.float32)).to(dev)
+                moved.append(engine.run_frame(pc0, flow, dt, f["pose0"], f["pose1"], refined=True)[1])
+            skip = None
+            if drop_ground:
+                skip = torch.from_numpy(np.ascontiguousarray(f["gm0"]).astype(np.uint8)).to(dev)
+            if drop_label:
+                lab = torch.from_numpy(np.ascontiguousarray(np.asarray(f[drop_label]) != 0).astype(np.uint8)).to(dev)
+                skip = lab if skip is None else skip | lab
+            skips.append(skip)
+        poses = [np.asarray(f["pose0"]) for f in frames]
+        most = max((sum(int(moved[k].shape[0]) for k in sources(t, len(frames), window)) for t in range(len(frames))), default=0)
+        acc = Accumulator(dev, params, capacity_for(most))
+        for t in range(len(frames)):
+            xyz, lag, count, _ = accumulate_target(moved, poses, t, window, skips=skips, acc=acc)
+            rows_in += acc.rows
+            out.append((xyz.cpu().numpy(), lag.cpu().numpy(), count.cpu().numpy()))
+    seconds = time.perf_counter() - t0
+    if opener is None:
+        from .save import h5_writer
+        mod, how = h5_writer()
+        if mod is None:
+            raise RuntimeError(f"{out_path}: writing a scene file needs an HDF5 library (h5py, or libhdf5 for himo_amd.h5c; HIMO_LIBHDF5 names one): {how}")
+        opener = lambda p: mod.File(p, "a")                                   # noqa: E731
+    with opener(out_path) as h:
+        for f, (xyz, lag, count) in zip(frames, out):
+            g = h.create_group(str(f["timestamp"]))
+            lidar = np.empty((len(xyz), 4), dtype=np.float32)
+            lidar[:, :3], lidar[:, 3] = xyz, lag.astype(np.float32) * np.float32(LAG_SECONDS)
+            g.create_dataset("lidar", data=lidar)
+            g.create_dataset("pose", data=np.asarray(f["pose0"]))
+            g.create_dataset("lidar_dt", data=np.zeros(len(xyz), dtype=np.float32))
+            g.create_dataset("acc_count", data=count.astype(np.int32))
+            g.create_dataset("ground_mask", data=np.zeros(len(xyz), dtype=bool))    # no centroid is marked: the viewer and the evaluators ask for a mask
+    return {"sweeps": len(frames), "rows_in": rows_in, "rows_out": int(sum(len(o[0]) for o in out)), "seconds": seconds}
+
+
+def _write_index(out_dir: Path, entries: list) -> None:
+    """``index_total.pkl`` of the output directory: what it held for other scenes, then ``entries``"""
+    import pickle
+    path = out_dir / "index_total.pkl"
+    mine = {s for s, _ in entries}
+    kept = []
+    if path.exists():
+        with open(path, "rb") as fh:
+            kept = [[str(s), str(t)] for s, t in pickle.load(fh) if str(s) not in mine]
+    with open(path, "wb") as fh:
+        pickle.dump(sorted(kept + [[s, t] for s, t in entries], key=lambda e: (e[0], int(e[1]))), fh)
+
+
+def main(data_dir: str, out_dir: str, res_name: str = "seflowpp_best", window: int = 10, voxel: float = 0.1, drop_ground: bool = False,
+         drop_label: str | None = None, data_name: str = "av2", overwrite: bool = False, params: AccumParams | None = None) -> dict:
+    """The program.  Under ``torchrun`` (one rank per GPU) the scenes are dealt round-robin to the ranks, so every file has one writer;
+    rank 0 writes the index once every rank is through.  Returns {scene: what ``accumulate_scene`` returned} of this rank."""
+    import warnings
+    from . import distenv
+    from .dataset import HDF5Dataset
+    from .save import h5_writer
+    if data_name not in ("av2", "scania"):
+        raise ValueError(f"data_name={data_name!r}: av2 or scania")
+    if params is None:
+        # the default grid's extent at any voxel size: 102.4 x 102.4 x 8 m
+        v = float(voxel)
+        cells = lambda extent, top: max(1, min(top, int(round(extent / v)))) if v > 0 and np.isfinite(v) else 0      # noqa: E731
+        params = AccumParams(voxel=v, nx=cells(102.4, 4096), ny=cells(102.4, 4096), nz=cells(8.0, 256), data_name=data_name)
+    params.check()
+    sources(0, 1, window)
+    if not sorted(Path(data_dir).glob("*.h5")):
+        raise FileNotFoundError(f"{data_dir}: no <scene>.h5 files")
+    mod, how = h5_writer()
+    if mod is None:
+        raise RuntimeError(f"writing scene files into {out_dir} needs an HDF5 library (h5py, or libhdf5 for himo_amd.h5c; HIMO_LIBHDF5 names "
+                           f"one): {how}")
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    fields = {"pc0", "pose0", "pose1", "lidar_dt"} | ({"gm0"} if drop_ground else set()) | ({drop_label} if drop_label else set())
+    fields |= {res_name} if res_name != "raw" else set()
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")                                       # (the last sweep of a scene has no successor: no target)
+        ds = HDF5Dataset(data_dir, vis_name=[res_name] if res_name != "raw" else "", fields=tuple(fields))
+    by_scene: dict = {}
+    for i, (s, _) in enumerate(ds.index):
+        by_scene.setdefault(s, []).append(i)
+    scenes = sorted(by_scene)
+    have = [s for s in scenes if (out_dir / f"{s}.h5").exists()]
+    if have and not overwrite:
+        ds.close()
+        raise FileExistsError(f"{out_dir}: {len(have)} of {len(scenes)} scene files exist already, {have[0]}.h5 among them (--overwrite replaces them)")
+    done = {}
+    with distenv.process_group() as (rank, world):
+        err = None
+        try:
+            for s in scenes[rank::world]:
+                path = out_dir / f"{s}.h5"
+                if path.exists():
+                    path.unlink()                                             # --overwrite: the file is written anew
+                r = done[s] = accumulate_scene(ds, by_scene[s], path, res_name, window, params, drop_ground, drop_label,
+                                               opener=lambda p: mod.File(p, "a"))
+                rate = r["sweeps"] / r["seconds"] if r["seconds"] > 0 else float("inf")
+                print(f"{s}: {r['sweeps']} sweeps, {r['rows_in']} rows in, {r['rows_out']} rows out  ({rate:.1f} sweeps/s)")
+        except Exception as e:                                                # arrive at the rendezvous anyway, then re-raise
+            err = e
+        finally:
+            ds.close()
+        distenv.rendezvous(err, "its scene files")
+        if rank == 0:
+            _write_index(out_dir, [[s, t] for s, t in ds.index])
+    return done
+
+
+def _parser():
+    import argparse
+    ap = argparse.ArgumentParser(description="accumulate the compensated sweeps t - window .. t of every scene into the frame of sweep t, one "
+                                             "centroid per voxel (sweep accumulation, v1; parity unpinned: the reference has no such program; "
+                                             "MI355X path)")
+    ap.add_argument("--data_dir", required=True, help="directory of <scene>.h5 files and index_total.pkl")
+    ap.add_argument("--out_dir", required=True, help="directory the accumulated <scene>.h5 files and their index_total.pkl are written to")
+    ap.add_argument("--res_name", default="seflowpp_best", help="the stored flow the sweeps are compensated by; raw = the points as recorded")
+    ap.add_argument("--window", type=int, default=10, help=f"past sweeps beside the target (0..{MAX_WINDOW})")
+    ap.add_argument("--voxel", type=float, default=0.1, help="voxel edge [m] of the 102.4 x 102.4 x 8 m grid")
+    ap.add_argument("--drop_ground", action="store_true", help="leave out rows whose ground_mask is set (python -m himo_amd.ground_seg)")
+    ap.add_argument("--drop_label", default=None, metavar="KEY", help="leave out rows whose stored integer label KEY is non-zero (ray_label: "
+                                                                      "python -m himo_amd.raymap)")
+    ap.add_argument("--data_name", default="av2", choices=("av2", "scania"), help="whose ego box is cut out of every source sweep")
+    ap.add_argument("--overwrite", action="store_true", help="replace scene files that exist in --out_dir instead of refusing")
+    return ap
+
+
+def _cli(argv=None):
+    a = _parser().parse_args(argv)
+    main(a.data_dir, a.out_dir, a.res_name, a.window, a.voxel, a.drop_ground, a.drop_label, a.data_name, a.overwrite)
+
+
+if __name__ == "__main__":
+    _cli()

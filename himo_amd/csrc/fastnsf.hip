@@ -18,6 +18,7 @@
 //   chamfer_trunc_*        the objective and its gradient with respect to the moved points.
 #include "himo_common.h"
 #include "adam.h"
+#include "rigid_math.h"
 #include <math.h>
 
 namespace himo {
@@ -639,14 +640,16 @@ __global__ __launch_bounds__(256) void chamfer_trunc_b_kernel(ChamferArgs a, int
     block_sum1(t, a.partial + blocks0 + blockIdx.x);
 }
 
-// p' = R p + t with separately rounded products and sums (the rule of seflow/spec.py step 0); out pitch >= 3, tail zeroed
+// p' = R p + t by rigid_apply (rigid_math.h: the operation sequence this kernel has always compiled to, now written out and
+// shared with accumulate.hip); out pitch >= 3, tail zeroed
 __global__ __launch_bounds__(256) void rigid_kernel(int64_t n, const float* __restrict__ p, int stride, const float* __restrict__ T,
                                                     float* __restrict__ y, int y_pitch) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const float x = p[i * stride], yy = p[i * stride + 1], z = p[i * stride + 2];
+    float q[3];
+    rigid_apply(T, p[i * stride], p[i * stride + 1], p[i * stride + 2], q);
 #pragma unroll
-    for (int r = 0; r < 3; ++r) y[i * y_pitch + r] = ((x * T[r * 4] + yy * T[r * 4 + 1]) + z * T[r * 4 + 2]) + T[r * 4 + 3];
+    for (int r = 0; r < 3; ++r) y[i * y_pitch + r] = q[r];
     for (int c = 3; c < y_pitch; ++c) y[i * y_pitch + c] = 0.f;
 }
 

@@ -47,8 +47,9 @@ pinhole with a vertical field of view.  ``Camera.from_view`` takes the four quan
 convention is not claimed.  ``spline_path`` is the clamped cubic spline through keyframes that ``interpolate_trajectory``
 (tools/animation_video.py:32) describes, in numpy.
 
-Not built: text in the image, video encoding, boxes or meshes, an interactive window, accumulation of many sweeps in the world
-frame (``index_base`` allows it; the program does not offer it), per-instance scores in the panel (``himo_amd.eval`` prints those).
+Not built: text in the image, video encoding, boxes or meshes, an interactive window, per-instance scores in the panel
+(``himo_amd.eval`` prints those).  Many sweeps in one frame are a stage of their own: ``python -m himo_amd.accumulate`` writes them as
+scene files, which ``--data_dir O --res_names raw`` then shows.
 """
 from __future__ import annotations
 

@@ -391,6 +391,52 @@ int himo_raymap_query(int64_t n, const float* d_pts, int pitch, const unsigned c
 int himo_raymap_status(void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Multi-sweep accumulation: several compensated sweeps moved into one target frame and reduced to one centroid per occupied voxel,
+ * each with the least time lag of its rows (himo_amd/csrc/accumulate.hip).  The reference has no such program in its tree, so this
+ * stage follows the build's own written rule, "sweep accumulation, v1" (the module docstring of himo_amd/accumulate.py is
+ * normative): PARITY UNPINNED.
+ *   rows      a source row takes part iff its skip byte is 0, its x, y, z are finite and it is not strictly inside the ego box
+ *             (six strict inequalities on the row as given)
+ *   move      q = R p + t, the arithmetic of himo_rigid_transform (csrc/rigid_math.h), with the transform passed by value
+ *   quantise  f = (c - min) * scale (float32, two operations), scale = (float)(256.0 / voxel); unusable when an f is not finite or
+ *             |f| >= 2^22; u = (int)floorf(f), voxel index u >> 8, sub-voxel offset u & 255; a voxel outside [0, n) is dropped
+ *   reduce    per occupied voxel, key (iz << 24) | (iy << 12) | ix: count, the integer sums Sx, Sy, Sz of the offsets, the least
+ *             lag.  Insert calls accumulate until the table is cleared; at most 2^24 rows between two clears (the caller counts)
+ *   emit      x = (float)((double)x0 + (((double)(256 * ix) + 0.5) + (double)Sx / (double)count) * ((double)voxel / 256.0)), every
+ *             operation rounding on its own; beside it lag (uint8), count (int32) and the key (uint32); rows in ANY order
+ * The table is an open-addressing hash table in device memory that the caller owns: himo_accum_table_bytes(capacity) bytes,
+ * 16-byte aligned, capacity a power of two in 2^4 .. 2^26.  Only 32-bit integer atomics touch it, so the rows emitted after
+ * equal calls, sorted by key, are the same bytes on every run (which slot a key sits in is not fixed).  The probe loop is bounded by the capacity: a row that finds every slot taken by other
+ * keys is left out and recorded in a flag word of the device; himo_accum_status(stream) waits for `stream`, returns
+ * HIMO_ERR_INVALID_ARGUMENT when an insert on the current device found the table full since the last himo_accum_status, and
+ * clears the flag (the insert itself is asynchronous and returns HIMO_OK).
+ * d_pts: float[n][pitch], pitch 3 or 4 (x, y, z first) in the source's frame; d_skip: uint8[n] or NULL; h_transform: 16 HOST
+ * floats, row-major 4x4, source frame -> target frame; lag: 0..255.  himo_accum_emit writes min(rows, max_rows) rows to d_keys
+ * uint32[max_rows], d_xyz float[max_rows][3], d_lag uint8[max_rows], d_count int32[max_rows], and the full number of occupied
+ * voxels to d_n_rows (int32[1]) even when it exceeds max_rows.
+ * Refused with HIMO_ERR_INVALID_ARGUMENT, nothing launched and nothing written: n < 0, a pitch other than 3 or 4, lag outside
+ * 0..255, max_rows < 0, NULL where data is required, d_pts / d_n_rows / d_keys / d_xyz / d_count not 4-byte or the table not 16-byte
+ * aligned, a refused capacity (himo_accum_table_bytes returns 0 for it) and parameters outside: every float finite, voxel > 0,
+ * scale == (float)(256.0 / voxel) and finite, 1 <= nx, ny <= 4096, 1 <= nz <= 256.  n > 2^31 - 1: HIMO_ERR_UNSUPPORTED.  n == 0:
+ * HIMO_OK without a launch. */
+typedef struct himo_accum_params {
+    float x0, y0, z0;      /* grid minimum */
+    float voxel;           /* voxel edge, m */
+    float scale;           /* (float)(256.0 / voxel), the division in double */
+    int32_t nx, ny, nz;
+    float ego_min[3];      /* rows strictly inside (ego_min, ego_max) take no part */
+    float ego_max[3];
+} himo_accum_params;
+
+size_t himo_accum_table_bytes(int64_t capacity);                       /* 32 * (capacity + 1); 0 = capacity refused */
+int himo_accum_clear(void* d_table, int64_t capacity, void* stream);
+int himo_accum_insert(int64_t n, const float* d_pts, int pitch, const unsigned char* d_skip, const float* h_transform, int lag,
+                      const himo_accum_params* params, void* d_table, int64_t capacity, void* stream);
+int himo_accum_emit(const void* d_table, int64_t capacity, const himo_accum_params* params, int64_t max_rows, int32_t* d_n_rows,
+                    uint32_t* d_keys, float* d_xyz, unsigned char* d_lag, int32_t* d_count, void* stream);
+int himo_accum_status(void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The headless viewer's renderer ("point splat, v1"; csrc/render.hip; the rule is the module docstring of himo_amd/view.py and is
  * this build's own: no claim is made about the pixels of any other viewer).
  *
@@ -947,8 +993,9 @@ int himo_chamfer_trunc(int n0, int n1, const float* d_moved, const float* d_pc1,
 /* y[i][c] = a[i][c] + b_scale * b[i][c] for c < cols (b may be NULL); zero_tail clears y's columns cols..y_pitch-1 */
 int himo_rows_add(int64_t n, int cols, const float* d_a, int a_pitch, const float* d_b, int b_pitch, float b_scale,
                   float* d_y, int y_pitch, int zero_tail, void* stream);
-/* out[i][0:3] = R p_i + t with d_transform a DEVICE row-major 4x4 float32 (rounding as seflow/spec.py step 0); the rest
- * of each out row (out_pitch floats) is zeroed */
+/* out[i][0:3] = R p_i + t with d_transform a DEVICE row-major 4x4 float32; the rest of each out row (out_pitch floats) is
+ * zeroed.  Per row one rounded product, two fused multiply-adds and one rounded sum, in the order written in csrc/rigid_math.h
+ * (the sequence this entry point has always computed; himo_accum_insert moves its rows with the same function) */
 int himo_rigid_transform(int64_t n, const float* d_pts, int pc_stride, const float* d_transform, float* d_out,
                          int out_pitch, void* stream);
 
