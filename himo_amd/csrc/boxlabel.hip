@@ -113,7 +113,7 @@ __global__ __launch_bounds__(kThreads) void box_label_kernel(BoxLabelArgs a) {
     __shared__ double s_geom[kBoxChunk * kGeom];
     const int64_t bstart = (int64_t)blockIdx.x * kBlockPts;
     const int64_t bend = bstart + kBlockPts < a.total ? bstart + kBlockPts : a.total;
-    const int f0 = __builtin_amdgcn_readfirstlane(find_frame(a.offsets, a.n_frames, bstart));
+    const int f0 = __builtin_amdgcn_readfirstlane(segment_of(a.offsets, a.n_frames, bstart));
     const bool uniform = a.offsets[f0 + 1] >= bend;
     const int64_t g = bstart + (int64_t)threadIdx.x * kPtsPerThread;
 

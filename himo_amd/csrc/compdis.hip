@@ -135,7 +135,7 @@ __global__ __launch_bounds__(kPrepThreads) void frame_prep_kernel(
     }
     const int64_t start = (int64_t)b * kPrepChunk;
     const int64_t end = start + kPrepChunk < total ? start + kPrepChunk : total;
-    const int f0 = __builtin_amdgcn_readfirstlane(find_frame(offsets, n_frames, start));
+    const int f0 = __builtin_amdgcn_readfirstlane(segment_of(offsets, n_frames, start));
     const bool vec = (reinterpret_cast<uintptr_t>(lidar_dt) & 15u) == 0;
 
     float v[kPrepChunk / kPrepThreads];   // this thread's 16 elements; -inf where out of range
@@ -215,7 +215,7 @@ template <int STRIDE, bool F32>
 __global__ __launch_bounds__(kThreads) void compdis_kernel(CompdisArgs a) {
     const int64_t bstart = (int64_t)blockIdx.x * kBlockPts;
     const int64_t bend = bstart + kBlockPts < a.total ? bstart + kBlockPts : a.total;
-    const int f0 = __builtin_amdgcn_readfirstlane(find_frame(a.offsets, a.n_frames, bstart));
+    const int f0 = __builtin_amdgcn_readfirstlane(segment_of(a.offsets, a.n_frames, bstart));
     const bool uniform = a.offsets[f0 + 1] >= bend;
     const int64_t g = bstart + (int64_t)threadIdx.x * kPtsPerThread;
     if (g >= bend) return;

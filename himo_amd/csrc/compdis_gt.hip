@@ -197,7 +197,7 @@ template <int STRIDE, bool F32>
 __global__ __launch_bounds__(kThreads) void compdis_gt_kernel(GtArgs a) {
     const int64_t bstart = (int64_t)blockIdx.x * kBlockPts;
     const int64_t bend = bstart + kBlockPts < a.total ? bstart + kBlockPts : a.total;
-    const int f0 = __builtin_amdgcn_readfirstlane(find_frame(a.offsets, a.n_frames, bstart));
+    const int f0 = __builtin_amdgcn_readfirstlane(segment_of(a.offsets, a.n_frames, bstart));
     const bool uniform = a.offsets[f0 + 1] >= bend;
 
     if (!uniform) {

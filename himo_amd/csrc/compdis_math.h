@@ -3,6 +3,7 @@
 // on operation order).  Translation units including this must be built with -ffp-contract=off.
 #pragma once
 #include "himo_common.h"
+#include "blockops.h"
 #include <math.h>
 
 namespace himo {
@@ -30,16 +31,6 @@ __host__ __device__ inline size_t keys_bytes(int n_frames) {
 // ------------------------------------------------------------------------------------------
 // per-frame helpers
 // ------------------------------------------------------------------------------------------
-// largest f in [0, n_frames) with offsets[f] <= i   (i < offsets[n_frames])
-__device__ inline int find_frame(const int64_t* __restrict__ offsets, int n_frames, int64_t i) {
-    int lo = 0, hi = n_frames;   // invariant: offsets[lo] <= i < offsets[hi]
-    while (hi - lo > 1) {
-        int mid = (lo + hi) >> 1;
-        if (offsets[mid] <= i) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 struct XfRegs {   // one frame's transform + max, held in registers (SGPRs on the uniform path)
     double R[9];
     double t[3];

@@ -23,6 +23,7 @@
 // larger root under the smaller with atomicMin: a component's root ends as its lowest index, deterministically; finds halve the
 // paths they walk; one wave per point shares the walk over its neighbours); labels = find.
 #include "himo_common.h"
+#include "blockops.h"
 #include "unionfind.h"
 #include <float.h>
 #include <math.h>
@@ -62,8 +63,8 @@ __global__ __launch_bounds__(256) void db_count_kernel(int n, const float* __res
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     int c = -1;
-    const float x = xyz[(int64_t)i * pitch], y = xyz[(int64_t)i * pitch + 1], z = xyz[(int64_t)i * pitch + 2];
-    if (!(skip && skip[i]) && x == x && y == y && z == z) {                 // (NaN rows take no part)
+    if (db_takes_part(xyz, pitch, skip, i)) {
+        const float x = xyz[(int64_t)i * pitch], y = xyz[(int64_t)i * pitch + 1];
         const int cx = db_cell(x, g.x0, g.inv_cell, g.gw - 1), cy = db_cell(y, g.y0, g.inv_cell, g.gh - 1);
         c = cy * g.gw + cx;
         atomicAdd(&count[c], 1);
@@ -85,11 +86,7 @@ __global__ __launch_bounds__(1024) void db_scan_tiles_kernel(int* __restrict__ v
 #pragma unroll
     for (int k = 0; k < 4; ++k) x[k] = at + k < n ? v[at + k] : 0;
     const int mine = x[0] + x[1] + x[2] + x[3];
-    int incl = mine;
-    for (int off = 1; off < 64; off <<= 1) {
-        const int y = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += y;
-    }
+    const int incl = wave_inclusive_scan(mine);
     if (lane == 63) wsum[w] = incl;
     __syncthreads();
     int run = incl - mine, total = 0;
@@ -102,13 +99,8 @@ __global__ __launch_bounds__(1024) void db_scan_tiles_kernel(int* __restrict__ v
 __global__ __launch_bounds__(1024) void db_scan_offsets_kernel(int* __restrict__ v, int n, const int* __restrict__ tile_sum) {
     __shared__ int s_before, s_all;
     if (threadIdx.x < 64) {                                     // one wave: the tiles before this block's, and all of them (last block)
-        int before = 0, all = 0;
-        for (int t = threadIdx.x; t < (int)gridDim.x; t += 64) {
-            const int x = tile_sum[t];
-            all += x;
-            if (t < (int)blockIdx.x) before += x;
-        }
-        for (int off = 32; off; off >>= 1) { before += __shfl_xor(before, off, 64); all += __shfl_xor(all, off, 64); }
+        int before, all;
+        tiles_before_and_all(tile_sum, before, all);
         if (threadIdx.x == 0) { s_before = before; s_all = all; }
     }
     __syncthreads();

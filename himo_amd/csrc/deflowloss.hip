@@ -34,6 +34,7 @@
 // and writes 12 B: 115..131 B per row in all, against 66 B per row more for the alternative of stashing d and e as doubles
 // (33 B written and read back) -- and that form still needs the counts before it can divide.  Timing unmeasured.
 #include "himo_common.h"
+#include "blockops.h"
 #include <math.h>
 
 namespace himo {
@@ -82,17 +83,13 @@ __device__ inline double deflow_error(const DeflowArgs& a, int64_t i, const doub
     return sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
 }
 
-// sums of v[0..2] and c[0..2] over the block, valid on thread 0: butterfly inside each wave (every lane ends with the same
-// bits: the additions of a stage are the same pairs whichever lane makes them), then ((w0 + w1) + w2) + w3
+// sums of v[0..2] and c[0..2] over the block, valid on thread 0: butterfly inside each wave (blockops.h), then
+// ((w0 + w1) + w2) + w3
 __device__ inline void deflow_block_sum(double (&v)[3], int64_t (&c)[3]) {
     __shared__ double s_v[3][kDeflowThreads / 64];
     __shared__ int64_t s_c[3][kDeflowThreads / 64];
 #pragma unroll
-    for (int k = 0; k < 3; ++k)
-        for (int off = 32; off > 0; off >>= 1) {
-            v[k] += __shfl_xor(v[k], off, 64);
-            c[k] += __shfl_xor(c[k], off, 64);
-        }
+    for (int k = 0; k < 3; ++k) wave_sum2(v[k], c[k]);
     if ((threadIdx.x & 63) == 0)
 #pragma unroll
         for (int k = 0; k < 3; ++k) { s_v[k][threadIdx.x >> 6] = v[k]; s_c[k][threadIdx.x >> 6] = c[k]; }

@@ -17,6 +17,7 @@
 // ~0.25 GB read + written each, milliseconds once per pair against ~0.3 ms of NN searches EVERY iteration).
 // HBM-bound streams; integer arithmetic; bit-deterministic.
 #include "himo_common.h"
+#include "blockops.h"
 #include "dtlookup.h"
 #include <math.h>
 
@@ -88,18 +89,6 @@ __global__ __launch_bounds__(256) void dt_pass_axis_kernel(DtGrid g, const unsig
     }
 }
 
-// block_sum of doubles in a fixed order (deterministic)
-__device__ inline void dt_block_sum(double t, double* out) {
-    __shared__ double sh[256];
-    sh[threadIdx.x] = t;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *out = sh[0];
-}
-
 // per point: unnormalised gradient d D / d p (zero outside the volume or beyond trunc); per block: sum of the counted distances and
 // the number of points in the volume
 __global__ __launch_bounds__(256) void dt_loss_kernel(int n, const float* __restrict__ moved, DtGrid g, const unsigned short* __restrict__ vol,
@@ -116,7 +105,7 @@ __global__ __launch_bounds__(256) void dt_loss_kernel(int n, const float* __rest
 #pragma unroll
         for (int c = 0; c < 3; ++c) grad[i * 3 + c] = gr[c];
     }
-    dt_block_sum(t, partial + blockIdx.x);
+    block_sum<256>(t, partial + blockIdx.x);
     __shared__ int cnt[256];
     cnt[threadIdx.x] = inside;
     __syncthreads();
@@ -150,7 +139,7 @@ __global__ __launch_bounds__(256) void dt_finish_kernel(int n, int nb, const dou
         double t = 0.0;
         for (int b = threadIdx.x; b < nb; b += 256) t += partial[b];
         __shared__ double res;
-        dt_block_sum(t, &res);
+        block_sum<256>(t, &res);
         if (threadIdx.x == 0) *out = m > 0 ? res / (double)m : 0.0;
     }
 }

@@ -78,7 +78,7 @@ __device__ inline bool selected(const EvalArgs& a, int64_t i) {
 __global__ __launch_bounds__(kSelThreads) void select_count_kernel(EvalArgs a) {
     const int64_t bstart = (int64_t)blockIdx.x * kSelBlock;
     const int64_t bend = bstart + kSelBlock < a.total ? bstart + kSelBlock : a.total;
-    const int f0 = __builtin_amdgcn_readfirstlane(find_frame(a.offsets, a.n_frames, bstart));
+    const int f0 = __builtin_amdgcn_readfirstlane(segment_of(a.offsets, a.n_frames, bstart));
     const bool uniform = a.offsets[f0 + 1] >= bend;
     int cnt = 0;
     int f = f0;
@@ -90,7 +90,7 @@ __global__ __launch_bounds__(kSelThreads) void select_count_kernel(EvalArgs a) {
             atomicAdd(&a.frame_counts[f], 1);          // integer atomics: deterministic totals
         }
     }
-    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
+    cnt = wave_sum(cnt);
     __shared__ int w[kSelThreads / 64];
     if ((threadIdx.x & 63) == 0) w[threadIdx.x >> 6] = cnt;
     __syncthreads();
@@ -114,15 +114,7 @@ __global__ __launch_bounds__(1024) void select_scan_kernel(int* block_counts, in
         for (int base = 0; base < n; base += 1024) {
             const int i = base + threadIdx.x;
             const int x = i < n ? v[i] : 0;
-            part[threadIdx.x] = x;
-            __syncthreads();
-            for (int off = 1; off < 1024; off <<= 1) {       // Hillis-Steele inclusive scan
-                const int y = threadIdx.x >= off ? part[threadIdx.x - off] : 0;
-                __syncthreads();
-                part[threadIdx.x] += y;
-                __syncthreads();
-            }
-            const int incl = part[threadIdx.x], c = carry;
+            const int incl = block_inclusive_scan<1024>(x, part), c = carry;
             if (i < n) v[i] = c + incl - x;
             __syncthreads();
             if (threadIdx.x == 1023) carry = c + incl;
@@ -140,7 +132,7 @@ __global__ __launch_bounds__(1024) void select_scan_kernel(int* block_counts, in
 __global__ __launch_bounds__(kSelThreads) void select_compact_kernel(EvalArgs a) {
     const int64_t bstart = (int64_t)blockIdx.x * kSelBlock;
     const int64_t bend = bstart + kSelBlock < a.total ? bstart + kSelBlock : a.total;
-    const int f0 = find_frame(a.offsets, a.n_frames, bstart);
+    const int f0 = segment_of(a.offsets, a.n_frames, bstart);
     bool sel[4];
     int cnt = 0;
 #pragma unroll
@@ -150,12 +142,8 @@ __global__ __launch_bounds__(kSelThreads) void select_compact_kernel(EvalArgs a)
         cnt += sel[k];
     }
     // exclusive prefix of cnt over the block: wave scan + wave totals
-    int incl = cnt;
+    const int incl = wave_inclusive_scan(cnt);
     const int lane = threadIdx.x & 63;
-    for (int off = 1; off < 64; off <<= 1) {
-        const int y = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += y;
-    }
     __shared__ int wtot[kSelThreads / 64];
     if (lane == 63) wtot[threadIdx.x >> 6] = incl;
     __syncthreads();

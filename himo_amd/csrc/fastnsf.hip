@@ -17,6 +17,7 @@
 //   adam_kernel            the optimiser step;
 //   chamfer_trunc_*        the objective and its gradient with respect to the moved points.
 #include "himo_common.h"
+#include "blockops.h"
 #include "adam.h"
 #include "rigid_math.h"
 #include <math.h>
@@ -598,17 +599,6 @@ struct ChamferArgs {
 };
 constexpr double kChamferScatScale = 1099511627776.0;      // 2^40 (csrc/sslloss.hip uses the same scheme)
 
-__device__ inline void block_sum1(double v, double* out) {
-    __shared__ double red[256];
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *out = red[0];
-}
-
 __global__ __launch_bounds__(256) void chamfer_trunc_a_kernel(ChamferArgs a) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     double t = 0.0;
@@ -624,7 +614,7 @@ __global__ __launch_bounds__(256) void chamfer_trunc_a_kernel(ChamferArgs a) {
         for (int c = 0; c < 3; ++c)                        // (the scattering kernel ran first)
             a.grad[i * 3 + c] = g[c] + (float)((double)(long long)a.scat[i * 3 + c] * (1.0 / kChamferScatScale));
     }
-    block_sum1(t, a.partial + blockIdx.x);
+    block_sum<256>(t, a.partial + blockIdx.x);
 }
 
 __global__ __launch_bounds__(256) void chamfer_trunc_b_kernel(ChamferArgs a, int blocks0) {
@@ -637,7 +627,7 @@ __global__ __launch_bounds__(256) void chamfer_trunc_b_kernel(ChamferArgs a, int
         for (int c = 0; c < 3; ++c)
             atomicAdd(a.scat + i * 3 + c, (unsigned long long)__double2ll_rn((double)(2.0f / (float)a.n1 * (a.moved[i * 3 + c] - a.pc1[j * 3 + c])) * kChamferScatScale));
     }
-    block_sum1(t, a.partial + blocks0 + blockIdx.x);
+    block_sum<256>(t, a.partial + blocks0 + blockIdx.x);
 }
 
 // p' = R p + t by rigid_apply (rigid_math.h: the operation sequence this kernel has always compiled to, now written out and
@@ -668,7 +658,7 @@ __global__ __launch_bounds__(256) void sum_partials_kernel(const double* __restr
     double t = 0.0;
     for (int b = threadIdx.x; b < n; b += 256) t += partial[b];
     __shared__ double res;
-    block_sum1(t, &res);
+    block_sum<256>(t, &res);
     if (threadIdx.x == 0) *out = res;
 }
 

@@ -103,12 +103,6 @@ struct FlowmArgsEx : FlowmArgs {
 template <bool EX> struct FlowmArgsOf { typedef FlowmArgs type; };
 template <> struct FlowmArgsOf<true> { typedef FlowmArgsEx type; };
 
-__device__ inline ull wave_sum(ull v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 __device__ inline int flow_bucket(double speed, double w) {
     int b = speed >= w ? (int)fmin(speed / w, (double)(HIMO_FLOWM_BUCKETS - 1)) : 0;   // a guess, then the rule itself
     while (b < HIMO_FLOWM_BUCKETS - 1 && speed >= (double)(b + 1) * w) ++b;
@@ -179,7 +173,7 @@ __global__ __launch_bounds__(kFlowThreads) void flow_metrics_kernel(const typena
     const int64_t end = start + a.chunk < a.total ? start + a.chunk : a.total;
     int fcur = -1;                                                    // the sweep whose three-way words s_tw holds
     for (int64_t i0 = start; i0 < end; i0 += kFlowThreads) {
-        const int fit = __builtin_amdgcn_readfirstlane(find_frame(a.offsets, a.n_frames, i0));
+        const int fit = __builtin_amdgcn_readfirstlane(segment_of(a.offsets, a.n_frames, i0));
         if (fit != fcur) {                                            // (block-uniform)
             __syncthreads();
             if (fcur >= 0 && tid < R * 6) {

@@ -21,6 +21,7 @@
 // Traffic: two reads of xyz and one byte written per point (25 B/point at pitch 3, 33 B/point at pitch 4), plus 12 B per CELL and
 // sweep (key memset, key read, height write: 1.1 MB a sweep at the defaults) and one random 8-byte read per occupied cell.
 #include "himo_common.h"
+#include "blockops.h"
 #include <math.h>
 
 namespace himo {
@@ -44,16 +45,6 @@ struct GroundArgs {
     float* G_out;                           // the caller's copy, or nullptr
     uint8_t* mask;
 };
-
-// largest f with offsets[f] <= i (i < offsets[n_frames]); sweeps without points are passed over
-__device__ inline int gs_find_frame(const int64_t* __restrict__ offsets, int n_frames, int64_t i) {
-    int lo = 0, hi = n_frames;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (offsets[mid] <= i) lo = mid; else hi = mid;
-    }
-    return lo;
-}
 
 // rule A: the cell of a point inside its sweep's table, bin * S + segment, or -1 for an unbinned point
 __device__ inline int cell_of(const himo_ground_params& p, int S, float x, float y, float z) {
@@ -81,18 +72,12 @@ __device__ inline void load_xyz(const float* __restrict__ xyz, int pitch, int64_
     x = q[0]; y = q[1]; z = q[2];
 }
 
-__device__ inline unsigned long long shfl_xor_u64(unsigned long long v, int m) {
-    const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)v, m, 64);
-    const unsigned hi = (unsigned)__shfl_xor((int)(unsigned)(v >> 32), m, 64);
-    return ((unsigned long long)hi << 32) | lo;
-}
-
 // VEC4: pitch 4 and a 16-byte aligned base: one 16-byte load per point
 template <bool VEC4>
 __global__ __launch_bounds__(kGsThreads) void ground_bin_kernel(GroundArgs a) {
     const int64_t bstart = (int64_t)blockIdx.x * kGsBlockPts;
     const int64_t g = bstart + (int64_t)threadIdx.x * kGsPtsPerThread;
-    int f = __builtin_amdgcn_readfirstlane(gs_find_frame(a.offsets, a.n_frames, bstart));
+    int f = __builtin_amdgcn_readfirstlane(segment_of(a.offsets, a.n_frames, bstart));
     const int64_t cells = (int64_t)a.p.n_bins * a.S;
     const int lane = threadIdx.x & 63;
 #pragma unroll 1
@@ -186,7 +171,7 @@ __global__ __launch_bounds__(kGsThreads) void ground_classify_kernel(GroundArgs 
     const int64_t bstart = (int64_t)blockIdx.x * kGsBlockPts;
     const int64_t g = bstart + (int64_t)threadIdx.x * kGsPtsPerThread;
     if (g >= a.total) return;
-    int f = gs_find_frame(a.offsets, a.n_frames, g);
+    int f = segment_of(a.offsets, a.n_frames, g);
     const int64_t cells = (int64_t)a.p.n_bins * a.S;
     uint8_t out[kGsPtsPerThread];
 #pragma unroll

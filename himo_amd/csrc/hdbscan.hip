@@ -47,6 +47,7 @@
 //   cost         QUADRATIC per round, by decision: rounds x |P|^2 pairs at ~14 vector operations each.  No pruning.
 // No kernel waits on another block; no loop is unbounded apart from the union-find's own retry (unionfind.h).
 #include "himo_common.h"
+#include "blockops.h"
 #include "unionfind.h"
 #include <math.h>
 #include <algorithm>
@@ -61,17 +62,12 @@ constexpr unsigned long long kHdNone = ~0ull;
 // device words: [r] = the components alive at the start of round r (0 = nothing to do); n < 2^31 takes 31 rounds at most
 constexpr int kHdWords = 64;
 
-__device__ inline bool hd_takes_part(const float* __restrict__ xyz, int pitch, const unsigned char* __restrict__ skip, int i) {
-    const float x = xyz[(int64_t)i * pitch], y = xyz[(int64_t)i * pitch + 1], z = xyz[(int64_t)i * pitch + 2];
-    return !(skip && skip[i]) && x == x && y == y && z == z;
-}
-
 // participating points of every block of 1024; core2 of every point starts at +inf (what a point that takes no part keeps)
 __global__ __launch_bounds__(1024) void hd_count_kernel(int n, const float* __restrict__ xyz, int pitch, const unsigned char* __restrict__ skip,
                                                         int* __restrict__ block_sum, float* __restrict__ core2_out) {
     __shared__ int wsum[16];
     const int i = blockIdx.x * 1024 + threadIdx.x;
-    const bool in = i < n && hd_takes_part(xyz, pitch, skip, i);
+    const bool in = i < n && db_takes_part(xyz, pitch, skip, i);
     if (i < n && core2_out) core2_out[i] = INFINITY;
     const int c = __popcll(__ballot(in));
     if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
@@ -92,17 +88,12 @@ __global__ __launch_bounds__(1024) void hd_compact_kernel(int n, const float* __
     __shared__ int wsum[16];
     __shared__ int s_before, s_all;
     if (threadIdx.x < 64) {                                     // one wave: the blocks before this one, and all of them
-        int before = 0, all = 0;
-        for (int t = threadIdx.x; t < (int)gridDim.x; t += 64) {
-            const int x = block_sum[t];
-            all += x;
-            if (t < (int)blockIdx.x) before += x;
-        }
-        for (int off = 32; off; off >>= 1) { before += __shfl_xor(before, off, 64); all += __shfl_xor(all, off, 64); }
+        int before, all;
+        tiles_before_and_all(block_sum, before, all);
         if (threadIdx.x == 0) { s_before = before; s_all = all; }
     }
     const int i = blockIdx.x * 1024 + threadIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const bool in = i < n && hd_takes_part(xyz, pitch, skip, i);
+    const bool in = i < n && db_takes_part(xyz, pitch, skip, i);
     const unsigned long long mask = __ballot(in);
     if (lane == 0) wsum[w] = __popcll(mask);
     __syncthreads();

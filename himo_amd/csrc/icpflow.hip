@@ -21,6 +21,7 @@
 // Built with -ffp-contract=off: every float operation rounds on its own, as numpy does.  Only sqrt and division appear (float32
 // division in the vote, float64 elsewhere), both correctly rounded.
 #include "nngrid.h"
+#include "blockops.h"
 #include <math.h>
 
 namespace himo {
@@ -33,18 +34,6 @@ constexpr int kMomDoubles = 10;              // n, m_bar xyz, q_bar xyz, A, B, (
 // the BEV cell grid the target sweep is binned on: the one the package's searches use (himo_amd/ssl_loss.py)
 constexpr float kIcpGridX0 = -52.f, kIcpGridY0 = -52.f, kIcpGridCell = 1.f;
 constexpr int kIcpGridW = 104, kIcpGridH = 104;
-
-__device__ inline int icp_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// largest k in [0, C) with offsets[k] <= i (i < offsets[C]): the cluster that owns sorted row i; empty clusters are passed over
-__device__ inline int icp_find_cluster(const int64_t* __restrict__ offsets, int C, int64_t i) {
-    int lo = 0, hi = C;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (offsets[mid] <= i) lo = mid; else hi = mid;
-    }
-    return lo;
-}
 
 struct VoteArgs {
     int64_t n;
@@ -66,7 +55,7 @@ __global__ __launch_bounds__(kIcpThreads) void icp_vote_kernel(VoteArgs a) {
     const bool use_lds = WW <= kVoteLdsBins;
     const int64_t base = (int64_t)blockIdx.x * kVotePts;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int k0 = icp_find_cluster(a.offsets, a.C, base);
+    const int k0 = segment_of(a.offsets, a.C, base);
     if (use_lds) {
         for (int b = threadIdx.x; b < WW; b += kIcpThreads) hist[b] = 0;
         __syncthreads();
@@ -75,16 +64,14 @@ __global__ __launch_bounds__(kIcpThreads) void icp_vote_kernel(VoteArgs a) {
     for (int p = wave; p < kVotePts; p += kVoteWaves) {
         const int64_t i = base + p;
         if (i >= a.n) break;
-        const int k = icp_find_cluster(a.offsets, a.C, i);
+        const int k = segment_of(a.offsets, a.C, i);
         const float* q = a.pts + i * a.pitch;
         const float ax = q[0], ay = q[1], az = q[2];
         // every target point that can vote lies within (half + 1/2) bins in x and in y, up to float32 rounding: half a bin and a
         // relative 1e-4 of the coordinates more cover that
         const float reach = (fhalf + 1.f) * a.bin + 1e-4f * (fabsf(ax) + fabsf(ay) + 1.f);
-        const int cx0 = icp_clampi((int)floorf((ax - reach - a.g.x0) * a.g.inv_cell), 0, a.g.gw - 1);
-        const int cx1 = icp_clampi((int)floorf((ax + reach - a.g.x0) * a.g.inv_cell), 0, a.g.gw - 1);
-        const int cy0 = icp_clampi((int)floorf((ay - reach - a.g.y0) * a.g.inv_cell), 0, a.g.gh - 1);
-        const int cy1 = icp_clampi((int)floorf((ay + reach - a.g.y0) * a.g.inv_cell), 0, a.g.gh - 1);
+        const int cx0 = nng_cell_x(a.g, ax - reach), cx1 = nng_cell_x(a.g, ax + reach);
+        const int cy0 = nng_cell_y(a.g, ay - reach), cy1 = nng_cell_y(a.g, ay + reach);
         int* const mine = a.counts + (size_t)k * WW;
         const bool to_lds = use_lds && k == k0;
         for (int cy = cy0; cy <= cy1; ++cy) {
@@ -124,13 +111,7 @@ __global__ __launch_bounds__(64) void icp_peak_kernel(int C, int half, float bin
         const unsigned long long key = ((unsigned long long)(unsigned)c[b] << 32) | (0xffffffffu - rank);
         best = key > best ? key : best;
     }
-#pragma unroll
-    for (int w = 32; w >= 1; w >>= 1) {
-        const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)best, w, 64);
-        const unsigned hi = (unsigned)__shfl_xor((int)(unsigned)(best >> 32), w, 64);
-        const unsigned long long o = ((unsigned long long)hi << 32) | lo;
-        best = o > best ? o : best;
-    }
+    best = wave_max_u64(best);
     if (threadIdx.x == 0) {
         const int b = (int)((0xffffffffu - (unsigned)best) & 0x7fffu);
         const int ky = b / W - half, kx = b % W - half;
@@ -161,19 +142,6 @@ struct StepArgs {
     double* mom;                     // [C][kMomDoubles]
 };
 
-// the fixed tree: every thread holds one partial; the sum in thread order 128, 64, ... 1 (the same bytes on every run)
-__device__ inline double icp_block_sum(double v, double* sh) {
-    __syncthreads();
-    sh[threadIdx.x] = v;
-    __syncthreads();
-#pragma unroll
-    for (int s = kIcpThreads / 2; s >= 1; s >>= 1) {
-        if ((int)threadIdx.x < s) sh[threadIdx.x] = sh[threadIdx.x] + sh[threadIdx.x + s];
-        __syncthreads();
-    }
-    return sh[0];
-}
-
 __global__ __launch_bounds__(kIcpThreads) void icp_moments_kernel(StepArgs a) {
     __shared__ double sh[kIcpThreads];
     const int k = blockIdx.x;
@@ -190,11 +158,11 @@ __global__ __launch_bounds__(kIcpThreads) void icp_moments_kernel(StepArgs a) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) { sm[c] = sm[c] + (double)m[c]; sq[c] = sq[c] + (double)q[c]; }
     }
-    const double n = icp_block_sum(cnt, sh);
+    const double n = group_sum<kIcpThreads>(cnt, sh);
     double mb[3], qb[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        const double s0 = icp_block_sum(sm[c], sh), s1 = icp_block_sum(sq[c], sh);
+        const double s0 = group_sum<kIcpThreads>(sm[c], sh), s1 = group_sum<kIcpThreads>(sq[c], sh);
         mb[c] = n > 0.0 ? s0 / n : 0.0;
         qb[c] = n > 0.0 ? s1 / n : 0.0;
     }
@@ -207,8 +175,8 @@ __global__ __launch_bounds__(kIcpThreads) void icp_moments_kernel(StepArgs a) {
         A = A + (mx * qx + my * qy);
         B = B + (mx * qy - my * qx);
     }
-    A = icp_block_sum(A, sh);
-    B = icp_block_sum(B, sh);
+    A = group_sum<kIcpThreads>(A, sh);
+    B = group_sum<kIcpThreads>(B, sh);
     if (threadIdx.x == 0) {
         double* o = a.mom + (size_t)k * kMomDoubles;
         o[0] = n; o[1] = mb[0]; o[2] = mb[1]; o[3] = mb[2]; o[4] = qb[0]; o[5] = qb[1]; o[6] = qb[2]; o[7] = A; o[8] = B; o[9] = 0.0;

@@ -18,6 +18,7 @@
 // order of scipy's cKDTree -- so sqrt(min) is bit-comparable with the reference; float32 mode uses
 // fused multiply-adds.  Ties keep the lowest reference index.  Built with -ffp-contract=off.
 #include "himo_common.h"
+#include "blockops.h"
 #include <math.h>
 
 namespace himo {
@@ -56,15 +57,6 @@ __device__ inline double dist2<double>(double qx, double qy, double qz, double r
     return (dx * dx + dy * dy) + dz * dz;
 }
 
-__device__ inline int find_segment(const int64_t* __restrict__ off, int n, int64_t i) {
-    int lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (off[mid] <= i) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 // SPLIT lanes share one query; lane s of the group scans tile entries s, s+SPLIT, ...
 template <typename T, int QPT, int SPLIT>
 __global__ __launch_bounds__(kNnThreads) void nn_kernel(NnArgs a) {
@@ -92,7 +84,7 @@ __global__ __launch_bounds__(kNnThreads) void nn_kernel(NnArgs a) {
             qx[k] = Q[i * 3]; qy[k] = Q[i * 3 + 1]; qz[k] = Q[i * 3 + 2];
             if (a.rbeg) { rs[k] = a.rbeg[i]; re[k] = rs[k] + a.rlen[i]; }
             else {
-                const int s = find_segment(a.q_off, a.n_segments, i);
+                const int s = segment_of(a.q_off, a.n_segments, i);
                 rs[k] = (int)a.r_off[s]; re[k] = (int)a.r_off[s + 1];
             }
             if (re[k] > rs[k]) { lo = min(lo, rs[k]); hi = max(hi, re[k]); }

@@ -3,6 +3,7 @@
 // set) jobs in one launch.  Not part of the C ABI (include/himo_amd.h declares himo_nn_grid, the one-job form).
 #pragma once
 #include "himo_common.h"
+#include "blockops.h"
 
 namespace himo {
 
@@ -10,6 +11,11 @@ struct NnGrid {
     float x0, y0, inv_cell, cell;
     int gw, gh;
 };
+
+// the grid column / row of a coordinate.  Points outside the grid are binned into the border cells (the ring bound of the query
+// stays valid because it is computed from the clamped cell geometry and the true query position)
+__device__ inline int nng_cell_x(const NnGrid& g, float x) { return clampi((int)floorf((x - g.x0) * g.inv_cell), 0, g.gw - 1); }
+__device__ inline int nng_cell_y(const NnGrid& g, float y) { return clampi((int)floorf((y - g.y0) * g.inv_cell), 0, g.gh - 1); }
 
 // one point set binned on the grid; every pointer is carved out of the caller's workspace by nng_carve
 struct NngSet {

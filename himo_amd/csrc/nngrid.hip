@@ -40,15 +40,6 @@ constexpr int kNngWaves = 8;          // waves of a query block (a power of two)
 constexpr int kNngSegCells = 16;      // widest stretch of a grid row one segment covers
 constexpr int kNngScanChunk = 4096;   // cells per iteration of the one-block scan
 
-__device__ inline int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-__device__ inline void cell_of(const NnGrid& g, float x, float y, int& cx, int& cy) {
-    // points outside the grid are binned into the border cells (the ring bound below stays valid
-    // because it is computed from the clamped cell geometry and the true query position)
-    cx = clampi((int)floorf((x - g.x0) * g.inv_cell), 0, g.gw - 1);
-    cy = clampi((int)floorf((y - g.y0) * g.inv_cell), 0, g.gh - 1);
-}
-
 struct NngArgs {
     NngSet set[kNngMaxSets];
     NngJob job[kNngMaxJobs];
@@ -59,8 +50,7 @@ __global__ __launch_bounds__(256) void nng_count_kernel(NngArgs a) {
     const NngSet& S = a.set[blockIdx.y];
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= S.n) return;
-    int cx, cy;
-    cell_of(a.g, S.pts[(size_t)i * 3], S.pts[(size_t)i * 3 + 1], cx, cy);
+    const int cx = nng_cell_x(a.g, S.pts[(size_t)i * 3]), cy = nng_cell_y(a.g, S.pts[(size_t)i * 3 + 1]);
     const int c = cy * a.g.gw + cx;
     S.cell_id[i] = c;
     atomicAdd(&S.offset[c], 1);
@@ -81,11 +71,7 @@ __global__ __launch_bounds__(1024) void nng_scan_kernel(NngArgs a, int cells) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) x[k] = at + k < cells ? v[at + k] : 0;
         const int mine = x[0] + x[1] + x[2] + x[3];
-        int incl = mine;
-        for (int off = 1; off < 64; off <<= 1) {
-            const int y = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += y;
-        }
+        const int incl = wave_inclusive_scan(mine);
         if (lane == 63) wsum[w] = incl;
         __syncthreads();
         int run = carry + incl - mine, total = 0;
@@ -135,8 +121,7 @@ __global__ __launch_bounds__(64 * kNngWaves) void nng_query_kernel(NngArgs a) {
     const bool valid = base + lane < Q.n;
     const float4 me = Q.sorted[min(base + lane, Q.n - 1)];
     const float qx = me.x, qy = me.y, qz = me.z;
-    int cx, cy;
-    cell_of(g, qx, qy, cx, cy);
+    const int cx = nng_cell_x(g, qx), cy = nng_cell_y(g, qy);
     unsigned long long best = kNngNone;
     float best_d = INFINITY;                 // the distance half of `best`
     const float2v q2x{qx, qx}, q2y{qy, qy}, q2z{qz, qz};

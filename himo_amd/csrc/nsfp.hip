@@ -21,6 +21,7 @@
 //                       slot (t - 1) & 1 -- every thread for itself -- and thread 0 writes slot t & 1; when the rule says "improved"
 //                       the iteration's MLP output is copied to best_out.  No host read is involved.
 #include "nngrid.h"
+#include "blockops.h"
 #include <math.h>
 
 namespace himo {
@@ -48,13 +49,6 @@ __global__ __launch_bounds__(256) void nsfp_moved_kernel(NsfpArgs a) {
     a.moved[(size_t)i * 3] = x.x + o.x; a.moved[(size_t)i * 3 + 1] = x.y + o.y; a.moved[(size_t)i * 3 + 2] = x.z + o.z;
 }
 
-// sum over the wave in a fixed (butterfly) order: the same bits in every lane, on every launch
-__device__ inline double nsfp_wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 __global__ __launch_bounds__(256) void nsfp_b_kernel(NsfpArgs a) {
     __shared__ double s_w[4];
     const int j = blockIdx.x * 256 + threadIdx.x;
@@ -70,7 +64,7 @@ __global__ __launch_bounds__(256) void nsfp_b_kernel(NsfpArgs a) {
                 atomicAdd(a.scat + (size_t)i * 3 + c, (unsigned long long)__double2ll_rn((double)(a.moved[(size_t)i * 3 + c] - a.pc1[(size_t)j * 3 + c]) * w));
         }
     }
-    t = nsfp_wave_sum(t);
+    t = wave_sum(t);
     if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = t;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -108,7 +102,7 @@ __global__ __launch_bounds__(256) void nsfp_a_kernel(NsfpArgs a) {
         }
     }
     *reinterpret_cast<float4*>(a.dout + (size_t)row * 4) = float4{g[0], g[1], g[2], 0.f};       // (padding rows: zeros)
-    t = nsfp_wave_sum(t);
+    t = wave_sum(t);
     const int cnt = __popcll(__ballot(real));
     if ((threadIdx.x & 63) == 0) {
         const int tile = blockIdx.x * 4 + (threadIdx.x >> 6);

@@ -22,6 +22,7 @@
 //                           HIMO_PILLAR_NO_LISTS: the ascending lists and NULL-offset sweeps' offsets are not written.
 // Only integer atomics are used; the output is bit-deterministic.
 #include "himo_common.h"
+#include "blockops.h"
 #include "bf16x3.h"
 #include <math.h>
 #include <algorithm>
@@ -119,12 +120,8 @@ __global__ __launch_bounds__(256) void cell_scan_local_kernel(PillarBatch m) {
 #pragma unroll
     for (int k = 0; k < 4; ++k) x[k] = base + k < n ? v[base + k] : 0;
     const int mine = x[0] + x[1] + x[2] + x[3];
-    int incl = mine;
+    const int incl = wave_inclusive_scan(mine);
     const int lane = threadIdx.x & 63;
-    for (int off = 1; off < 64; off <<= 1) {
-        const int y = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += y;
-    }
     if (lane == 63) wsum[threadIdx.x >> 6] = incl;
     __syncthreads();
     int run = incl - mine;
@@ -138,15 +135,8 @@ __global__ __launch_bounds__(1024) void cell_scan_top_kernel(PillarBatch m, int 
     int* block_sum = m.s[blockIdx.y].block_sum;
     __shared__ int part[1024];
     const int x = (int)threadIdx.x < nblk ? block_sum[threadIdx.x] : 0;
-    part[threadIdx.x] = x;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
-        const int y = threadIdx.x >= off ? part[threadIdx.x - off] : 0;
-        __syncthreads();
-        part[threadIdx.x] += y;
-        __syncthreads();
-    }
-    if ((int)threadIdx.x < nblk) block_sum[threadIdx.x] = part[threadIdx.x] - x;
+    const int incl = block_inclusive_scan<1024>(x, part);
+    if ((int)threadIdx.x < nblk) block_sum[threadIdx.x] = incl - x;
     if (threadIdx.x == 1023) block_sum[nblk] = part[1023];
 }
 

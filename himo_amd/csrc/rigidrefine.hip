@@ -30,6 +30,7 @@
 // Built with -ffp-contract=off: every float operation rounds on its own, as numpy does.  Only sqrt and division appear (float32
 // division in the vote, float64 elsewhere), both correctly rounded.
 #include "himo_common.h"
+#include "blockops.h"
 #include <math.h>
 
 namespace himo {
@@ -56,50 +57,6 @@ struct RrArgs {
     int* status;                     // [C][models][4]
 };
 
-// every lane of the group: the sum of the group's values in a fixed order
-template <int NT> __device__ inline double rr_sum(double v, double* sh) {
-    if constexpr (NT == 64) {
-#pragma unroll
-        for (int w = 32; w >= 1; w >>= 1) v = v + __shfl_xor(v, w, 64);
-        return v;
-    } else {
-        __syncthreads();
-        sh[threadIdx.x] = v;
-        __syncthreads();
-#pragma unroll
-        for (int s = NT / 2; s >= 1; s >>= 1) {
-            if ((int)threadIdx.x < s) sh[threadIdx.x] = sh[threadIdx.x] + sh[threadIdx.x + s];
-            __syncthreads();
-        }
-        return sh[0];
-    }
-}
-
-// ... and the maximum of 64-bit keys / of non-negative doubles (whose bit patterns order as they do)
-template <int NT> __device__ inline unsigned long long rr_max(unsigned long long v, double* sh) {
-    if constexpr (NT == 64) {
-#pragma unroll
-        for (int w = 32; w >= 1; w >>= 1) {
-            const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)v, w, 64);
-            const unsigned hi = (unsigned)__shfl_xor((int)(unsigned)(v >> 32), w, 64);
-            const unsigned long long o = ((unsigned long long)hi << 32) | lo;
-            v = o > v ? o : v;
-        }
-        return v;
-    } else {
-        unsigned long long* u = reinterpret_cast<unsigned long long*>(sh);
-        __syncthreads();
-        u[threadIdx.x] = v;
-        __syncthreads();
-#pragma unroll
-        for (int s = NT / 2; s >= 1; s >>= 1) {
-            if ((int)threadIdx.x < s) u[threadIdx.x] = u[threadIdx.x] > u[threadIdx.x + s] ? u[threadIdx.x] : u[threadIdx.x + s];
-            __syncthreads();
-        }
-        return u[0];
-    }
-}
-
 // the group's earlier LDS / global writes and atomics are done and seen by the whole group
 template <int NT> __device__ inline void rr_sync() {
     if constexpr (NT == 64) {
@@ -113,7 +70,8 @@ template <int NT> __device__ inline void rr_sync() {
 template <int NT> __global__ __launch_bounds__(NT == 64 ? kRrWaveBlock : NT) void rr_fit_kernel(RrArgs p) {
     constexpr int kGroups = NT == 64 ? kRrWaveBlock / 64 : 1;
     __shared__ int lds_hist[kRrLdsBins];
-    __shared__ double red[NT == 64 ? 1 : NT];
+    __shared__ double red[NT == 64 ? 1 : NT];                                // blockops.h: the block group's tree; a wave uses none
+    unsigned long long* const red_u = reinterpret_cast<unsigned long long*>(red);
     const int lane = (int)threadIdx.x % NT, group = (int)threadIdx.x / NT;
     const int k = (int)blockIdx.x * kGroups + group;
     if (k >= p.C) return;                                     // (a whole group: wave groups use no block barrier)
@@ -167,7 +125,7 @@ template <int NT> __global__ __launch_bounds__(NT == 64 ? kRrWaveBlock : NT) voi
             const unsigned long long key = ((unsigned long long)(unsigned)cnt << 32) | (0xffffffffu - rank);
             best = key > best ? key : best;
         }
-        best = rr_max<NT>(best, red);
+        best = group_max_u64<NT>(best, red_u);
         rr_sync<NT>();
         const int pb = (int)((0xffffffffu - (unsigned)best) & 0x7fffu);
         const int pky = pb / W - p.half, pkx = pb % W - p.half;
@@ -199,14 +157,14 @@ template <int NT> __global__ __launch_bounds__(NT == 64 ? kRrWaveBlock : NT) voi
 #pragma unroll
                 for (int d = 0; d < 3; ++d) { sa[d] = sa[d] + (double)a[d]; sq[d] = sq[d] + (double)q[d]; }
             }
-            n = (int)rr_sum<NT>(cnt, red);                       // whole numbers below 2^31: exact in any order
+            n = (int)group_sum<NT>(cnt, red);                    // whole numbers below 2^31: exact in any order
             if (pass == p.iters) break;
             if (n < p.min_inliers) { failed = true; break; }
             double ab[3], qb[3];
 #pragma unroll
             for (int d = 0; d < 3; ++d) {
-                ab[d] = rr_sum<NT>(sa[d], red) / (double)n;
-                qb[d] = rr_sum<NT>(sq[d], red) / (double)n;
+                ab[d] = group_sum<NT>(sa[d], red) / (double)n;
+                qb[d] = group_sum<NT>(sq[d], red) / (double)n;
             }
             double A = 0.0, B = 0.0;
             for (int64_t i = lo + lane; i < hi; i += NT) {
@@ -217,8 +175,8 @@ template <int NT> __global__ __launch_bounds__(NT == 64 ? kRrWaveBlock : NT) voi
                 A = A + (ax * qx + ay * qy);
                 B = B + (ax * qy - ay * qx);
             }
-            A = rr_sum<NT>(A, red);
-            B = rr_sum<NT>(B, red);
+            A = group_sum<NT>(A, red);
+            B = group_sum<NT>(B, red);
             const double h = sqrt(A * A + B * B);
             c = h == 0.0 ? 1.0 : A / h;
             s = h == 0.0 ? 0.0 : B / h;
@@ -247,7 +205,7 @@ template <int NT> __global__ __launch_bounds__(NT == 64 ? kRrWaveBlock : NT) voi
                 p.claim_s[i] = (uint8_t)(j + 1);                 // 2e: the claim (this thread's own byte)
                 p.claim[p.rows[i]] = (int8_t)(j + 1);
             }
-            far = __builtin_bit_cast(double, rr_max<NT>(__builtin_bit_cast(unsigned long long, far), red));
+            far = __builtin_bit_cast(double, group_max_u64<NT>(__builtin_bit_cast(unsigned long long, far), red_u));
             if (far < p.static2) {
                 state = HIMO_RIGID_STATIC;
                 c = 1.0; s = 0.0; tx = 0.0; ty = 0.0; tz = 0.0;

@@ -28,6 +28,7 @@
 // point at a time through compare-and-add on the same counters, each point exactly once.  At the end: a shuffle reduction
 // inside the wave, LDS across the block's four waves, one 64-bit global atomicAdd per non-zero bin per block.
 #include "himo_common.h"
+#include "blockops.h"
 
 namespace himo {
 
@@ -126,9 +127,7 @@ __global__ __launch_bounds__(kSegThreads) void seg_confusion_kernel(const SegArg
         for (int m = 0; m < 2; ++m)
 #pragma unroll
             for (int b = 0; b < kSegBins; ++b) {
-                unsigned v = cnt[r][m][b];
-#pragma unroll
-                for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+                const unsigned v = wave_sum(cnt[r][m][b]);
                 if (lane == 0) s_part[wave][(r * 2 + m) * kSegBins + b] = v;
             }
     __syncthreads();

@@ -26,6 +26,7 @@
 // float atomics made two runs of the same step differ in the last bits, and 20 optimiser steps amplified that into
 // different weights), converted once per point: the whole gradient is bit-reproducible.
 #include "nngrid.h"
+#include "blockops.h"
 #include <math.h>
 
 namespace himo {
@@ -69,7 +70,7 @@ __global__ __launch_bounds__(256) void loss_prepare_kernel(LossArgs a) {
 __global__ __launch_bounds__(256) void dyn_count_kernel(int n, const int* __restrict__ lab, int* __restrict__ block_cnt) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     int c = (i < n && lab[i] > 0) ? 1 : 0;
-    for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off, 64);
+    c = wave_sum(c);
     __shared__ int w[4];
     if ((threadIdx.x & 63) == 0) w[threadIdx.x >> 6] = c;
     __syncthreads();
@@ -84,15 +85,7 @@ __global__ __launch_bounds__(1024) void dyn_scan_kernel(int* v, int n, int* tota
     for (int base = 0; base < n; base += 1024) {
         const int i = base + threadIdx.x;
         const int x = i < n ? v[i] : 0;
-        part[threadIdx.x] = x;
-        __syncthreads();
-        for (int off = 1; off < 1024; off <<= 1) {
-            const int y = threadIdx.x >= off ? part[threadIdx.x - off] : 0;
-            __syncthreads();
-            part[threadIdx.x] += y;
-            __syncthreads();
-        }
-        const int incl = part[threadIdx.x], c = carry;
+        const int incl = block_inclusive_scan<1024>(x, part), c = carry;
         if (i < n) v[i] = c + incl - x;
         __syncthreads();
         if (threadIdx.x == 1023) carry = c + incl;
@@ -106,12 +99,8 @@ __global__ __launch_bounds__(256) void dyn_write_kernel(int n, const int* __rest
                                                         int* __restrict__ pos_out, float* __restrict__ pts_out) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     const bool sel = i < n && lab[i] > 0;
-    int incl = sel ? 1 : 0;
+    const int incl = wave_inclusive_scan(sel ? 1 : 0);
     const int lane = threadIdx.x & 63;
-    for (int off = 1; off < 64; off <<= 1) {
-        const int y = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += y;
-    }
     __shared__ int wt[4];
     if (lane == 63) wt[threadIdx.x >> 6] = incl;
     __syncthreads();
@@ -143,22 +132,6 @@ __global__ __launch_bounds__(256) void cluster_count_kernel(LossArgs a) {
     if (i >= a.n0) return;
     const int l = a.lab0[i];
     if (l > 0 && l < a.n_labels && a.anchor[l] != 0ull) atomicAdd(&a.counts[3], 1);
-}
-
-__device__ inline void block_sum4(double (&v)[4], double* out) {
-    __shared__ double red[4][256];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) red[k][threadIdx.x] = v[k];
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off)
-#pragma unroll
-            for (int k = 0; k < 4; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + off];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) out[k] = red[k][0];
 }
 
 // per pc0 point: the terms it owns and their gradient
@@ -210,7 +183,7 @@ __global__ __launch_bounds__(256) void loss_pc0_kernel(LossArgs a) {
         for (int c = 0; c < 3; ++c)                                // the scattering kernel ran before this one
             a.grad[i * 3 + c] = g[c] + (float)((double)(long long)a.scat[i * 3 + c] * (1.0 / kScatScale));
     }
-    block_sum4(t, a.partial + (size_t)blockIdx.x * 4);
+    block_sum<256>(t, a.partial + (size_t)blockIdx.x * 4);
 }
 
 __device__ inline void scat_add(unsigned long long* p, float v) {
@@ -236,7 +209,7 @@ __global__ __launch_bounds__(256) void loss_pc1_kernel(LossArgs a, int blocks0) 
 #pragma unroll
         for (int c = 0; c < 3; ++c) scat_add(a.scat + i * 3 + c, 2.0f / (float)nd1 * (a.mdyn[k * 3 + c] - a.qdyn[j * 3 + c]));
     }
-    block_sum4(t, a.partial + ((size_t)blocks0 + blockIdx.x) * 4);
+    block_sum<256>(t, a.partial + ((size_t)blocks0 + blockIdx.x) * 4);
 }
 
 // expect0 / expect1 >= 0: the dynamic subset sizes the host was GIVEN (himo_ssl_loss_presized) -- a mismatch with the counted ones would
@@ -248,7 +221,7 @@ __global__ __launch_bounds__(256) void loss_final_kernel(const double* __restric
 #pragma unroll
         for (int k = 0; k < 4; ++k) t[k] += partial[(size_t)b * 4 + k];
     __shared__ double out[4];
-    block_sum4(t, out);
+    block_sum<256>(t, out);
     if (threadIdx.x == 0) {
         loss[0] = out[0]; loss[1] = out[1]; loss[2] = out[2]; loss[3] = out[3];
         loss[4] = ((out[0] + out[1]) + out[2]) + out[3];

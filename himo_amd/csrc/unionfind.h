@@ -1,9 +1,16 @@
-// unionfind.h -- the lock-free union-find of the clustering kernels (dbscan.hip, hdbscan.hip): components over point indices, hooked with
-// atomicMin so that a component's root ends as its lowest index, whatever the order the hooks land in.
+// unionfind.h -- what the clustering kernels (dbscan.hip, hdbscan.hip) share: which rows take part, and the lock-free union-find:
+// components over point indices, hooked with atomicMin so that a component's root ends as its lowest index, whatever the order the
+// hooks land in.
 #pragma once
 #include <hip/hip_runtime.h>
 
 namespace himo {
+
+// whether row i takes part in the clustering: not flagged in `skip` and no NaN coordinate (both stages give such a row label 0)
+__device__ inline bool db_takes_part(const float* __restrict__ xyz, int pitch, const unsigned char* __restrict__ skip, int i) {
+    const float x = xyz[(int64_t)i * pitch], y = xyz[(int64_t)i * pitch + 1], z = xyz[(int64_t)i * pitch + 2];
+    return !(skip && skip[i]) && x == x && y == y && z == z;
+}
 
 __device__ inline int db_find(const int* __restrict__ parent, int x) {
     int p = parent[x];

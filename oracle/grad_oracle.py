@@ -9,23 +9,23 @@ whatever autograd dispatches to.
 
 Arithmetics (names of conv_oracle.R, whose values and arguments are taken over unchanged):
   f32     v_mfma_f32_32x32x2_f32 on float32 operands -- conv_wgrad_partial_kernel (train.hip:256-274),
-          conv_wgrad_tiled_kernel (train.hip:358-367), wgrad_partial_kernel (fastnsf.hip:53-67), wgrad_partial_lds_kernel
-          (fastnsf.hip:135-148) -- and the float32 FMA chains of wgrad_thin_partial_kernel (fastnsf.hip:721-726) and the
-          column-sum kernels (fastnsf.hip:506, 524-527).  Every product rounds once, every addition once, in the order of
+          conv_wgrad_tiled_kernel (train.hip:358-367), wgrad_partial_kernel (fastnsf.hip:54-68), wgrad_partial_lds_kernel
+          (fastnsf.hip:136-149) -- and the float32 FMA chains of wgrad_thin_partial_kernel (fastnsf.hip:712-717) and the
+          column-sum kernels (fastnsf.hip:507, 525-528).  Every product rounds once, every addition once, in the order of
           the kernel: conv_oracle.R["f32"] = 2.
-  bf16x2  flag 2: x = h + m per operand (split2_bf16_pair train.hip:391-400, wg_split_pair fastnsf.hip:175-184: h = RNE
+  bf16x2  flag 2: x = h + m per operand (split2_bf16_pair train.hip:391-400, wg_split_pair fastnsf.hip:176-185: h = RNE
           bf16 of x, m = RNE bf16 of x - h, i.e. conv_oracle.split_terms("bf16x2")), three v_mfma_f32_32x32x16_bf16 per
           fragment pair.  The kept products, as (term of A, term of B):
               conv_wgrad_split_kernel    train.hip:525-527     (1, 0) (0, 1) (0, 0)
               conv_wgrad_split2_kernel   train.hip:665-667     (1, 0) (0, 1) (0, 0)
-              wgrad_partial_split_kernel fastnsf.hip:287-289   (1, 0) (0, 1) (0, 0)
-              wgrad_full_split_kernel    fastnsf.hip:433-435   (1, 0) (0, 1) (0, 0)
+              wgrad_partial_split_kernel fastnsf.hip:288-290   (1, 0) (0, 1) (0, 0)
+              wgrad_full_split_kernel    fastnsf.hip:434-436   (1, 0) (0, 1) (0, 0)
           m * m (2^-18 relative) is dropped: conv_oracle.KEPT["bf16x2"] and conv_oracle.R["bf16x2"] = 128.
   elem    the element-wise kernels; R_ELEM below.
 
 Partial-sum merges (conv_wgrad_reduce_kernel train.hip:745, conv_wgrad_tiled_reduce_kernel train.hip:716-729,
-wgrad_reduce_kernel fastnsf.hip:480-493, colsum_reduce_kernel fastnsf.hip:549-563, wgrad_thin_reduce_kernel
-fastnsf.hip:743-757): a product passes through the additions of its own block (at most the block's share K_b of the K
+wgrad_reduce_kernel fastnsf.hip:481-494, colsum_reduce_kernel fastnsf.hip:550-564, wgrad_thin_reduce_kernel
+fastnsf.hip:734-748): a product passes through the additions of its own block (at most the block's share K_b of the K
 products), then through at most ceil(blocks / 16) + 4 additions of the reduce kernel.  A second block exists only when the
 first owns at least 256 products (conv_wgrad_chunk, wgrad_rows_per_block, four 64-pixel tiles per chunk), so
 K_b + ceil(blocks / 16) + 4 <= K + 4 for any admitted size; with the rounding of the product itself and two spare
@@ -244,7 +244,7 @@ def linear_dw_bound(arith, x, dz, old=None):
 
 
 def colsum_bound(z, old=None):
-    """float32 column sums (colsum_partial*_kernel, the bias partials of the split kernels, train.hip:475 / fastnsf.hip:255):
+    """float32 column sums (colsum_partial*_kernel, the bias partials of the split kernels, train.hip:475 / fastnsf.hip:256):
     (K + MERGE_C) u sum |z|, K = rows."""
     z = _d(z).abs()
     z = z.reshape(-1, z.shape[-1])
@@ -313,7 +313,7 @@ def elementwise(name, dtype=torch.float64, **a):
 
 
 def elementwise_bound(name, **a):
-    """Per-output worst case of the float32 kernels (train.hip:17-144, fastnsf.hip:655-663), float64 inputs as given:
+    """Per-output worst case of the float32 kernels (train.hip:17-144, fastnsf.hip:646-654), float64 inputs as given:
     conv_oracle.bound's budgets for the transcendental functions (sigmoid: g u (6 + |v|); tanh: 2 e u (4 + 2 |v|) + 4 u |q|,
     e = exp(-2 |v|); GELU: (|t| / 2) (1.5e-7 + 16 u) + 4 u |y|) plus c u |value| for the c roundings of the products and sums
     of each formula (counted below), plus the float32 underflow floor."""
@@ -397,7 +397,7 @@ def ok_cols(got, ref, bnd, ref32, arith, case=""):
 
 
 def emulate_colsum(z, groups=8):
-    """the column-sum kernels' order (fastnsf.hip:498-565): blocks of wgrad_rows_per_block rows, ``groups`` interleaved
+    """the column-sum kernels' order (fastnsf.hip:499-566): blocks of wgrad_rows_per_block rows, ``groups`` interleaved
     sequential chains per block (2: colsum_partial_kernel, 8: colsum_partial_v4_kernel), the block partials reduced by 8
     groups of 4 chains, every step in float32"""
     z = np.asarray(z, np.float32)

@@ -9,7 +9,7 @@ with the inputs bit-unchanged and no byte outside the output view written.  Oper
 NaN-filled guarded buffers (oracle/guarded.py): a read outside an input view poisons the result.  Workspaces have exactly
 the size the library's own query returns.
 
-The case strings name the kernel the host code dispatches to (mirrored from csrc/fastnsf.hip:766-832 and
+The case strings name the kernel the host code dispatches to (mirrored from csrc/fastnsf.hip:757-823 and
 csrc/train.hip:948-976); the module summary lists which were met.
 """
 import pytest
