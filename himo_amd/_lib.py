@@ -93,6 +93,11 @@ SIGNATURES = {
     "himo_accum_insert": (c_int, [c_int64, c_void_p, c_int, c_void_p, ctypes.POINTER(c_float), c_int, c_void_p, c_void_p, c_int64, c_void_p]),
     "himo_accum_emit": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "himo_accum_status": (c_int, [c_void_p]),
+    "himo_accum_insert_ex": (c_int, [c_int64, c_void_p, c_int, c_void_p, ctypes.POINTER(c_float), c_int, c_void_p, c_void_p, c_int64, c_void_p, c_float,
+                                     c_void_p, c_int, c_float, c_void_p, c_void_p]),
+    "himo_accum_emit_ex": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p,
+                                   c_void_p]),
+    "himo_accum_motion": (c_int, [c_int64, c_void_p, c_int, c_void_p, ctypes.POINTER(c_float), c_void_p, c_void_p]),
     "himo_render_clear": (c_int, [c_void_p, c_int, c_int, c_void_p]),
     "himo_render_splat": (c_int, [c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, ctypes.c_uint32, c_void_p, c_void_p]),
     "himo_render_resolve": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),

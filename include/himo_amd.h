@@ -436,6 +436,34 @@ int himo_accum_emit(const void* d_table, int64_t capacity, const himo_accum_para
                     uint32_t* d_keys, float* d_xyz, unsigned char* d_lag, int32_t* d_count, void* stream);
 int himo_accum_status(void* stream);
 
+/* "sweep accumulation, v2": opt-in additions to v1, PARITY UNPINNED as v1 is (the same docstring is normative; the numpy restatement
+ * is tests/accumulate2_ref.py).  The table, its size, its hash and every v1 result are unchanged: words 6 and 7 of a 32-byte slot,
+ * unused and cleared to 0 in v1, hold Sa and the greatest tag.  The v1 entry points above launch the same kernels with v2 compiled out.
+ *   advect    (himo_accum_insert_ex, d_motion float[n][3] not NULL) after the row test and before the move: a row with a non-finite
+ *             motion component takes no part; s = (mx*mx + my*my) + mz*mz, each operation rounded; iff s >= motion_min2 the row is
+ *             moved, x' = fmaf((float)lag, mx, x), likewise y and z.  The ego-box test stays on the row as given.
+ *   attribute (d_attr not NULL; row i's value is d_attr[i * attr_stride], so column 3 of float[n][4] rows is read in place with
+ *             stride 4) g = v * attr_scale; q = 0 if !(g > 0), 255 if g >= 255, else (uint)floorf(g + 0.5f); Sa += q
+ *   label     (d_label int32[n] not NULL) lab = label if 0 < label < 2^24 else 0; tag = ((255 - lag) << 24) | lab; the slot keeps
+ *             the greatest tag: the label of the freshest row, the largest among ties, whatever the order of arrival
+ *             A call without d_attr (d_label), v1's insert included, leaves Sa (the tag) alone: its rows count as intensity 0 and
+ *             carry no label.
+ *   emit      (himo_accum_emit_ex) beside v1's columns, where the pointer is not NULL:
+ *             d_intensity[row] = (float)(((double)Sa / (double)count) / (double)attr_scale), d_label[row] = tag & 0xFFFFFF (int32)
+ *   motion    (himo_accum_motion) a stored flow less its sweep pair's ego motion: q = E p with the arithmetic of
+ *             himo_rigid_transform, d = q - p, m = flow - d, three rounded subtractions a row after the shared move; h_ego: 16 HOST
+ *             floats, row-major, E = inv(pose1) @ pose0; d_pts float[n][pitch], d_flow and d_motion float[n][3]
+ * Refused with HIMO_ERR_INVALID_ARGUMENT, nothing launched and nothing written: everything v1 refuses; attr_scale not finite or
+ * not > 0 beside a d_attr (insert) or a d_intensity (emit); attr_stride < 1; motion_min2 not finite or negative (both whether or not
+ * their pointer is NULL); d_motion, d_attr, d_label or d_intensity not 4-byte aligned.  Any of the v2 pointers may be NULL. */
+int himo_accum_insert_ex(int64_t n, const float* d_pts, int pitch, const unsigned char* d_skip, const float* h_transform, int lag,
+                         const himo_accum_params* params, void* d_table, int64_t capacity, const float* d_motion, float motion_min2,
+                         const float* d_attr, int attr_stride, float attr_scale, const int32_t* d_label, void* stream);
+int himo_accum_emit_ex(const void* d_table, int64_t capacity, const himo_accum_params* params, int64_t max_rows, int32_t* d_n_rows,
+                       uint32_t* d_keys, float* d_xyz, unsigned char* d_lag, int32_t* d_count, float attr_scale, float* d_intensity,
+                       int32_t* d_label, void* stream);
+int himo_accum_motion(int64_t n, const float* d_pts, int pitch, const float* d_flow, const float* h_ego, float* d_motion, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * The headless viewer's renderer ("point splat, v1"; csrc/render.hip; the rule is the module docstring of himo_amd/view.py and is
  * this build's own: no claim is made about the pixels of any other viewer).
