@@ -1246,7 +1246,15 @@ int himo_dt_loss(int n, const float* d_moved, const float* h_origin, float cell,
  *   d_xhat = (x - mean) * invstd (may alias d_x; NULL: not written, see himo_bn_train_bwd_x); d_y = gelu(gamma * xhat + beta); running statistics updated in place when
  *   given.  himo_bn_train_bwd: d_dy = d loss / d y -> d_dx = d loss / d x (the three-term BatchNorm gradient through the
  *   exact-erf GELU; may alias d_dy), d_dgamma / d_dbeta [ch] (flags bit 0: accumulate).  Every reduction is a fixed tree.
- * himo_bn_fold: eval-mode constants scale = gamma / sqrt(var + eps), shift = beta - mean * scale from the running statistics. */
+ * himo_bn_fold: eval-mode constants scale = gamma / sqrt(var + eps), shift = beta - mean * scale from the running statistics.
+ * A single row (n_img * rows == 1), which torch refuses: var = 0, invstd = 1 / sqrt(eps), xhat = 0 and dx = 0, and the running
+ *   variance takes var unchanged (there is no unbiased estimate): running_var <- (1 - momentum) running_var.
+ * Status: HIMO_ERR_INVALID_ARGUMENT for n_img < 1, rows < 1, ch < 4, ch % 4 != 0, a NULL d_gamma / d_beta / d_mean (fwd, bwd_x) /
+ *   d_invstd / d_dgamma / d_dbeta / d_workspace, exactly one of d_running_mean / d_running_var NULL, and for himo_bn_fold ch < 1 or
+ *   any NULL pointer; HIMO_ERR_UNSUPPORTED for a map that is NULL (d_xhat of the forward pass excepted) or whose base is not
+ *   16-byte aligned, img_stride % 4 != 0, pitch % 4 != 0, pitch < ch, and for n_img * rows * ch / 4 >= 2^31; HIMO_ERR_WORKSPACE
+ *   for workspace_bytes < himo_bn_workspace_bytes(n_img * rows, ch) or a workspace that is not 16-byte aligned.  A refused call
+ *   writes nothing.  himo_bn_workspace_bytes returns 0 for total_rows < 1 or ch < 1. */
 size_t himo_bn_workspace_bytes(int64_t total_rows, int ch);
 int himo_bn_train_fwd(int n_img, int64_t rows, int ch, const float* d_x, int64_t x_img_stride, int x_pitch,
                       const float* d_gamma, const float* d_beta, float eps, float momentum, float* d_running_mean,
