@@ -74,6 +74,9 @@ SIGNATURES = {
     "himo_rigid_refine_workspace_bytes": (c_size_t, [c_int64, c_int, c_int, c_int]),
     "himo_rigid_refine": (c_int, [c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "himo_boxfit_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
+    "himo_boxfit": (c_int, [c_int64, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                            c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "himo_nsf_forward_keep": (c_int, [c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_void_p]),
     "himo_nsf_last_grad": (c_int, [c_int64, c_int, c_void_p, c_void_p, c_void_p]),

@@ -624,6 +624,56 @@ int himo_rigid_refine(int64_t n, const float* d_pc0, int pitch, const float* d_f
                       void* d_workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Cluster boxes (`python -m himo_amd.box_fit`, dataset `boxes_<name>`): one oriented box per cluster of labelled points by the
+ * search-based L-shape fit -- every heading of a fixed integer table is tried, the one with the most edge inliers is kept, ties go
+ * to the smaller area, then to the lower table index (himo_amd/csrc/boxfit.hip).  The reference has no such stage: this one follows
+ * the build's own written rule, "cluster boxes, v1" (the module docstring of himo_amd/box_fit.py is normative): PARITY UNPINNED.
+ * Timed on a synthetic sweep only (profiles/box_fit.txt); nothing has been tried on field data.
+ *
+ *   d_pts float[n][pitch], pitch >= 3 (x, y, z first), raw or compensated as the caller decides; d_labels int32[n], 0 = none.
+ *   The labelled rows SORTED BY LABEL, as for himo_rigid_refine: d_rows int64[n_clustered] the sweep row of every sorted row; cluster
+ *   k (label k + 1) owns the sorted rows offsets[k] .. offsets[k + 1], given on the host (validation) and on the device.
+ *   d_motion float[n][3] or NULL: a displacement per sweep period.  h_dirs: int32[n_dirs][2] on the HOST, read before the call
+ *   returns: 1 <= n_dirs <= HIMO_BOXFIT_MAX_DIRS, every |a|, |b| <= 4096, a*a + b*b > 0.
+ *   quantise  a row is USABLE iff its label > 0, x, y, z are finite and |x*scale|, |y*scale| (one float32 product each) are below
+ *             4194304; X = (int)floorf(x*scale), Y likewise; n = the cluster's usable rows
+ *   state     TOO_FEW iff n < min_points; else TOO_LARGE iff n > max_points or Xmax - Xmin >= 16384 or Ymax - Ymin >= 16384; else
+ *             FITTED.  A cluster that is not FITTED writes its state and n, and zeros elsewhere
+ *   fit       per direction (a, b): u = a X' + b Y', v = -b X' + a Y' over X' = X - Xmin, Y' = Y - Ymin; a row is an edge inlier iff
+ *             min(u - umin, umax - u, v - vmin, vmax - v) <= tol_q << 12; S = the inlier count, A = (umax - umin)(vmax - vmin) in
+ *             int64; the chosen k has the largest S, then the smallest A, then the lowest k.  All integers: order-independent
+ *   box       float64, every operation rounding on its own: n2 = a a + b b, r = sqrt(n2), su = (umin + umax) / 2, sv likewise,
+ *             px = (a su - b sv) / n2, py = (b su + a sv) / n2, cx = ((Xmin + px) + 0.5) / scale, eu = (umax - umin) / (r scale),
+ *             cz = (zmin + zmax) / 2, h = zmax - zmin (the float32 extremes, -0 below +0); the float64 mean of the usable rows'
+ *             motion, rows with a non-finite value left out of sum and count (a fixed summation shape: the same bytes every run)
+ * Outputs: d_info int32[C][12] = state, n, k, S, Xmin, Ymin, umin, umax, vmin, vmax, motion row count, 0; d_box double[C][10] = cx,
+ * cy, cz, eu, ev, h, mx, my, mz, 0.
+ * Refused with HIMO_ERR_INVALID_ARGUMENT, nothing launched and nothing written: a negative count, pitch < 3, n_clustered > n,
+ * clustered rows without clusters, offsets that are negative, decreasing, do not start at 0 or end at n_clustered, NULL or misaligned
+ * where data is required, a refused table, and parameters outside: scale finite and > 0, 0 <= tol_q <= 1024, min_points >= 1,
+ * min_points <= max_points <= 2^20.  n > 2^31 - 1: HIMO_ERR_UNSUPPORTED.  A short, NULL or misaligned (16 bytes) workspace:
+ * HIMO_ERR_WORKSPACE (himo_boxfit_workspace_bytes returns 0 for what it refuses).  n_clusters == 0: HIMO_OK, nothing launched.
+ * One launch, asynchronous on `stream`, whatever the clusters. */
+typedef struct himo_boxfit_params {
+    float scale;           /* sub-units per metre */
+    int32_t tol_q;         /* edge-inlier tolerance, sub-units */
+    int32_t min_points;    /* fewer usable rows: TOO_FEW */
+    int32_t max_points;    /* more usable rows: TOO_LARGE */
+} himo_boxfit_params;
+
+#define HIMO_BOXFIT_FITTED 0
+#define HIMO_BOXFIT_TOO_FEW 1
+#define HIMO_BOXFIT_TOO_LARGE 2
+#define HIMO_BOXFIT_MAX_DIRS 128
+#define HIMO_BOXFIT_CHUNK 1024     /* points the kernel stages in LDS at a time (a size its tests straddle) */
+
+size_t himo_boxfit_workspace_bytes(int64_t n_clustered, int n_clusters, int n_dirs);
+int himo_boxfit(int64_t n, const float* d_pts, int pitch, const int32_t* d_labels, int64_t n_clustered, const int64_t* d_rows,
+                int n_clusters, const int64_t* h_offsets, const int64_t* d_offsets, const float* d_motion, const int32_t* h_dirs,
+                int n_dirs, const himo_boxfit_params* params, int32_t* d_info, double* d_box, void* d_workspace,
+                size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * a10: scene-flow network (voxelise -> encoder/decoder -> per-point flow).
  * The reference's implementation is in the absent OpenSceneFlow submodule: these
  * entry points have NO reference lines to cite beyond the call sites README.md:50 (`save.py`) and the
