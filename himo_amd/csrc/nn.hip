@@ -186,6 +186,7 @@ extern "C" int himo_sqrt_inplace(int64_t n, void* d_values, int dtype_is_f64, vo
     if (n == 0) return HIMO_OK;
     if (!d_values) return HIMO_ERR_INVALID_ARGUMENT;
     const dim3 grid((unsigned)((n + 255) / 256));
+    ProfScope ps("sqrt_kernel", (hipStream_t)stream);
     if (dtype_is_f64) hipLaunchKernelGGL(sqrt_kernel<double>, grid, dim3(256), 0, (hipStream_t)stream, n, (double*)d_values);
     else hipLaunchKernelGGL(sqrt_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, n, (float*)d_values);
     HIMO_LAUNCH_CHECK("sqrt_kernel");

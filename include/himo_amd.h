@@ -184,7 +184,13 @@ int himo_dt0(int64_t n, const float* d_lidar_dt, float* d_dt0, void* d_workspace
  * [r_offsets[s], r_offsets[s+1]) (segments = sweeps of a batch, or instances).  d_q, d_r: [n][3]
  * float32, or float64 when dtype_is_f64.  d_dist2: [nq] SQUARED distance in the same dtype (+inf for
  * an empty reference range); d_idx: [nq] int32 global reference row or -1 (may be NULL).
- * float64 mode is bit-comparable with cKDTree ((dx*dx + dy*dy) + dz*dz, then sqrt by the caller). */
+ * float64 mode is bit-comparable with cKDTree ((dx*dx + dy*dy) + dz*dz, then sqrt by the caller);
+ * float32 mode forms fmaf(dz, dz, fmaf(dy, dy, dx * dx)): within 6 * 2^-24 of the exact minimum.
+ * Among equally distant references the LOWEST row wins, in both dtypes.  A candidate wins only while
+ * its distance is < the best so far, starting from +inf: a reference with a NaN coordinate is never
+ * matched, and a query with a NaN coordinate (or whose candidates are all at +inf) gets +inf and -1,
+ * like an empty range.  The offsets are not validated: they must be ascending, q_offsets[n_segments]
+ * == nq and r_offsets[n_segments] <= nr.  nq == 0 returns HIMO_OK and writes nothing. */
 int himo_nn_search(int n_segments, const int64_t* d_q_offsets, const int64_t* d_r_offsets,
                    int64_t nq, int64_t nr, const void* d_q, const void* d_r, int dtype_is_f64,
                    void* d_dist2, int32_t* d_idx, void* stream);
@@ -197,7 +203,12 @@ int himo_sqrt_inplace(int64_t n, void* d_values, int dtype_is_f64, void* stream)
  * ScoreMetrics.step (tools/test/score.py:223-321) up to, but not including, the bucket bookkeeping
  * (eval.py:99-147), which needs a few dozen records per sweep and stays on the host.
  * One record per (frame, class group, instance id) among the points with eval_mask != 0 and
- * class_lut[category] != 0, in no particular order (sort on the host). */
+ * (class_lut[category] & 3) != 0, in no particular order (sort on the host).
+ * Only the low two bits of a class_lut byte are read: `group` is class_lut[category] & 3, so a byte of 3 opens a third
+ * group, 5 joins group 1, and 4 evaluates nothing.  Only the low 32 bits of an instance id are read: ids that agree
+ * modulo 2^32 (-1 and 2^32 - 1, say) are ONE instance, and `instance` reports the id modulo 2^32 (0 .. 2^32 - 1).
+ * The four means are sums in a fixed order (tests/test_eval_conformance_gpu.py holds them to equal bits of
+ * oracle/eval_oracle.py): a call repeated gives the same bits. */
 typedef struct himo_instance_record {
     int32_t frame;     /* index of the sweep in the batch */
     int32_t group;     /* class_lut value: 1 = CAR, 2 = OTHER_VEHICLES */
@@ -227,7 +238,12 @@ size_t himo_eval_workspace_bytes(int n_frames, int64_t total_points, int64_t max
 /* d_gt: GT flow incl. ego motion [T][3] (data['flow']); d_category uint8[T]; d_instance int64[T] (ids must fit
  * 32 bits); d_eval_mask uint8[T] (e.g. from himo_compdis_batch); h_class_lut: HOST uint8[256].
  * d_records: himo_instance_record[max_records]; d_counts: int64[2] = {selected points, records found}.
- * flags: HIMO_FLAG_POSE_IS_EGO.  Always the float64 chain.  Synchronises the stream once internally. */
+ * flags: HIMO_FLAG_POSE_IS_EGO.  Always the float64 chain.  Synchronises the stream once internally.
+ * d_counts[1] is the number of records FOUND; when it exceeds max_records only max_records of them (any) were
+ * written, each complete: call again with room for all.  total_points == 0 zeroes d_counts and writes nothing
+ * else; with nothing selected d_counts is {0, 0} and no record is written.
+ * sensor_dt: +0.0 and -0.0 are refused (HIMO_ERR_INVALID_ARGUMENT); a NaN is NOT -- it is divided by like any
+ * other value, so vel and mpe come back NaN and cham +inf (points that are all NaN match nothing). */
 int himo_eval_instances(int n_frames, int64_t total_points,
                         const int64_t* d_offsets, const double* d_pose0, const double* d_pose1,
                         const float* d_pc0, int pc_stride, const void* d_gt, const void* d_est,
