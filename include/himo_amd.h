@@ -690,6 +690,50 @@ int himo_boxfit(int64_t n, const float* d_pts, int pitch, const int32_t* d_label
                 size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Box evaluation (`python -m himo_amd.eval_box`): the rotated BEV IoU and the 3-D IoU of oriented boxes, and the greedy matching of
+ * two sets of boxes per sweep by descending BEV IoU (himo_amd/csrc/boxeval.hip).  The reference has no such stage: this one follows
+ * the build's own written rule, "box evaluation, v1" (the module docstring of himo_amd/eval_box.py is normative): PARITY UNPINNED.
+ * Timed on synthetic sweeps only (profiles/box_eval.txt).
+ *
+ *   A rect is double[12]: the four BEV corners x0, y0 .. x3, y3, counter-clockwise; zlo, zhi; area; 0.  The HOST makes rects from box
+ *   rows (the library calls no transcendental).  INVALID (IoU 0 with everything, never matched): a value that is not finite, a
+ *   negative area, zhi < zlo.
+ *   pair      float64, every operation rounding on its own: all corners relative to A's corner 0; disjoint bounds: 0; else A clipped
+ *             by B's four edges in order (Sutherland-Hodgman; inside iff ex (vy - py) - ey (vx - px) >= 0; crossing s + (ds / (ds - de))
+ *             (e - s)); the shoelace fan about vertex 0 times 0.5, clamped to [0, min(areaA, areaB)]; iou = inter / ((areaA + areaB) -
+ *             inter), iou3 from inter times the overlap of the z ranges -- each 0 where its denominator is not > 0
+ *   matching  per sweep, greedy: the pairs with iou >= min_iou in the order greater iou, then lower i, then lower j; a pair is kept
+ *             iff neither its i nor its j was kept before
+ * himo_boxeval_match: n_sweeps sweeps a call; sweep s owns the rects h_off[s] .. h_off[s + 1] of its side's packed table (offsets
+ * int64[n_sweeps + 1], on the host for validation and on the device; the device copy is clamped to the host's totals, not read back).
+ * Outputs, in the packed order: d_match_a int32[rows of A] = the j within the sweep or -1, d_match_b int32[rows of B] = the i or
+ * -1, d_iou_a double[rows of A][2] = iou and iou3 of the kept pair, zeros otherwise.  A sweep with boxes on one side only writes
+ * -1 / zeros for it.  The workspace is the dense candidate store: (rows of A in the call) x (the largest sweep of B) x 8 bytes,
+ * rounded up to 256 (himo_boxeval_workspace_bytes: 0 for what it refuses).  Two launches, asynchronous on `stream`, no host wait.
+ * Refused, nothing launched and nothing written.  HIMO_ERR_INVALID_ARGUMENT: n_sweeps < 0, params NULL or min_iou not finite or
+ * outside (0, 1], host offsets that are NULL, do not start at 0 or decrease, device offsets NULL where the host's name boxes, NULL
+ * or misaligned tables and outputs where data is required.  HIMO_ERR_UNSUPPORTED: a sweep of more than HIMO_BOXEVAL_MAX_BOXES boxes
+ * on a side.  HIMO_ERR_WORKSPACE: a NULL, misaligned (16 bytes) or short workspace.  n_sweeps == 0 or no box at all: HIMO_OK,
+ * nothing launched.
+ * himo_box_iou_pairs: iou and iou3 of the listed pairs, d_pairs int64[n_pairs][2] = (row of A, row of B), d_iou double[n_pairs][2];
+ * an index outside its table gives zeros for that pair.  One launch.  HIMO_ERR_INVALID_ARGUMENT: a negative count, NULL or misaligned
+ * where data is required. */
+typedef struct himo_boxeval_params {
+    double min_iou;        /* the smallest BEV IoU of a candidate pair: finite, 0 < min_iou <= 1 */
+    int32_t reserved[2];   /* 0 */
+} himo_boxeval_params;
+
+#define HIMO_BOXEVAL_MAX_BOXES 1024
+#define HIMO_BOXEVAL_TILE 128      /* rects of B a pair-phase block stages in LDS (a size its tests straddle) */
+
+size_t himo_boxeval_workspace_bytes(int n_sweeps, const int64_t* h_off_a, const int64_t* h_off_b);
+int himo_boxeval_match(int n_sweeps, const double* d_rect_a, const int64_t* h_off_a, const int64_t* d_off_a, const double* d_rect_b,
+                       const int64_t* h_off_b, const int64_t* d_off_b, const himo_boxeval_params* params, int32_t* d_match_a,
+                       int32_t* d_match_b, double* d_iou_a, void* d_workspace, size_t workspace_bytes, void* stream);
+int himo_box_iou_pairs(int64_t n_pairs, const double* d_rect_a, int64_t n_a, const double* d_rect_b, int64_t n_b, const int64_t* d_pairs,
+                       double* d_iou, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * a10: scene-flow network (voxelise -> encoder/decoder -> per-point flow).
  * The reference's implementation is in the absent OpenSceneFlow submodule: these
  * entry points have NO reference lines to cite beyond the call sites README.md:50 (`save.py`) and the
