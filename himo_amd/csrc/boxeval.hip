@@ -29,8 +29,10 @@
 // but no access outside the tables.
 //
 // Built with -ffp-contract=off: every float64 operation rounds on its own, as in the restatement.  Only + - * / and comparisons.
+// The device functions of rules A to D (be_valid, be_pair, be_match_rounds, ...) are in boxiou.h, which boxtrack.hip shares.
 #include "himo_common.h"
 #include "blockops.h"
+#include "boxiou.h"
 #include <math.h>
 
 namespace himo {
@@ -42,110 +44,6 @@ constexpr int kBeMatchThreads = 512;
 constexpr int kBeMax = HIMO_BOXEVAL_MAX_BOXES;
 constexpr int kBeListThreads = 256;
 static_assert(kBePairThreads % kBeTile == 0 && kBeRows % (kBePairThreads / kBeTile) == 0 && kBeMatchThreads % 64 == 0, "boxeval tiling");
-
-__device__ inline bool be_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }
-
-// rule A, the library's side: INVALID iff a value is not finite, the area is negative or zhi < zlo
-__device__ inline bool be_valid(const double (&r)[12]) {
-    bool ok = true;
-#pragma unroll
-    for (int k = 0; k < 12; ++k) ok = ok && be_finite(r[k]);
-    return ok && r[10] >= 0.0 && r[9] >= r[8];
-}
-
-// append (vx, vy) at position c of a polygon of at most NOUT vertices when `on` (rule B4: a vertex beyond NOUT is dropped): selects on
-// the count, no runtime index
-template <int NOUT> __device__ inline void be_emit(double (&ox)[8], double (&oy)[8], int& c, double vx, double vy, bool on) {
-#pragma unroll
-    for (int k = 0; k < NOUT; ++k) {
-        const bool here = on && c == k;
-        ox[k] = here ? vx : ox[k];
-        oy[k] = here ? vy : oy[k];
-    }
-    c += on && c < NOUT ? 1 : 0;
-}
-
-// rules B3, B4: one Sutherland-Hodgman pass of the polygon (x, y)[0 .. n), n <= NIN, against the edge (px, py) -> (qx, qy)
-template <int NIN> __device__ inline void be_clip(double (&x)[8], double (&y)[8], int& n, double px, double py, double qx, double qy) {
-    const double ex = qx - px, ey = qy - py;
-    double d[NIN];
-#pragma unroll
-    for (int m = 0; m < NIN; ++m) d[m] = ex * (y[m] - py) - ey * (x[m] - px);
-    double ox[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, oy[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    int c = 0;
-#pragma unroll
-    for (int m = 0; m < NIN; ++m) {
-        constexpr int kNone = 0;
-        const int nx = m + 1 < NIN ? m + 1 : kNone;                 // (a constant once unrolled)
-        const bool on = m < n, wrap = m + 1 >= n || m + 1 >= NIN;
-        const double sx = x[m], sy = y[m], ds = d[m];
-        const double tx = wrap ? x[0] : x[nx], ty = wrap ? y[0] : y[nx], de = wrap ? d[0] : d[nx];
-        const bool is = ds >= 0.0, ie = de >= 0.0;
-        be_emit<NIN + 1>(ox, oy, c, sx, sy, on && is);
-        const bool cross = on && is != ie;
-        double cx = 0.0, cy = 0.0;
-        if (cross) {
-            const double t = ds / (ds - de);
-            cx = sx + t * (tx - sx);
-            cy = sy + t * (ty - sy);
-        }
-        be_emit<NIN + 1>(ox, oy, c, cx, cy, cross);
-    }
-#pragma unroll
-    for (int k = 0; k < 8; ++k) { x[k] = ox[k]; y[k] = oy[k]; }
-    n = c;
-}
-
-// rules B and C for one pair: A the subject, B the clip polygon
-__device__ inline void be_pair(const double (&A)[12], const double (&B)[12], bool valid, double& iou, double& iou3) {
-    iou = 0.0; iou3 = 0.0;
-    if (!valid) return;
-    // B1: everything relative to A's corner 0
-    const double ox = A[0], oy = A[1];
-    double x[8], y[8], qx[4], qy[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        x[k] = A[2 * k] - ox; y[k] = A[2 * k + 1] - oy;
-        qx[k] = B[2 * k] - ox; qy[k] = B[2 * k + 1] - oy;
-        x[4 + k] = 0.0; y[4 + k] = 0.0;
-    }
-    // B2: the bounds, strictly disjoint in x or y
-    double axl = x[0], axh = x[0], ayl = y[0], ayh = y[0], bxl = qx[0], bxh = qx[0], byl = qy[0], byh = qy[0];
-#pragma unroll
-    for (int k = 1; k < 4; ++k) {
-        axl = x[k] < axl ? x[k] : axl; axh = x[k] > axh ? x[k] : axh;
-        ayl = y[k] < ayl ? y[k] : ayl; ayh = y[k] > ayh ? y[k] : ayh;
-        bxl = qx[k] < bxl ? qx[k] : bxl; bxh = qx[k] > bxh ? qx[k] : bxh;
-        byl = qy[k] < byl ? qy[k] : byl; byh = qy[k] > byh ? qy[k] : byh;
-    }
-    if (axh < bxl || bxh < axl || ayh < byl || byh < ayl) return;
-    // B3, B4: the four passes, in edge order
-    int n = 4;
-    be_clip<4>(x, y, n, qx[0], qy[0], qx[1], qy[1]);
-    be_clip<5>(x, y, n, qx[1], qy[1], qx[2], qy[2]);
-    be_clip<6>(x, y, n, qx[2], qy[2], qx[3], qy[3]);
-    be_clip<7>(x, y, n, qx[3], qy[3], qx[0], qy[0]);
-    // B5, B6
-    if (n < 3) return;
-    double acc = 0.0;
-#pragma unroll
-    for (int m = 1; m < 7; ++m)
-        if (m + 1 < n) acc = acc + ((x[m] - x[0]) * (y[m + 1] - y[0]) - (x[m + 1] - x[0]) * (y[m] - y[0]));
-    double inter = 0.5 * acc;
-    const double aa = A[10], ab = B[10];
-    const double lim = aa < ab ? aa : ab;
-    if (!(inter >= 0.0)) inter = 0.0;
-    if (inter > lim) inter = lim;
-    // C
-    const double uni = (aa + ab) - inter;
-    iou = uni > 0.0 ? inter / uni : 0.0;
-    const double top = A[9] < B[9] ? A[9] : B[9], bot = A[8] > B[8] ? A[8] : B[8];
-    const double dz = top - bot;
-    const double hz = dz > 0.0 ? dz : 0.0;
-    const double inter3 = inter * hz;
-    const double den = (aa * (A[9] - A[8]) + ab * (B[9] - B[8])) - inter3;
-    iou3 = den > 0.0 ? inter3 / den : 0.0;
-}
 
 struct BeArgs {
     int S, sweep0;                   // sweeps of the call; the first sweep of this launch
@@ -167,11 +65,6 @@ __device__ inline void be_extent(const BeArgs& p, int s, int64_t& a0, int& Fa, i
     lo = lo < 0 ? 0 : (lo > p.nb ? p.nb : lo);
     hi = hi < lo ? lo : (hi > p.nb ? p.nb : hi);
     b0 = lo; Fb = (int)(hi - lo < p.pitch ? hi - lo : p.pitch);
-}
-
-__device__ inline void be_load(const double* __restrict__ r, double (&v)[12]) {
-#pragma unroll
-    for (int k = 0; k < 12; ++k) v[k] = r[k];
 }
 
 __global__ __launch_bounds__(kBePairThreads) void be_pair_kernel(BeArgs p) {
@@ -204,7 +97,7 @@ __global__ __launch_bounds__(kBePairThreads) void be_pair_kernel(BeArgs p) {
 
 __global__ __launch_bounds__(kBeMatchThreads) void be_match_kernel(BeArgs p) {
     __shared__ int s_rb[kBeMax], s_cb[kBeMax], s_ma[kBeMax], s_mb[kBeMax];      // a row's best column, a column's best row, the matching
-    const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6, s = p.sweep0 + (int)blockIdx.x;
+    const int t = (int)threadIdx.x, s = p.sweep0 + (int)blockIdx.x;
     int64_t a0, b0;
     int Fa, Fb;
     be_extent(p, s, a0, Fa, b0, Fb);
@@ -212,42 +105,7 @@ __global__ __launch_bounds__(kBeMatchThreads) void be_match_kernel(BeArgs p) {
     for (int i = t; i < kBeMax; i += kBeMatchThreads) { s_rb[i] = -2; s_cb[i] = -2; s_ma[i] = -1; s_mb[i] = -1; }      // -2: not looked at yet
     __syncthreads();
     const double* M = p.M + (size_t)a0 * (size_t)p.pitch;
-    const int bound = (Fa < Fb ? Fa : Fb) + 1;
-    for (int round = 0; round < bound; ++round) {
-        // a wave per free row whose best is unknown or taken: the greatest key, then the lowest j
-        for (int i = wave; i < Fa; i += kBeMatchThreads / 64) {
-            const int had = s_rb[i];
-            if (s_ma[i] >= 0 || had == -1 || (had >= 0 && s_mb[had] < 0)) continue;       // (wave-uniform)
-            unsigned long long best = 0ull;
-            int bj = 0x7fffffff;
-            for (int j = lane; j < Fb; j += 64) {
-                const unsigned long long k = s_mb[j] < 0 ? (unsigned long long)__double_as_longlong(M[(size_t)i * p.pitch + j]) : 0ull;
-                if (k > best) { best = k; bj = j; }
-            }
-            const unsigned long long top = wave_max_u64(best);
-            const unsigned long long low = wave_max_u64(top > 0ull && best == top ? (unsigned long long)(0xffffffffu - (unsigned)bj) : 0ull);
-            if (lane == 0) s_rb[i] = top > 0ull ? (int)(0xffffffffu - (unsigned)low) : -1;
-        }
-        // a thread per free column whose best is unknown or taken: the greatest key, then the lowest i
-        for (int j = t; j < Fb; j += kBeMatchThreads) {
-            const int had = s_cb[j];
-            if (s_mb[j] >= 0 || had == -1 || (had >= 0 && s_ma[had] < 0)) continue;
-            unsigned long long best = 0ull;
-            int bi = -1;
-            for (int i = 0; i < Fa; ++i) {
-                const unsigned long long k = s_ma[i] < 0 ? (unsigned long long)__double_as_longlong(M[(size_t)i * p.pitch + j]) : 0ull;
-                if (k > best) { best = k; bi = i; }
-            }
-            s_cb[j] = bi;
-        }
-        __syncthreads();
-        int kept = 0;
-        for (int i = t; i < Fa; i += kBeMatchThreads) {
-            const int j = s_rb[i];
-            if (s_ma[i] < 0 && j >= 0 && s_cb[j] == i) { s_ma[i] = j; s_mb[j] = i; kept = 1; }      // (s_cb[j] == i names one row a column)
-        }
-        if (!__syncthreads_or(kept)) break;                         // (a barrier; the same answer in every thread)
-    }
+    be_match_rounds<kBeMatchThreads>(M, p.pitch, Fa, Fb, s_rb, s_cb, s_ma, s_mb);
     // the kept pairs: rules B and C once more, the same operations as in the pair phase
     for (int i = t; i < Fa; i += kBeMatchThreads) {
         const int j = s_ma[i];

@@ -734,6 +734,61 @@ int himo_box_iou_pairs(int64_t n_pairs, const double* d_rect_a, int64_t n_a, con
                        double* d_iou, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Box tracking (`python -m himo_amd.track`, dataset `tracks_<name>`): identities of oriented boxes over the sweeps of a scene -- a
+ * constant-velocity prediction, the rotated BEV IoU and greedy matching of box evaluation v1 between live tracks and a sweep's boxes,
+ * an alpha-beta update, births and deaths (himo_amd/csrc/boxtrack.hip).  The reference has no such stage: this one follows the build's
+ * own written rule, "box tracking, v1" (the module docstring of himo_amd/track.py is normative): PARITY UNPINNED.  Timed on synthetic
+ * scenes only (profiles/box_track.txt); nothing has been tried on field data.
+ *
+ *   A detection row is double[12]: x, y, z, l, w, h, c, s, vx, vy, 0, 0 in the scene frame, (c, s) the unit heading.  The HOST makes
+ *   them from box rows and poses (the library calls no transcendental).  INVALID (never matched, never a track, id -1): a value that
+ *   is not finite or a negative extent.
+ *   Scene n owns the sweeps h_sweep_off[n] .. h_sweep_off[n + 1] (int64[n_scenes + 1]); sweep k owns the rows h_det_off[k] ..
+ *   h_det_off[k + 1] of d_det (int64[n_sweeps + 1]); both on the host for validation and on the device, where the copies are clamped
+ *   to the host's totals and to the cap, not read back.  h_dt / d_dt double[n_sweeps]: the time from the sweep before; a scene's first
+ *   is not read, every other must be finite and > 0.
+ *   step      per live track px = x + vx dt, py likewise; the rects of tracks and detections as in box evaluation v1 with (c, s) given;
+ *             BEV IoU with the track the subject; greedy matching at min_iou (greater IoU, then lower track slot, then lower j);
+ *             matched: x = px + alpha (dx - px), z, l, w, h, c, s the detection's, vx = vx + beta (dvx - vx) [vel_mode 0] or vx + beta
+ *             ((dx - px) / dt) [vel_mode 1], hits + 1, misses 0; unmatched: x = px, misses + 1, dead iff misses > max_age; an unmatched
+ *             valid detection starts a track in ascending j with the scene's next id (from 0, never reused) while the table holds
+ *             fewer than max_tracks, else id -1 and the scene's overflow count goes up; the table keeps its order, births behind.
+ * Outputs, in the packed order: d_track_id int32[rows] (the id or -1), d_age int32[rows] (the track's hits after the step, 0 for -1),
+ * d_state double[rows][4] (x, y, vx, vy of the track after the step, zeros for -1), d_iou double[rows] (the matched pair's BEV IoU, 0
+ * for births and -1), d_live int32[n_sweeps] (live tracks after the step), d_scene_info int32[n_scenes][2] (ids issued, overflow).
+ * The workspace is a slice per scene: the dense candidate matrix max_tracks x (the largest sweep of the call) x 8 bytes, the rects and
+ * the track state (himo_boxtrack_workspace_bytes: 0 for what it refuses).  ONE launch (one per 32768 scenes), one 512-thread workgroup
+ * per scene, asynchronous on `stream`, no host wait; the same inputs give the same bytes.
+ * Refused, nothing launched and nothing written.  HIMO_ERR_INVALID_ARGUMENT: n_scenes < 0, params NULL or outside (min_iou finite in
+ * (0, 1]; alpha, beta finite in [0, 1]; max_age 0..255; max_tracks 1..HIMO_BOXTRACK_MAX; vel_mode 0 or 1), host offsets that are NULL,
+ * do not start at 0 or decrease, a dt that is read and is not finite and > 0, NULL or misaligned tables and outputs where data is
+ * required.  HIMO_ERR_UNSUPPORTED: a sweep of more than HIMO_BOXTRACK_MAX boxes, more than 2^31 - 2 sweeps.  HIMO_ERR_WORKSPACE: a
+ * NULL, misaligned (16 bytes) or short workspace.  n_scenes == 0: HIMO_OK, nothing launched.
+ * himo_boxtrack_slabbed is himo_boxtrack with the scenes per launch given (>= 1): what the tests use to cross a launch boundary
+ * without a large batch. */
+typedef struct himo_boxtrack_params {
+    double min_iou;        /* the smallest BEV IoU of a candidate pair: finite, 0 < min_iou <= 1 */
+    double alpha;          /* position gain, finite, 0..1 */
+    double beta;           /* velocity gain, finite, 0..1 */
+    int32_t max_age;       /* a track dies after more than this many sweeps without a match, 0..255 */
+    int32_t max_tracks;    /* live tracks of a scene, 1..HIMO_BOXTRACK_MAX */
+    int32_t vel_mode;      /* 0: the velocity follows the boxes' ("box"); 1: it follows the position residual ("track") */
+    int32_t reserved;      /* 0 */
+} himo_boxtrack_params;
+
+#define HIMO_BOXTRACK_MAX 512      /* live tracks of a scene and boxes of a sweep */
+
+size_t himo_boxtrack_workspace_bytes(int n_scenes, const int64_t* h_sweep_off, const int64_t* h_det_off, const himo_boxtrack_params* params);
+int himo_boxtrack(int n_scenes, const double* d_det, const int64_t* h_sweep_off, const int64_t* d_sweep_off, const int64_t* h_det_off,
+                  const int64_t* d_det_off, const double* h_dt, const double* d_dt, const himo_boxtrack_params* params, int32_t* d_track_id,
+                  int32_t* d_age, double* d_state, double* d_iou, int32_t* d_live, int32_t* d_scene_info, void* d_workspace,
+                  size_t workspace_bytes, void* stream);
+int himo_boxtrack_slabbed(int n_scenes, const double* d_det, const int64_t* h_sweep_off, const int64_t* d_sweep_off, const int64_t* h_det_off,
+                          const int64_t* d_det_off, const double* h_dt, const double* d_dt, const himo_boxtrack_params* params,
+                          int32_t* d_track_id, int32_t* d_age, double* d_state, double* d_iou, int32_t* d_live, int32_t* d_scene_info,
+                          void* d_workspace, size_t workspace_bytes, int slab_scenes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * a10: scene-flow network (voxelise -> encoder/decoder -> per-point flow).
  * The reference's implementation is in the absent OpenSceneFlow submodule: these
  * entry points have NO reference lines to cite beyond the call sites README.md:50 (`save.py`) and the
