@@ -89,6 +89,7 @@ extern "C" size_t himo_abi_sizeof(const char* struct_name) {
     if (!strcmp(struct_name, "himo_boxfit_params")) return sizeof(himo_boxfit_params);
     if (!strcmp(struct_name, "himo_boxeval_params")) return sizeof(himo_boxeval_params);
     if (!strcmp(struct_name, "himo_boxtrack_params")) return sizeof(himo_boxtrack_params);
+    if (!strcmp(struct_name, "himo_trackflow_params")) return sizeof(himo_trackflow_params);
     if (!strcmp(struct_name, "himo_raymap_params")) return sizeof(himo_raymap_params);
     if (!strcmp(struct_name, "himo_accum_params")) return sizeof(himo_accum_params);
     if (!strcmp(struct_name, "himo_camera")) return sizeof(himo_camera);

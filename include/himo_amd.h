@@ -789,6 +789,58 @@ int himo_boxtrack_slabbed(int n_scenes, const double* d_det, const int64_t* h_sw
                           void* d_workspace, size_t workspace_bytes, int slab_scenes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Track-consistent flow (`python -m himo_amd.track_flow`, dataset `<name>_track`): the velocity of a box becomes the mean over its track
+ * in a window of sweeps, and the points of the box are moved by it (himo_amd/csrc/trackflow.hip).  The reference has no such stage: this
+ * one follows the build's own written rule, "track flow, v1" (the module docstring of himo_amd/track_flow.py is normative): PARITY
+ * UNPINNED.  Timing (synthetic tables only, profiles/track_flow.txt; nothing has been tried on field data): 16 scenes of 150 sweeps of 300 boxes and
+ * 120k points: plan 0.56 ms, apply 3.87 ms in 16 launches (1.96 x himo_accum_motion on the same rows); one 120k-row sweep applied alone 11.2 us.
+ *
+ *   The box tables are packed in the order of himo_boxtrack: scene n owns the sweeps h_sweep_off[n] .. h_sweep_off[n + 1], sweep k the
+ *   rows h_det_off[k] .. h_det_off[k + 1] and scene n the words h_id_off[n] .. h_id_off[n + 1] of the workspace (one per track id of the
+ *   scene: ids are 0 .. n_ids - 1); every table on the host for validation and on the device, where the copies are clamped to the host's
+ *   totals and to the cap, not read back.  d_id int32[rows] (-1: no track), d_w double[rows][3] (the box velocity in the scene frame, made
+ *   by the HOST), d_boxes float[rows][12] (columns 7..9: the float32 velocity in the sensor frame), d_U double[n_sweeps][9] (the rotation
+ *   back into the sweep's sensor frame).  A row is USABLE iff 0 <= id < n_ids and w is finite.
+ *   plan      L(id) = the USABLE rows of the scene with that id (integer atomics); a USABLE row of sweep k on a track with L >= min_len:
+ *             S = 0, m = 0; for j = max(first, k - half) .. min(last, k + half) ascending, if sweep j holds a USABLE row of the id (the
+ *             lowest such row) S += w_j, m += 1; wbar = S / m; u = U_k wbar, each component ((U0 x + U1 y) + U2 z); d_s = u sensor_dt;
+ *             d_b = (double)v32 sensor_dt; STATIC (2) iff ((d_s.x^2 + d_s.y^2) + d_s.z^2) < motion_min^2, else MOVING (1); every other
+ *             row NONE (0) with zeros.  d_state int32[rows], d_m int32[rows], d_shift float[rows][3] = (float)(d_s - d_b), d_disp
+ *             float[rows][3] = (float)d_s, d_u double[rows][3].  One workgroup per (scene, sweep).
+ *   apply     over the packed point rows of n_sweeps sweeps (h_pt_off int64[n_sweeps + 1] from 0; d_pc0 float[rows][pitch], pitch >= 3;
+ *             d_flow float[rows][3]; d_label int32[rows]; d_E float[n_sweeps][12], the first three rows of inv(pose1) pose0); sweep k
+ *             owns the plan rows h_box_off[k] .. h_box_off[k + 1] (absolute, at most n_box_rows), d_sorted_id / d_sorted_row int32 aligned
+ *             with them: the sweep's label ids ascending (stable) and each one's row inside the sweep.  A row with label > 0 whose label
+ *             is among the ids (the lowest row among equals), whose box is not NONE and whose three flow values are finite is rewritten:
+ *             STATIC: a - pc0 with a = E pc0 (the arithmetic of himo_rigid_transform); MOVING, mode 0: flow + shift; MOVING, mode 1:
+ *             (a - pc0) + disp; float32, every operation rounded.  Every other row keeps the bytes of its flow.  d_out float[rows][3];
+ *             d_counts int32[n_sweeps][2]: rows written as MOVING, as STATIC.
+ * Asynchronous on `stream`, no host wait; the only atomics are integer adds: the same inputs give the same bytes.
+ * Refused, nothing launched and nothing written.  HIMO_ERR_INVALID_ARGUMENT: a negative count, pitch < 3, params NULL or outside (below),
+ * host offsets that are NULL, do not start at 0 (h_box_off: are negative or pass n_box_rows) or decrease, NULL or misaligned tables and
+ * outputs where data is required.  HIMO_ERR_UNSUPPORTED: a sweep of more than HIMO_BOXTRACK_MAX boxes, more than 2^31 - 2 sweeps or ids.
+ * HIMO_ERR_WORKSPACE: a NULL, misaligned (16 bytes) or short workspace (himo_trackflow_workspace_bytes: 0 for what it refuses).
+ * n_scenes == 0 / n_sweeps == 0: HIMO_OK, nothing launched. */
+typedef struct himo_trackflow_params {
+    double sensor_dt;      /* seconds between sweeps: finite, > 0 */
+    double motion_min;     /* a box that moves less than this a sweep is STATIC [m]: finite, >= 0 */
+    int32_t half;          /* the window is the sweeps k - half .. k + half, 0..8 */
+    int32_t min_len;       /* a track with this many USABLE rows is CONFIRMED, >= 1 */
+    int32_t mode;          /* MOVING rows: 0 flow + shift ("shift"), 1 the ego-motion flow + disp ("replace") */
+    int32_t reserved;      /* 0 */
+} himo_trackflow_params;
+
+size_t himo_trackflow_workspace_bytes(int n_scenes, const int64_t* h_sweep_off, const int64_t* h_det_off, const int64_t* h_id_off);
+int himo_trackflow_plan(int n_scenes, const int64_t* h_sweep_off, const int64_t* d_sweep_off, const int64_t* h_det_off,
+                        const int64_t* d_det_off, const int64_t* h_id_off, const int64_t* d_id_off, const int32_t* d_id, const double* d_w,
+                        const float* d_boxes, const double* d_U, const himo_trackflow_params* params, int32_t* d_state, int32_t* d_m,
+                        float* d_shift, float* d_disp, double* d_u, void* d_workspace, size_t workspace_bytes, void* stream);
+int himo_trackflow_apply(int n_sweeps, const int64_t* h_pt_off, const int64_t* d_pt_off, const float* d_pc0, int pitch, const float* d_flow,
+                         const int32_t* d_label, const float* d_E, const int64_t* h_box_off, const int64_t* d_box_off, int64_t n_box_rows,
+                         const int32_t* d_sorted_id, const int32_t* d_sorted_row, const int32_t* d_state, const float* d_shift,
+                         const float* d_disp, const himo_trackflow_params* params, float* d_out, int32_t* d_counts, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * a10: scene-flow network (voxelise -> encoder/decoder -> per-point flow).
  * The reference's implementation is in the absent OpenSceneFlow submodule: these
  * entry points have NO reference lines to cite beyond the call sites README.md:50 (`save.py`) and the
