@@ -118,6 +118,8 @@ SIGNATURES = {
     "himo_render_clear": (c_int, [c_void_p, c_int, c_int, c_void_p]),
     "himo_render_splat": (c_int, [c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, ctypes.c_uint32, c_void_p, c_void_p]),
     "himo_render_resolve": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "himo_render_lines": (c_int, [c_int64, c_void_p, c_void_p, c_int, ctypes.c_uint32, c_void_p, c_void_p]),
+    "himo_render_composite": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, ctypes.c_uint32, c_void_p, c_void_p]),
 }
 
 FLAG_F32_CHAIN = 0x1

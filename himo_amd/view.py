@@ -40,6 +40,50 @@ G. Eye-dome lighting, when ``edl > 0`` (depth made readable in a flat-coloured c
    channel becomes ``floor(c * shade + 0.5)``.  (``log2`` / ``exp2`` differ from numpy's by a few ulp: a channel may differ from
    the restatement by one level here, nowhere else.)
 
+The rule -- "line overlay, v1" (normative)
+===========================================
+Oriented boxes (``boxes_<name>``, with their velocities) and track trails (``tracks_<name>``) are drawn as line segments over the
+panels.  PARITY UNPINNED: the reference has no such stage; the rule is this build's own and is checked bit for bit against
+``tests/renderlines_ref.py``.  All float arithmetic is float32 and every operation rounds on its own
+(``himo_amd/csrc/renderlines.hip`` is built with ``-ffp-contract=off``, without fast-math); everything after rule C is integer
+arithmetic.
+
+The overlay has ITS OWN buffer, ``lines``: one uint64 per pixel, ``[height][width]``; ``~0`` is empty, otherwise the word is
+``(zq << 32) | segment index``.  ``himo_render_clear`` clears it.  The point buffer and ``himo_render_resolve`` are untouched by it.
+A segment is a float32 row ``[6]`` = ``x0, y0, z0, x1, y1, z1`` in the frame the camera matrix reads; its ends are ``a`` and ``b``.
+
+A. Camera coordinates.  Both ends by rule B of the point splat: the same expression in the same order.  The segment is dropped when
+   any of the six values is not finite.
+B. Depth clip.  Dropped when both ``zc < znear`` or both ``zc > zfar``.  Otherwise each end is replaced on its own, both replacements
+   computed from the ORIGINAL pair, so that their order cannot matter.  End ``a`` with ``za < znear``: ``t = (znear - za) / (zb - za)``,
+   ``xa' = xa + t * (xb - xa)``, ``ya' = ya + t * (yb - ya)``, ``za' = znear``; with ``za > zfar`` the same with ``zfar`` in place of
+   ``znear``; otherwise unchanged.  End ``b`` symmetrically: ``t = (znear - zb) / (za - zb)``, ``xb' = xb + t * (xa - xb)``, ...
+C. Screen.  Each end is projected by rule C of the point splat.  Dropped when any of ``u0, v0, u1, v1`` is not finite or has
+   ``|.| >= 2^20`` (a documented limit of v1: it keeps everything below in exact integers).  The end pixels are ``X = floor(u)``,
+   ``Y = floor(v)`` as int32; ``zq0`` and ``zq1`` by rule D of the point splat from the clipped ``zc``.
+D. Pixels.  ``dx = X1 - X0``, ``dy = Y1 - Y0``, ``steps = max(|dx|, |dy|)``.  For ``k = 0 .. steps``, in int64 with FLOOR division:
+   ``x_k = X0 + floordiv(2 k dx + steps, 2 steps)``, ``y_k`` likewise, ``zq_k = zq0 + floordiv(k (zq1 - zq0), steps)``; for
+   ``steps = 0`` the one pixel ``(X0, Y0)`` with ``zq0``.  So ``k = 0`` is exactly end ``a`` and ``k = steps`` exactly end ``b``.  A half-way
+   case rounds UP (towards +x, +y), whichever way the segment runs: ``x_k = floor(X0 + k dx / steps + 1/2)`` exactly, a function of the
+   point alone, and ``floordiv((steps - k)(zq0 - zq1), steps) = floordiv(k (zq1 - zq0), steps) - (zq1 - zq0)``; so the walk from ``b`` to
+   ``a`` visits the pixels and depths of the walk from ``a`` to ``b`` in reverse, and swapping the ends of a segment changes no bit (what
+   is NOT symmetric is a reflection of the segment: the mirror image of a half-way pixel rounds the other way).  Depth is linear along
+   the SCREEN segment; under a pinhole camera that is an approximation: THE OVERLAY MAKES NO CLAIM OF
+   PERSPECTIVE-CORRECT DEPTH.
+E. Write.  For every ``k`` and every ``(ddx, ddy)`` with ``ddx^2 + ddy^2 <= half_px^2`` (``half_px`` 0..3) whose pixel
+   ``(x_k + ddx, y_k + ddy)`` lies inside the image: the 64-bit minimum of the word and ``(zq_k << 32) | (index_base + i)``.  The nearest
+   segment wins, the lowest index among equal ``zq``; the buffer is a pure function of the set of (segment, index), whatever the launch
+   order and the split over calls.
+F. Composite, per pixel, onto an RGB image that ``himo_render_resolve`` has written.  An empty ``lines`` word leaves the three bytes
+   alone.  With the depth test on, a non-empty point word whose ``zq`` is LESS than the line's leaves them alone too; on equal ``zq`` the
+   line wins; an empty point word never hides a line.  Otherwise the pixel takes ``colors[idx]`` (uint32 ``r | g << 8 | b << 16``), or
+   ``neutral`` when ``idx >= n_colors``.  Lines are not eye-dome shaded.
+
+What is drawn (host code, float64, cast to float32 at the end): ``box_segments`` -- per box its 12 edges, a heading mark and, for a
+MOVING box, a velocity arrow; ``trail_segments`` -- per tracked box the polyline of its id's stored positions over the last sweeps.
+Not part of v1: perspective-correct line depth, anti-aliasing or alpha, text labels, filled faces or meshes, a 2-D clip of segments
+beyond the 2^20 bound, trails from coasting tracks (``track`` v1 does not store them).  Nothing has been tried on field data.
+
 Cameras.  ``Camera.bev``: orthographic, looking down, world x to the right and world y UP in the image.  ``Camera.look_at``: a
 pinhole with a vertical field of view.  ``Camera.from_view`` takes the four quantities of the reference's camera keyframes
 (``front``, ``lookat``, ``up``, ``zoom``; tools/animation_video.py:36) and maps them onto ``look_at``: the eye sits at
@@ -47,7 +91,7 @@ pinhole with a vertical field of view.  ``Camera.from_view`` takes the four quan
 convention is not claimed.  ``spline_path`` is the clamped cubic spline through keyframes that ``interpolate_trajectory``
 (tools/animation_video.py:32) describes, in numpy.
 
-Not built: text in the image, video encoding, boxes or meshes, an interactive window, per-instance scores in the panel
+Not built: text in the image, video encoding, meshes, an interactive window, per-instance scores in the panel
 (``himo_amd.eval`` prints those).  Many sweeps in one frame are a stage of their own: ``python -m himo_amd.accumulate`` writes them as
 scene files, which ``--data_dir O --res_names raw`` then shows.
 """
@@ -229,12 +273,71 @@ class Renderer:
         self._lut = torch.from_numpy(sequential_lut().view(np.int32)).to(self.device)
         self._palette = torch.from_numpy(palette().view(np.int32)).to(self.device)
         self._top = 0
+        self._lines = None                                        # the overlay's buffer: allocated by the first clear_lines() / lines()
+        self._resolved = False
         self.clear()
 
     def clear(self) -> None:
+        """empties the panel: the point buffer and, when one was allocated, the lines buffer (a renderer that never draws lines
+        launches one clear)"""
         from . import _lib
         _lib.check(self.lib.himo_render_clear(self._vis.data_ptr(), self.width, self.height, _lib.stream_handle()), "himo_render_clear")
         self._top = 0
+        if self._lines is not None:
+            self.clear_lines()
+
+    def clear_lines(self) -> None:
+        """empties the lines buffer of "line overlay, v1" (allocated here on first use); the point buffer stays"""
+        import torch
+        from . import _lib
+        if self._lines is None:
+            self._lines = torch.empty((self.height, self.width), dtype=torch.int64, device=self.device)
+        _lib.check(self.lib.himo_render_clear(self._lines.data_ptr(), self.width, self.height, _lib.stream_handle()), "himo_render_clear")
+
+    def lines(self, segments, half_px: int = 0, index_base: int = 0, camera: Camera | None = None) -> None:
+        """Add segments to the lines buffer (rules A-E of "line overlay, v1"): ``segments`` (n, 6) float32 rows ``x0, y0, z0, x1, y1,
+        z1`` (array or tensor), ``half_px`` 0..3 the disc radius round every pixel of the walk, ``index_base`` the index of the first
+        segment in the buffer's keys (``composite`` reads ``colors`` by it)."""
+        import torch
+        from . import _lib
+        if camera is None:
+            raise ValueError("lines: a camera is required")
+        if (int(camera.width), int(camera.height)) != (self.width, self.height):
+            raise ValueError(f"lines: the camera renders {camera.width} x {camera.height}, the buffer is {self.width} x {self.height}")
+        seg = self._on_device(segments, torch.float32, None, "segments")
+        if seg.dim() != 2 or seg.shape[1] != 6:
+            raise ValueError(f"segments are rows of x0, y0, z0, x1, y1, z1, not {tuple(seg.shape)}")
+        n = int(seg.shape[0])
+        if not 0 <= int(index_base) <= int(index_base) + n <= 1 << 32:
+            raise ValueError(f"lines: segments {index_base}..{int(index_base) + n} do not fit the 32 index bits of a key")
+        if self._lines is None:
+            self.clear_lines()
+        _lib.check(self.lib.himo_render_lines(n, _lib.ptr(seg), ctypes.addressof(camera), int(half_px), int(index_base), self._lines.data_ptr(),
+                                              _lib.stream_handle()), "himo_render_lines")
+
+    def composite(self, colors, depth_test: bool = False, neutral: int = NEUTRAL):
+        """Rule F of "line overlay, v1": the lines buffer over the image the last ``resolve`` returned, which is written in place and
+        returned.  ``colors``: uint32 ``r | g << 8 | b << 16`` per segment index (an index past it takes ``neutral``); ``depth_test``:
+        a nearer point hides a line (the default draws lines on top)."""
+        import torch
+        from . import _lib
+        if not self._resolved:
+            raise ValueError("composite: nothing was resolved yet: lines are drawn over the image resolve() made")
+        if self._lines is None:
+            self.clear_lines()
+        t = colors if isinstance(colors, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(colors, dtype=np.uint32).view(np.int32))
+        col = self._on_device(t, torch.int32, None, "colors")
+        if col.dim() != 1:
+            raise ValueError(f"colors are one uint32 per segment index, not {tuple(col.shape)}")
+        _lib.check(self.lib.himo_render_composite(self._lines.data_ptr(), self._vis.data_ptr() if depth_test else None, self.width, self.height,
+                                                  _lib.ptr(col) if col.numel() else None, int(col.numel()), int(neutral), self._rgb.data_ptr(),
+                                                  _lib.stream_handle()), "himo_render_composite")
+        return self._rgb
+
+    def line_buffer(self):
+        """the raw lines buffer, (H, W) int64 on the device holding the uint64 words (``EMPTY`` = -1), as ``visibility()`` is for
+        the points; None before the first ``clear_lines()`` / ``lines()``"""
+        return self._lines
 
     def _on_device(self, a, dtype, shape, what):
         import torch
@@ -302,6 +405,7 @@ class Renderer:
         sh.n_attr = int(attr.numel())
         _lib.check(self.lib.himo_render_resolve(self._vis.data_ptr(), self.width, self.height, ctypes.addressof(sh), self._rgb.data_ptr(),
                                                 _lib.stream_handle()), "himo_render_resolve")
+        self._resolved = True
         return self._rgb
 
     def visibility(self):
@@ -386,14 +490,223 @@ def _speed(data: dict, res_name: str, sensor_dt: float) -> np.ndarray:
     return (np.linalg.norm(np.asarray(_need(data, res_name), dtype=np.float64) - pose_flow, axis=1) / float(sensor_dt)).astype(np.float32)
 
 
+# --------------------------------------------------------------------------------------------------------------------------
+# boxes and trails -> segments (host, float64; what "line overlay, v1" draws)
+# --------------------------------------------------------------------------------------------------------------------------
+BOX_COLOR_BY = ("fixed", "track", "moving")
+# the ring of a box face in (sx, sy): front-left, rear-left, rear-right, front-right (counter-clockwise seen from above; +x of the
+# box is its front)
+BOX_RING = ((1, 1), (-1, 1), (-1, -1), (1, -1))
+SEGMENTS_STATIC, SEGMENTS_MOVING = 13, 16
+ARROW_HEAD_BACK, ARROW_HEAD_SIDE = 0.25, 0.125
+
+
+def box_corners(row) -> np.ndarray:
+    """float64 [8][3]: the corners of one ``box_fit`` row (``x, y, z, l, w, h, yaw``; z is the box CENTRE), the bottom ring in the
+    order of ``BOX_RING`` and then the top ring.  With ``c, s = cos yaw, sin yaw`` the corner ``(sx, sy, sz)`` is ``X = x + sx (l / 2) c
+    - sy (w / 2) s``, ``Y = y + sx (l / 2) s + sy (w / 2) c``, ``Z = z + sz (h / 2)``."""
+    x, y, z, l, w, h, yaw = (float(v) for v in np.asarray(row, dtype=np.float64)[:7])
+    c, s = np.cos(yaw), np.sin(yaw)
+    return np.array([[x + sx * (l / 2) * c - sy * (w / 2) * s, y + sx * (l / 2) * s + sy * (w / 2) * c, z + sz * (h / 2)]
+                     for sz in (-1, 1) for sx, sy in BOX_RING], dtype=np.float64)
+
+
+def box_valid(rows) -> np.ndarray:
+    """bool [F]: every value of the row finite and no negative extent (the rows ``track`` takes as valid)"""
+    rows = np.asarray(rows, dtype=np.float64).reshape(-1, 12)
+    return np.isfinite(rows).all(axis=1) & (rows[:, 3:6] >= 0).all(axis=1)
+
+
+def box_moving(rows, sensor_dt: float, motion_min: float) -> np.ndarray:
+    """bool [F]: ``hypot(vx, vy) * sensor_dt >= motion_min``, the MOVING test of ``box_fit`` on the stored velocity"""
+    rows = np.asarray(rows, dtype=np.float64).reshape(-1, 12)
+    with np.errstate(all="ignore"):
+        return np.hypot(rows[:, 7], rows[:, 8]) * float(sensor_dt) >= float(motion_min)
+
+
+def box_segments(rows, sensor_dt: float = 0.1, motion_min: float = 0.05, arrow_s: float = 0.5):
+    """``box_fit``'s ``[F][12]`` rows -> (segments float32 [S][6], box_of_segment int64 [S]).  A row with a value that is not finite
+    or with a negative extent is skipped.  Per box, in this order (corners as ``box_corners`` numbers them, 0..3 the bottom ring, 4..7
+    the top ring):
+
+      0..3    the bottom ring 0-1, 1-2, 2-3, 3-0
+      4..7    the top ring 4-5, 5-6, 6-7, 7-4
+      8..11   the uprights 0-4, 1-5, 2-6, 3-7
+      12      the heading mark: from the centre of the top face ``T = (x, y, z + h / 2)`` to the midpoint of its front edge
+              ``(x + (l / 2) c, y + (l / 2) s, z + h / 2)``
+      13..15  only for a MOVING box (``box_moving``) and ``arrow_s > 0``: the velocity arrow on the top face.  With ``d = (vx, vy) *
+              arrow_s`` (the way the box travels in ``arrow_s`` seconds), the tip ``P = T + d`` and the left normal ``n = (-d_y, d_x)``:
+              the shaft ``T -> P``, then the two head strokes ``P -> P - 0.25 d + 0.125 n`` and ``P -> P - 0.25 d - 0.125 n``
+
+    so a static box gives 13 segments and a moving one 16.  Everything in float64, cast to float32 at the end."""
+    rows = np.asarray(rows, dtype=np.float64).reshape(-1, 12)
+    valid, moving = box_valid(rows), box_moving(rows, sensor_dt, motion_min)
+    segs, owner = [], []
+    for f in np.flatnonzero(valid):
+        row = rows[f]
+        q = box_corners(row)
+        pairs = [(q[a], q[(a + 1) % 4]) for a in range(4)] + [(q[4 + a], q[4 + (a + 1) % 4]) for a in range(4)] + [(q[a], q[4 + a]) for a in range(4)]
+        top = np.array([row[0], row[1], row[2] + row[5] / 2])
+        pairs.append((top, (q[4] + q[7]) / 2))
+        if moving[f] and float(arrow_s) > 0:
+            d = np.array([row[7], row[8], 0.0]) * float(arrow_s)
+            n = np.array([-d[1], d[0], 0.0])
+            tip = top + d
+            pairs += [(top, tip), (tip, tip - ARROW_HEAD_BACK * d + ARROW_HEAD_SIDE * n), (tip, tip - ARROW_HEAD_BACK * d - ARROW_HEAD_SIDE * n)]
+        segs += [np.concatenate(p) for p in pairs]
+        owner += [int(f)] * len(pairs)
+    return np.asarray(segs, dtype=np.float64).reshape(-1, 6).astype(np.float32), np.asarray(owner, dtype=np.int64)
+
+
+def _stored(ds, i, keys) -> dict:
+    """the arrays ``keys`` of item ``i`` that exist (and its ``scene_id``), read without the sweep itself where the dataset can"""
+    if hasattr(ds, "index"):
+        from .eval_box import _stored_boxes
+        return {**_stored_boxes(ds, i, keys), "scene_id": ds.index[i][0], "timestamp": ds.index[i][1]}
+    d = ds[i]
+    return {**{k: np.asarray(d[k]) for k in keys if k in d}, "scene_id": d.get("scene_id"), "timestamp": d.get("timestamp")}
+
+
+def trail_segments(dataset, item: int, name: str, trail: int, boxes=None):
+    """The trails of sweep ``item`` (its position in ``dataset``) -> (segments float32 [S][6], box_of_segment int64 [S]).  For every
+    box row f of the sweep whose stored ``tracks_<name>`` row has id >= 0: the polyline through that id's stored ``(x, y)`` in the
+    sweeps ``item - trail .. item`` of the same scene, each earlier point moved into THIS sweep's sensor frame by ``inv(pose0_item) @
+    pose0_j`` (float64; the point's z is taken as 0 in sweep j's frame, and only x and y of the result are used) and placed at the
+    height of the box's top face, ``z + h / 2`` (``boxes``: the sweep's ``boxes_<name>`` rows; read from the dataset when None).  Two
+    consecutive sweeps that both hold the id give one segment, older end first; a sweep without the id leaves a gap; a neighbour of
+    another scene ends the walk.  Reads only ``tracks_<name>`` and ``pose0`` of the neighbour sweeps.  A ``tracks_<name>`` whose row
+    count differs from the boxes' is refused as stale."""
+    from .box_fit import boxes_key
+    from .track import tracks_key
+    bk, tk, trail = boxes_key(name), tracks_key(name), int(trail)
+    if trail < 0:
+        raise ValueError(f"trail={trail}: the number of earlier sweeps, >= 0")
+    wanted = [tk, "pose0"] + ([bk] if boxes is None else [])
+    here = _stored(dataset, item, wanted)
+    for k in wanted:
+        _need(here, k)
+    rows = np.asarray(here[bk] if boxes is None else boxes, dtype=np.float64).reshape(-1, 12)
+    tracks = _check_tracks(np.asarray(here[tk]), rows, tk, bk)
+    inv_here = np.linalg.inv(np.asarray(here["pose0"], dtype=np.float64))
+    history = [(tracks, np.eye(4))]                                # newest first
+    for j in range(item - 1, item - trail - 1, -1):
+        if j < 0:
+            break
+        then = _stored(dataset, j, [tk, "pose0"])
+        if then["scene_id"] != here["scene_id"] or tk not in then or "pose0" not in then:
+            break
+        history.append((np.asarray(then[tk], dtype=np.float64).reshape(-1, 6), inv_here @ np.asarray(then["pose0"], dtype=np.float64)))
+    segs, owner = [], []
+    valid = box_valid(rows)
+    for f in np.flatnonzero(valid & (tracks[:, 0] >= 0)):
+        top = rows[f, 2] + rows[f, 5] / 2
+        points = []
+        for trk, move in reversed(history):                       # oldest first
+            hit = np.flatnonzero(trk[:, 0] == tracks[f, 0])
+            if len(hit) == 0:
+                points.append(None)
+                continue
+            p = move @ np.array([trk[hit[0], 2], trk[hit[0], 3], 0.0, 1.0])
+            points.append(np.array([p[0], p[1], top]))
+        for a, b in zip(points[:-1], points[1:]):
+            if a is not None and b is not None:
+                segs.append(np.concatenate([a, b]))
+                owner.append(int(f))
+    return np.asarray(segs, dtype=np.float64).reshape(-1, 6).astype(np.float32), np.asarray(owner, dtype=np.int64)
+
+
+def _check_tracks(tracks, rows, tk: str, bk: str) -> np.ndarray:
+    tracks = np.asarray(tracks)
+    if tracks.ndim != 2 or tracks.shape[1] != 6:
+        raise ValueError(f"{tk}: holds {tracks.dtype} {tracks.shape}, not [F][6] track rows")
+    if len(tracks) != len(rows):
+        raise ValueError(f"{tk}: holds {len(tracks)} rows for the {len(rows)} boxes of {bk}: stale tracks (run `python -m himo_amd.track "
+                         f"--overwrite` after box_fit)")
+    return tracks.astype(np.float64)
+
+
+def check_line_options(box_color_by: str = "fixed", trail: int = 0, line_px: int = 0, arrow_s: float = 0.5) -> None:
+    if box_color_by not in BOX_COLOR_BY:
+        raise ValueError(f"--box_color_by {box_color_by!r}: one of {', '.join(BOX_COLOR_BY)}")
+    if isinstance(trail, bool) or int(trail) != trail or int(trail) < 0:
+        raise ValueError(f"--trail {trail!r}: the number of earlier sweeps, >= 0")
+    if isinstance(line_px, bool) or int(line_px) != line_px or not 0 <= int(line_px) <= 3:
+        raise ValueError(f"--line_px {line_px!r}: 0..3")
+    if not (np.isfinite(arrow_s) and arrow_s >= 0):
+        raise ValueError(f"--arrow_s {arrow_s!r}: finite and >= 0")
+
+
+def overlay_keys(res_names, boxes: bool = False, boxes_gt=None, box_color_by: str = "fixed", trail: int = 0) -> list:
+    """the frame keys the line overlay of ``render_frame`` reads for these options, beside ``required_keys``"""
+    from .box_fit import boxes_key
+    from .track import tracks_key
+    keys = []
+    if boxes:
+        keys += [boxes_key(n) for n in res_names]
+        if box_color_by == "track" or int(trail) > 0:
+            keys += [tracks_key(n) for n in res_names]
+    if boxes_gt:
+        keys.append(boxes_key(boxes_gt))
+    return list(dict.fromkeys(keys))
+
+
+def _panel_lines(data: dict, names, clouds, gt, box_color_by, trails, sensor_dt, motion_min, arrow_s):
+    """the segments of one panel -> (segments float32 [S][6], colours uint32 [S], boxes drawn).  ``names``: the result names whose
+    boxes the panel draws; ``clouds``: None, or one colour per name (the overlay panel); ``gt``: a name drawn in white, or None."""
+    from .box_fit import boxes_key
+    from .track import tracks_key
+    pal = palette()
+    segs, cols, count = [], [], 0
+    for k, name in enumerate(names):
+        rows = np.asarray(_need(data, boxes_key(name)), dtype=np.float64)
+        if rows.ndim != 2 or rows.shape[1] != 12:
+            raise ValueError(f"{boxes_key(name)}: holds {rows.shape}, not [F][12] box rows")
+        per_box = np.full(len(rows), pal[1], dtype=np.uint32)
+        if clouds is not None:
+            per_box[:] = clouds[k]
+        elif box_color_by == "track":
+            ids = _check_tracks(_need(data, tracks_key(name)), rows, tracks_key(name), boxes_key(name))[:, 0].astype(np.int64)
+            per_box = np.where(ids >= 0, pal[ids % len(pal)], np.uint32(NEUTRAL)).astype(np.uint32)
+        elif box_color_by == "moving":
+            per_box = np.where(box_moving(rows, sensor_dt, motion_min), pal[1], pal[2]).astype(np.uint32)
+        s, owner = box_segments(rows, sensor_dt, motion_min, arrow_s)
+        segs.append(s)
+        cols.append(per_box[owner])
+        count += int(box_valid(rows).sum())
+        if trails is not None and name in trails:
+            s, owner = trails[name]
+            segs.append(np.asarray(s, dtype=np.float32).reshape(-1, 6))
+            cols.append(per_box[np.asarray(owner, dtype=np.int64)])
+    if gt:
+        rows = np.asarray(_need(data, boxes_key(gt)), dtype=np.float64)
+        s, owner = box_segments(rows, sensor_dt, motion_min, arrow_s)
+        segs.append(s)
+        cols.append(np.full(len(owner), WHITE, dtype=np.uint32))
+        count += int(box_valid(rows).sum())
+    if not segs:
+        return np.zeros((0, 6), np.float32), np.zeros(0, np.uint32), 0
+    return np.concatenate(segs).astype(np.float32), np.concatenate(cols).astype(np.uint32), count
+
+
 def render_frame(data: dict, res_names, color_by: str = "lidar", camera: Camera | None = None, renderer: Renderer | None = None,
                  point_px: int = 1, edl: float = 0.0, keep_ground: bool = False, instances=None, sensor_dt: float = 0.1,
-                 value_range=None, background: int = BACKGROUND, return_buffers: bool = False):
+                 value_range=None, background: int = BACKGROUND, return_buffers: bool = False, *, boxes: bool = False, boxes_gt=None,
+                 box_color_by: str = "fixed", trails=None, arrow_s: float = 0.5, line_px: int = 0, box_depth: bool = False,
+                 motion_min: float = 0.05):
     """One panel per result name of ``res_names``, joined left to right with a ``SEPARATOR_PX`` separator: ``raw`` draws ``pc0`` as it
     stands, any other name ``pc0 + comp_dis`` (``compdis.comp_dis_frame(data, name)``; the offset goes to the splat, it is not added
     on the host).  ``color_by``: see the module docstring of the program below; ``overlay`` draws ONE panel.  ``point_px`` is the
     disc radius of rule E.  Returns (image: (H, W_total, 3) uint8 device tensor, info: {"panels", "points", "pixels"}); with
-    ``return_buffers`` also the list of the panels' visibility buffers (clones)."""
+    ``return_buffers`` also the list of the panels' visibility buffers (clones).
+
+    The line overlay ("line overlay, v1"), all off by default: ``boxes`` draws on each panel ``boxes_<its own name>`` (``raw``:
+    ``boxes_raw``; the ``overlay`` panel draws every name's boxes in that name's cloud colour, whatever ``box_color_by`` says);
+    ``boxes_gt`` a name whose boxes are drawn in white on every panel; ``box_color_by``: ``fixed`` one palette colour, ``track``
+    ``palette[id % 6]`` of ``tracks_<name>`` (neutral for id -1; a row count that differs from the boxes' is refused as stale),
+    ``moving`` one colour for MOVING boxes and another for the rest; ``trails``: {name: ``trail_segments(...)``} drawn in their boxes'
+    colours; ``arrow_s`` the seconds of travel a velocity arrow shows; ``line_px`` the ``half_px`` of rule E; ``box_depth`` tests the
+    lines against the points (default: lines on top).  With any of them ``info`` gains "boxes", "segments" and "line_pixels" per panel
+    and ``return_buffers`` a second list, the panels' lines buffers."""
     import torch
     from . import compdis, utils
     res_names = list(res_names)
@@ -401,7 +714,12 @@ def render_frame(data: dict, res_names, color_by: str = "lidar", camera: Camera 
         raise ValueError("render_frame: no result names")
     kind, key = parse_color_by(color_by)
     keep_ground = keep_ground or kind == "ground"
-    for k in required_keys(res_names, color_by, instances):
+    with_lines = bool(boxes or boxes_gt)
+    if trails and not boxes:
+        raise ValueError("render_frame: trails belong to the boxes of boxes=True")
+    if with_lines:
+        check_line_options(box_color_by, 0, line_px, arrow_s)
+    for k in required_keys(res_names, color_by, instances) + (overlay_keys(res_names, boxes, boxes_gt, box_color_by) if with_lines else []):
         _need(data, k)
     if camera is None:
         camera = auto_camera(data, 1024, 1024, keep_ground, instances)
@@ -412,8 +730,20 @@ def render_frame(data: dict, res_names, color_by: str = "lidar", camera: Camera 
     drawn = n - int(skip.sum().item())
     offsets = {name: torch.from_numpy(compdis.comp_dis_frame(data, name, sensor_dt=sensor_dt)).to(dev) for name in res_names if name != "raw"}
     panels, images, points, pixels, buffers = [], [], [], [], []
+    line_info, line_buffers = {"boxes": [], "segments": [], "line_pixels": []}, []
 
-    def finish(name, image, count):
+    def finish(name, image, count, drawn_names=None, clouds=None):
+        if with_lines:                                            # rule F, over the image just resolved
+            segs, cols, n_boxes = _panel_lines(data, drawn_names if boxes else [], clouds, boxes_gt, box_color_by, trails if boxes else None,
+                                               sensor_dt, motion_min, arrow_s)
+            r.clear_lines()
+            r.lines(segs, line_px, 0, camera)
+            image = r.composite(cols, depth_test=box_depth)
+            line_info["boxes"].append(n_boxes)
+            line_info["segments"].append(int(len(segs)))
+            line_info["line_pixels"].append(int((r.line_buffer() != EMPTY).sum().item()))
+            if return_buffers:
+                line_buffers.append(r.line_buffer().clone())
         panels.append(name)
         images.append(image.clone())
         points.append(count)
@@ -423,12 +753,14 @@ def render_frame(data: dict, res_names, color_by: str = "lidar", camera: Camera 
 
     if kind == "overlay":
         r.clear()
-        pal, colors, results = palette(), [], 0
+        pal, colors, results, clouds = palette(), [], 0, []
         for k, name in enumerate(res_names):
             r.splat(pc0, offsets.get(name), skip, point_px, k * n, camera)
-            colors.append(np.full(n, WHITE if name == "raw" else pal[results % len(pal)], dtype=np.uint32))
+            clouds.append(WHITE if name == "raw" else pal[results % len(pal)])
+            colors.append(np.full(n, clouds[-1], dtype=np.uint32))
             results += name != "raw"
-        finish("+".join(res_names), r.resolve(colors=np.concatenate(colors), edl=edl, background=background), drawn * len(res_names))
+        finish("+".join(res_names), r.resolve(colors=np.concatenate(colors), edl=edl, background=background), drawn * len(res_names),
+               res_names, clouds)
     else:
         shared = None
         if kind == "lidar":
@@ -447,16 +779,18 @@ def render_frame(data: dict, res_names, color_by: str = "lidar", camera: Camera 
             if kind == "speed":
                 lo, hi = value_range if value_range is not None else DEFAULT_RANGE["speed"]
                 how = dict(scalar=(_speed(data, name, sensor_dt), lo, hi))
-            finish(name, r.resolve(edl=edl, background=background, **how), drawn)
+            finish(name, r.resolve(edl=edl, background=background, **how), drawn, [name])
     sep = torch.tensor([SEPARATOR & 0xFF, (SEPARATOR >> 8) & 0xFF, (SEPARATOR >> 16) & 0xFF], dtype=torch.uint8, device=dev)
     parts = []
     for k, image in enumerate(images):
         if k:
             parts.append(sep.expand(image.shape[0], SEPARATOR_PX, 3))
         parts.append(image)
-    info = {"panels": panels, "points": points, "pixels": pixels}
+    info = {"panels": panels, "points": points, "pixels": pixels, **(line_info if with_lines else {})}
     out = (torch.cat(parts, dim=1).contiguous(), info)
-    return out + (buffers,) if return_buffers else out
+    if return_buffers:
+        out += (buffers, line_buffers) if with_lines else (buffers,)
+    return out
 
 
 # --------------------------------------------------------------------------------------------------------------------------
@@ -525,11 +859,17 @@ def parse_indices(index, indices) -> list:
 
 def main(data_dir: str, out_dir: str, res_names="raw,seflowpp_best", index=None, indices=None, scene: str | None = None,
          color_by: str = "lidar", camera: str = "bev", sample_step: int = 10, size: str = "1024x768", point_px: int = 1, edl: float = 0.0,
-         keep_ground: bool = False, instance=None, dataset=None) -> list:
+         keep_ground: bool = False, instance=None, dataset=None, *, boxes: bool = False, boxes_gt: str | None = None,
+         box_color_by: str = "fixed", trail: int = 0, arrow_s: float = 0.5, line_px: int = 0, box_depth: bool = False) -> list:
     """The program: the sweeps ``index`` / ``indices`` of the dataset's index (of ``scene``'s sweeps with ``scene``) as
     ``<out_dir>/<scene>_<timestamp>.png``, from a fixed camera; or, with a camera file of several keyframes, ONE sweep as the numbered
     frames ``00000.png ...`` along ``spline_path(keyframes, sample_step)``.  ``<out_dir>/view.json`` lists every image with its panel
-    names, its camera and, per panel, the points drawn and the non-empty pixels.  Returns that list."""
+    names, its camera and, per panel, the points drawn and the non-empty pixels.  Returns that list.
+
+    ``boxes`` / ``boxes_gt`` / ``box_color_by`` / ``arrow_s`` / ``line_px`` / ``box_depth``: the line overlay of ``render_frame``;
+    ``trail`` K > 0 adds to every tracked box the trail of its id over the K sweeps before it (``trail_segments``; needs ``boxes`` and
+    the stored ``tracks_<name>``).  With ``boxes`` or ``boxes_gt`` every entry of ``view.json`` gains "boxes", "segments" and
+    "line_pixels" per panel; without them it gains nothing."""
     from . import _lib
     from .dataset import open_dataset
     from .eval_seg import parse_res_names
@@ -539,7 +879,10 @@ def main(data_dir: str, out_dir: str, res_names="raw,seflowpp_best", index=None,
     todo = parse_indices(index, indices)
     instances = [int(v) for v in str(instance).split(",")] if instance not in (None, "") else None
     keep_ground = keep_ground or kind == "ground"
-    keys = required_keys(names, color_by, instances)
+    check_line_options(box_color_by, trail, line_px, arrow_s)
+    if int(trail) > 0 and not boxes:
+        raise ValueError("--trail draws the trails of the boxes of --boxes: give --boxes")
+    keys = required_keys(names, color_by, instances) + overlay_keys(names, boxes, boxes_gt, box_color_by, trail)
     keyframes = None if camera in ("bev", "auto") else load_keyframes(camera)
     if keyframes is not None and len(keyframes) > 1 and len(todo) != 1:
         raise ValueError("a camera path of several keyframes renders one sweep: give --index")
@@ -555,8 +898,10 @@ def main(data_dir: str, out_dir: str, res_names="raw,seflowpp_best", index=None,
     renderer = Renderer(width, height, _lib.require_gpu())
     listing = []
 
-    def one(data, cam, file_name):
-        image, info = render_frame(data, names, color_by, cam, renderer, point_px=point_px, edl=edl, keep_ground=keep_ground, instances=instances)
+    def one(data, cam, file_name, trails=None):
+        image, info = render_frame(data, names, color_by, cam, renderer, point_px=point_px, edl=edl, keep_ground=keep_ground, instances=instances,
+                                   boxes=boxes, boxes_gt=boxes_gt, box_color_by=box_color_by, trails=trails, arrow_s=arrow_s, line_px=line_px,
+                                   box_depth=box_depth)
         write_png(out_dir / file_name, image)
         listing.append({"file": file_name, "scene_id": str(data.get("scene_id")), "timestamp": int(data.get("timestamp", 0)),
                         "color_by": color_by, "camera": cam.as_dict(), **info})
@@ -568,15 +913,19 @@ def main(data_dir: str, out_dir: str, res_names="raw,seflowpp_best", index=None,
             data = dataset[where[i]]
             for k in keys:
                 _need(data, k)
+            trails = None
+            if int(trail) > 0:
+                from .box_fit import boxes_key
+                trails = {n: trail_segments(dataset, where[i], n, int(trail), boxes=data[boxes_key(n)]) for n in names}
             if keyframes is None:
                 cam = Camera.bev(width=width, height=height) if camera == "bev" else auto_camera(data, width, height, keep_ground, instances)
-                one(data, cam, f"{data['scene_id']}_{data['timestamp']}.png")
+                one(data, cam, f"{data['scene_id']}_{data['timestamp']}.png", trails)
                 continue
             radius = scene_radius(data, keep_ground, instances)
             path = spline_path(keyframes, sample_step) if len(keyframes) > 1 else keyframes
             for k, kf in enumerate(path):
                 cam = Camera.from_view(kf["front"], kf["lookat"], kf["up"], kf["zoom"], radius, width=width, height=height)
-                one(data, cam, f"{k:05d}.png" if len(keyframes) > 1 else f"{data['scene_id']}_{data['timestamp']}.png")
+                one(data, cam, f"{k:05d}.png" if len(keyframes) > 1 else f"{data['scene_id']}_{data['timestamp']}.png", trails)
     finally:
         close = getattr(dataset, "close", None)
         if close is not None:
@@ -605,13 +954,22 @@ def _parser():
     ap.add_argument("--keep_ground", action="store_true", help="draw the ground points too")
     ap.add_argument("--instance", default=None, help="8,9 -- draw only these flow_instance_ids (--camera auto fits them)")
     ap.add_argument("--out_dir", required=True)
+    # the line overlay ("line overlay, v1": this build's own rule; parity unpinned, the reference has no such stage; timing: profiles/view_boxes.txt)
+    ap.add_argument("--boxes", action="store_true", help="draw boxes_<name> on the panel of <name> (raw: boxes_raw; --color_by overlay: every name's, in its cloud colour)")
+    ap.add_argument("--boxes_gt", default=None, help="NAME -- also draw boxes_<NAME> in white on every panel")
+    ap.add_argument("--box_color_by", default="fixed", help=f"{' | '.join(BOX_COLOR_BY)} (track: by tracks_<name> id; moving: MOVING boxes apart from the rest)")
+    ap.add_argument("--trail", type=int, default=0, help="K -- the trail of every tracked box over the K sweeps before it (needs --boxes and tracks_<name>)")
+    ap.add_argument("--arrow_s", type=float, default=0.5, help="a velocity arrow shows this many seconds of travel (0 = none)")
+    ap.add_argument("--line_px", type=int, default=0, help="half-width of a line in pixels (0..3)")
+    ap.add_argument("--box_depth", action="store_true", help="nearer points hide lines (default: lines on top)")
     return ap
 
 
 def _cli(argv=None):
     a = _parser().parse_args(argv)
     return main(a.data_dir, a.out_dir, a.res_names, a.index, a.indices, a.scene, a.color_by, a.camera, a.sample_step, a.size, a.point_px,
-                a.edl, a.keep_ground, a.instance)
+                a.edl, a.keep_ground, a.instance, boxes=a.boxes, boxes_gt=a.boxes_gt, box_color_by=a.box_color_by, trail=a.trail,
+                arrow_s=a.arrow_s, line_px=a.line_px, box_depth=a.box_depth)
 
 
 if __name__ == "__main__":

@@ -536,6 +536,33 @@ int himo_render_splat(int64_t n, const float* d_pts, int pitch, const float* d_o
 int himo_render_resolve(const uint64_t* d_vis, int width, int height, const himo_shade* shade, unsigned char* d_rgb, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The viewer's line overlay ("line overlay, v1"; csrc/renderlines.hip; the rule is the module docstring of himo_amd/view.py, this
+ * build's own: PARITY UNPINNED, the reference has no such stage).
+ *
+ * The overlay has its own buffer, d_lines, one uint64 per pixel [height][width]: ~0 = empty, else (zq << 32) | segment index;
+ * himo_render_clear clears it.  himo_render_lines adds n segments (float32 [n][6] = x0, y0, z0, x1, y1, z1): both ends to camera
+ * coordinates as himo_render_splat does (dropped when one of the six is not finite); dropped when both zc < znear or both
+ * zc > zfar, else an end outside [znear, zfar] moves along the ORIGINAL segment onto the plane it passed
+ * (t = (plane - z) / (z_other - z), x' = x + t * (x_other - x), y' likewise, z' = plane); both ends projected as a point is,
+ * dropped when a screen coordinate is not finite or |.| >= 2^20; end pixels (floor u, floor v), end depths zq as for a point.  Then
+ * integers: dx = X1 - X0, dy = Y1 - Y0, steps = max(|dx|, |dy|); for k = 0..steps (floor division)
+ * x_k = X0 + (2 k dx + steps) / (2 steps), y_k likewise, zq_k = zq0 + k (zq1 - zq0) / steps (steps = 0: the one pixel); the 64-bit
+ * minimum of (zq_k << 32) | (index_base + i) into every pixel (x_k + ddx, y_k + ddy), ddx^2 + ddy^2 <= half_px^2, inside the image.
+ * Depth is linear along the SCREEN segment: no perspective-correct depth is claimed.  Calls accumulate, in any order and split, to
+ * the same bits.  himo_render_composite, per pixel of an RGB image himo_render_resolve has written: an empty d_lines word leaves the
+ * pixel alone; with d_vis (nullable: no depth test) a non-empty point word of SMALLER zq leaves it alone too (a tie shows the line);
+ * otherwise the pixel takes d_colors[idx] (r | g << 8 | b << 16), `neutral` when idx >= n_colors.
+ *
+ * Both are asynchronous on `stream`.  Refused with HIMO_ERR_INVALID_ARGUMENT, nothing launched and nothing written: n < 0, half_px
+ * outside 0..3, a non-positive width or height, a NULL camera, a NULL or misaligned d_lines, NULL segments with n > 0, misaligned
+ * segments, d_vis or d_colors, a NULL d_rgb, znear / zfar / inv_range as for himo_render_splat, n_colors < 0, NULL d_colors with
+ * n_colors > 0.  HIMO_ERR_UNSUPPORTED: a side above 16384, n > 2^31 - 1, index_base + n > 2^32.  n == 0: HIMO_OK without a launch. */
+int himo_render_lines(int64_t n, const float* d_seg, const himo_camera* cam, int half_px, uint32_t index_base, uint64_t* d_lines,
+                      void* stream);
+int himo_render_composite(const uint64_t* d_lines, const uint64_t* d_vis /* NULL = no depth test */, int width, int height,
+                          const uint32_t* d_colors, int64_t n_colors, uint32_t neutral, unsigned char* d_rgb, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * ICP-Flow baseline (`save --model icpflow`, result key `icpflow`): clusters of the non-ground points of pc0, one rigid fit
  * (yaw + 3-D translation) per cluster against pc1, flow = fitted motion.  The reference's ICP-Flow code is in its absent
  * submodule (only the key name is in its tree, tools/view_instance.py:155-156), so this stage follows the build's own written
