@@ -98,6 +98,22 @@ __device__ inline float tanh_f(float v) {
     const float t = (1.0f - e) * __builtin_amdgcn_rcpf(1.0f + e);
     return copysignf(t, v);
 }
+// The same gates with the exponential's ARGUMENT formed by the caller in one fused multiply-add on the accumulator, x = fma(acc, A, B)
+// (fused head, gruhead.hip): for v = k acc + bias,  sigmoid_from_arg takes x = -log2(e) v  (A = -log2(e) k, B = -log2(e) bias) and the
+// tanh forms take y = 2 log2(e) v (A = 2 log2(e) k, B = 2 log2(e) bias).
+// Saturation: x -> +inf gives rcp(inf) = 0, x -> -inf gives rcp(1) = 1; e = exp2(-|y|) is in [0, 1] for every y.  No NaN from finite inputs.
+constexpr float kLog2e = 1.44269504088896340736f;
+__device__ inline float sigmoid_from_arg(float x) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x)); }
+__device__ inline float tanh_from_arg(float y) {            // tanh_f's arrangement: -|y| rides on v_exp's source modifiers, y carries v's sign
+    const float e = __builtin_amdgcn_exp2f(-fabsf(y));
+    const float t = (1.0f - e) * __builtin_amdgcn_rcpf(1.0f + e);
+    return copysignf(t, y);
+}
+// tanh(v) = 1 - 2 / (1 + exp(2 v)) from the same y: no |y|, no sign transfer, no 1 - e.  y -> +inf: rcp(inf) = 0, q = 1; y -> -inf:
+// rcp(1) = 1, q = -1.  Near 0 the difference 1 - 2 r cancels: the ABSOLUTE error is that of 2 r ~ 1, about 4 units of 2^-24 (one ulp of
+// the exponential, the sum's rounding, one ulp of the reciprocal), where tanh_from_arg's is relative -- inside the 8 u the head's error
+// model (oracle/head_oracle.py _tanh_b) allows the gate at v = 0, and 1e-2 of the head's float32 margin.
+__device__ inline float tanh_direct_from_arg(float y) { return fmaf(__builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(y)), -2.0f, 1.0f); }
 
 
 // ---- the two epilogues of the backbone (bias; bias + BatchNorm + GELU) with the fewest vector instructions ------------------------

@@ -75,6 +75,31 @@ struct GruHeadBatch {
 constexpr int kGhRows = 64;
 constexpr bool kGhLaunder = false;
 
+// The instruction diet of the fp16 folded inference kernel (gru_head_kernel<2, 9, false> only; table and timings in
+// profiles/head_instruction_diet.txt).  Each item is a compile-time switch so that it can be measured alone:
+//   HIMO_HEAD_PACKED_SLAB  the ninth slab's K = 4 product [o, 1] F as ONE matrix instruction.  The three kept terms of the fp16 split,
+//                          hi hi + lo hi + hi lo, are three K = 4 products; a slab has K = 16, so they sit side by side in one fragment:
+//                            A columns  0-3 hi(o, 1) | 4-7 lo(o, 1) | 8-11 hi(o, 1) | 12-15 zero   (the kernel writes them, plane 0)
+//                            B rows     0-3 hi(F)    | 4-7 hi(F)    | 8-11 lo(F)    | 12-15 zero
+//                          The B fragment is put together in registers from the packer's ordinary [slab][term][cout][16] layout: the
+//                          lanes of k 0-7 load hi(F) rows 0-3 (plane 0) and repeat them, the lanes of k 8-15 load lo(F) rows 0-3
+//                          (plane 1) -- 8 bytes a lane instead of 32, and the packed weights are what they were.  Same products,
+//                          another order inside the accumulation.
+//   HIMO_HEAD_GATE_FMA     packing scale, bias and the exponential's constant in one fused multiply-add per accumulator element
+//                          (conv_common.h sigmoid_from_arg / tanh_from_arg); gemm192 leaves the accumulator unscaled, and the gates'
+//                          operand stores take the two-instruction split (a_store_f16).
+//   HIMO_HEAD_TANH_DIRECT  q = 1 - 2 / (1 + exp2(y)) (conv_common.h tanh_direct_from_arg) in place of the |y| / copysign form: three plain
+//                          instructions fewer per element.  Needs HIMO_HEAD_GATE_FMA.
+#ifndef HIMO_HEAD_PACKED_SLAB
+#define HIMO_HEAD_PACKED_SLAB 1
+#endif
+#ifndef HIMO_HEAD_GATE_FMA
+#define HIMO_HEAD_GATE_FMA 1
+#endif
+#ifndef HIMO_HEAD_TANH_DIRECT
+#define HIMO_HEAD_TANH_DIRECT 1
+#endif
+
 template <int SLABS>
 __device__ inline int a_slot(int s, int slab, int row, int half) {
     return ((s * SLABS + slab) * kGhRows + row) * 32 + ((half ^ ((row >> 4) & 1)) << 4);
@@ -93,9 +118,25 @@ __device__ inline void a_store(unsigned char* A, int row, int k, float v) {
     *reinterpret_cast<unsigned short*>(A + off + (FMT - 1) * kGhPlane) = (unsigned short)l;
 }
 
+// a_store of the fp16 planes in two instructions: h = v_cvt_f16_f32(v), l = fp16(v - h) as ONE mixed-precision fused multiply-add
+// (v * 1 - h is exact in float32, so this is split2's single rounding).  Left to itself the compiler finds that form only where it can
+// fuse v's own last operation in, and otherwise emits convert, convert back, subtract, convert (32 instructions more per iteration)
+template <int SLABS>
+__device__ inline void a_store_f16(unsigned char* A, int row, int k, float v) {
+    constexpr int kGhPlane = SLABS * kGhRows * 32;
+    const _Float16 hh = (_Float16)v;
+    _Float16 ll;
+    asm("v_fma_mixlo_f16 %0, %1, 1.0, -%2 op_sel_hi:[0,0,1]" : "=v"(ll) : "v"(v), "v"(hh));
+    const int slab = k >> 4, kk = k & 15;
+    const int off = a_slot<SLABS>(0, slab, row, kk >> 3) + (kk & 7) * 2;
+    *reinterpret_cast<_Float16*>(A + off) = hh;
+    *reinterpret_cast<_Float16*>(A + off + kGhPlane) = ll;
+}
+
 // acc[rt][t] += A[rows of tile rt][0..192) * W[:, col[t] + li] for the wave's NT column tiles; RT row tiles starting at rt0
 // FMT = 2: one accumulator for the three terms of the fp16 split (bf16x3.h)
-template <int RT, int NT, int FMT, int SLABS>
+// PK: the last slab is the packed offset slab (HIMO_HEAD_PACKED_SLAB above), multiplied first.  SCALE = false leaves the fp16 packing scale to the caller
+template <int RT, int NT, int FMT, int SLABS, bool PK = false, bool SCALE = true>
 __device__ inline void gemm192(const unsigned char* A, const unsigned short* __restrict__ wpk, int cout, const int (&col)[NT],
                                floatx16 (&acc)[RT][NT], int rt0, int li, int lh) {
     uint4 bcur[NT][FMT], bnxt[NT][FMT];
@@ -106,11 +147,73 @@ __device__ inline void gemm192(const unsigned char* A, const unsigned short* __r
             for (int s = 0; s < FMT; ++s)
                 b[t][s] = *reinterpret_cast<const uint4*>(wpk + (((int64_t)slab * FMT + s) * cout + col[t] + li) * 16 + lh * 8);
     };
+    static_assert(!PK || FMT == 2, "the packed offset slab is the fp16 split's");
+    constexpr int NFULL = PK ? SLABS - 1 : SLABS;        // slabs that take all their terms
+    if constexpr (PK) {
+        // fragment addresses as a uniform base (the slab, the plane and the wave's column tile: scalar registers) plus ONE 32-bit lane
+        // offset; as 64-bit pointers per fragment the compiler keeps a register pair per (tile, plane) live across the loop and spills
+        const unsigned lane_b = (unsigned)(li * 16 + lh * 8) * 2u, lane_p = (unsigned)li * 32u;
+        auto load_bu = [&](int slab, uint4 (&b)[NT][FMT]) {
+            unsigned lane_o = lane_b;
+            asm volatile("" : "+v"(lane_o));                        // (the zero extension stays beside the loads: scalar base + 32-bit offset form)
+#pragma unroll
+            for (int t = 0; t < NT; ++t)
+#pragma unroll
+                for (int s = 0; s < FMT; ++s)
+                {
+                    typedef const __attribute__((address_space(1))) char* gptr;       // global: the empty asm hides where the pointer came from
+                    gptr base = (gptr)(reinterpret_cast<const char*>(wpk) + (((int64_t)slab * FMT + s) * cout + col[t]) * 32);
+                    asm volatile("" : "+s"(base));                  // a scalar register pair of its own: plane strides exceed the 13-bit immediate
+                    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+                    b[t][s] = __builtin_bit_cast(uint4, *(const __attribute__((address_space(1))) u32x4*)(base + lane_o));
+                }
+        };
+        load_bu(0, bcur);
+        // the packed slab goes FIRST: its fragment load shares the wait of slab 0's, and on the callers' zero accumulators the compiler
+        // gives the matrix instruction a constant-zero addend instead of clearing 16 registers per tile beforehand
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {                           // rows 0-3 of plane lh of the last slab, twice: hi(F) for k 0-7, lo(F) for k 8-15
+            const char* base = reinterpret_cast<const char*>(wpk) + ((int64_t)NFULL * FMT * cout + col[t]) * 32;
+            const uint2 v = *reinterpret_cast<const uint2*>(base + (lh ? (unsigned)cout * 32u + lane_p : lane_p));
+            bnxt[t][0] = uint4{v.x, v.y, v.x, v.y};              // (k 12-15 meet the operand's zero columns)
+        }
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt) {
+            const f16x8 af = *reinterpret_cast<const f16x8*>(A + a_slot<SLABS>(0, NFULL, (rt0 + rt) * 32 + li, lh));
+#pragma unroll
+            for (int t = 0; t < NT; ++t)
+                acc[rt][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, __builtin_bit_cast(f16x8, bnxt[t][0]), acc[rt][t], 0, 0, 0);
+        }
+        // the full slabs two at a time, the two fragment sets changing roles: no register copies between slabs
+        static_assert(NFULL % 2 == 0, "slab pairs");
+        auto terms = [&](int slab, const uint4 (&b)[NT][FMT]) {
+            f16x8 af[RT][FMT];
+#pragma unroll
+            for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+                for (int s = 0; s < FMT; ++s)
+                    af[rt][s] = *reinterpret_cast<const f16x8*>(A + a_slot<SLABS>(s, slab, (rt0 + rt) * 32 + li, lh));
+#pragma unroll
+            for (int term = 0; term < 3; ++term)                 // (1, 0) (0, 1) (0, 0): the order of the loop below
+#pragma unroll
+                for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+                    for (int t = 0; t < NT; ++t)
+                        acc[rt][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[rt][term == 0], __builtin_bit_cast(f16x8, b[t][term == 1]), acc[rt][t], 0, 0, 0);
+        };
+#pragma unroll 1
+        for (int slab = 0; slab < NFULL; slab += 2) {
+            load_bu(slab + 1, bnxt);
+            terms(slab, bcur);
+            if (slab + 2 < NFULL) load_bu(slab + 2, bcur);
+            terms(slab + 1, bnxt);
+        }
+    } else {
     load_b(0, bcur);
-    constexpr int kUnroll = SLABS % 2 == 0 ? 2 : 3;      // a divisor of the trip count: no remainder loop, no full unroll
+    constexpr int kUnroll = NFULL % 2 == 0 ? 2 : 3;      // a divisor of the trip count: no remainder loop, no full unroll
 #pragma unroll kUnroll
-    for (int slab = 0; slab < SLABS; ++slab) {
-        if (slab + 1 < SLABS) load_b(slab + 1, bnxt);
+    for (int slab = 0; slab < NFULL; ++slab) {
+        if (slab + 1 < NFULL) load_b(slab + 1, bnxt);
         bf16x8 af[RT][FMT];
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt)
@@ -136,7 +239,8 @@ __device__ inline void gemm192(const unsigned char* A, const unsigned short* __r
 #pragma unroll
             for (int s = 0; s < FMT; ++s) bcur[t][s] = bnxt[t][s];
     }
-    if (FMT == 2) {                                     // fold the cross terms in and undo the weights' packing scale
+    }
+    if (FMT == 2 && SCALE) {                                     // fold the cross terms in and undo the weights' packing scale
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
@@ -162,6 +266,8 @@ template <int FMT, int SLABS, bool SAVE = false>
 __global__ __launch_bounds__(256, (FMT == 2 && !SAVE) ? 3 : 2) void gru_head_kernel(GruHeadArgs a, GruHeadBatch batch, GruHeadSave sv) {
     constexpr bool FOLD = SLABS == 9;
     static_assert(!(SAVE && FOLD), "the training forward keeps x explicit");
+    constexpr bool DIET = FMT == 2 && FOLD && !SAVE;                  // the instantiation the switches above apply to
+    constexpr bool PKSLAB = DIET && HIMO_HEAD_PACKED_SLAB, GFMA = DIET && HIMO_HEAD_GATE_FMA;
     constexpr int kGhPlane = SLABS * kGhRows * 32;
     __shared__ __attribute__((aligned(16))) unsigned char A[FMT * kGhPlane];
     __shared__ int s_pid[kGhRows];
@@ -182,7 +288,21 @@ __global__ __launch_bounds__(256, (FMT == 2 && !SAVE) ? 3 : 2) void gru_head_ker
         const int64_t i = r0 + threadIdx.x;
         s_pid[threadIdx.x] = i < a.n ? a.pid[i] : -1;
     }
-    if constexpr (FOLD) {
+    if constexpr (PKSLAB) {
+        // ninth slab, packed: thread -> (row, 4 columns): hi(o0, o1, o2, 1) | lo(o0, o1, o2, 1) | hi again | zeros, plane 0 only
+        const int row = threadIdx.x >> 2, q = threadIdx.x & 3;
+        const int64_t i = r0 + row;
+        float v[4] = {0.f, 0.f, 0.f, 1.f};
+        if (i < a.n) { v[0] = a.offsets[i * 3]; v[1] = a.offsets[i * 3 + 1]; v[2] = a.offsets[i * 3 + 2]; }
+        unsigned w[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            unsigned hh, ll;
+            split2(v[k], hh, ll);
+            w[k] = q == 3 ? 0u : q == 1 ? ll : hh;
+        }
+        *reinterpret_cast<uint2*>(A + a_slot<SLABS>(0, 8, row, q >> 1) + (q & 1) * 8) = uint2{w[0] | (w[1] << 16), w[2] | (w[3] << 16)};
+    } else if constexpr (FOLD) {
         // ninth slab of the A operand, columns 128 .. 143 of every row: (o0, o1, o2, 1, 0, ..., 0); thread -> (row, 4 columns)
         const int row = threadIdx.x >> 2, q = threadIdx.x & 3;
         const int64_t i = r0 + row;
@@ -307,16 +427,25 @@ __global__ __launch_bounds__(256, (FMT == 2 && !SAVE) ? 3 : 2) void gru_head_ker
             for (int t = 0; t < 2; ++t)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[rt][t][r] = 0.f;
-        gemm192<2, 2, FMT, SLABS>(A, a.wzr, 256, col_zr, acc, 0, li, lh);
+        gemm192<2, 2, FMT, SLABS, PKSLAB, !GFMA>(A, a.wzr, 256, col_zr, acc, 0, li, lh);
         __syncthreads();                                        // every wave has read [h | x]      the bound on what a second operand buffer could buy
+        // GFMA: exponent argument = fma(acc, -log2(e) / 64, -log2(e) bias) -- packing scale, bias and exp's constant in one instruction
+        const float kAs = -kLog2e * kF16AccScale, kBz = -kLog2e * bz, kBr = -kLog2e * br;
 #pragma unroll
         for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                acc[rt][0][r] = sigmoid_f(acc[rt][0][r] + bz);                      // z replaces its accumulator element
-                const float rr = sigmoid_f(acc[rt][1][r] + br);
+                float rr;
+                if constexpr (GFMA) {
+                    acc[rt][0][r] = sigmoid_from_arg(fmaf(acc[rt][0][r], kAs, kBz));
+                    rr = sigmoid_from_arg(fmaf(acc[rt][1][r], kAs, kBr));
+                } else {
+                    acc[rt][0][r] = sigmoid_f(acc[rt][0][r] + bz);                  // z replaces its accumulator element
+                    rr = sigmoid_f(acc[rt][1][r] + br);
+                }
                 const int row = rt * 32 + (r & 3) + 8 * (r >> 2) + 4 * slh;
-                a_store<FMT, SLABS>(A, row, wave * 32 + sli, rr * h[rt][r]);
+                if constexpr (GFMA) a_store_f16<SLABS>(A, row, wave * 32 + sli, rr * h[rt][r]);
+                else a_store<FMT, SLABS>(A, row, wave * 32 + sli, rr * h[rt][r]);
                 if constexpr (SAVE) {
                     const unsigned dr = rt * 32 + (r & 3) + 8 * (r >> 2);
                     sv_store<2>(sz, o128 + dr * 512u, acc[rt][0][r]); sv_store<2>(sr, o128 + dr * 512u, rr);
@@ -331,18 +460,26 @@ __global__ __launch_bounds__(256, (FMT == 2 && !SAVE) ? 3 : 2) void gru_head_ker
         for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acq[rt][0][r] = 0.f;
-        gemm192<2, 1, FMT, SLABS>(A, a.wq, 128, col_q, acq, 0, li, lh);
+        gemm192<2, 1, FMT, SLABS, PKSLAB, !GFMA>(A, a.wq, 128, col_q, acq, 0, li, lh);
         __syncthreads();
+        const float kAt = 2.0f * kLog2e * kF16AccScale, kBq = 2.0f * kLog2e * bq;    // GFMA: y = 2 log2(e) (acc / 64 + bias) in one instruction
 #pragma unroll
         for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const float q = tanh_f(acq[rt][0][r] + bq);
+                float q;
+                if constexpr (GFMA) {
+                    const float y = fmaf(acq[rt][0][r], kAt, kBq);
+                    if constexpr (HIMO_HEAD_TANH_DIRECT) q = tanh_direct_from_arg(y); else q = tanh_from_arg(y);
+                } else {
+                    q = tanh_f(acq[rt][0][r] + bq);
+                }
                 const float zz = acc[rt][0][r];
                 const float hn = (1.0f - zz) * h[rt][r] + zz * q;
                 h[rt][r] = hn;
                 const int row = rt * 32 + (r & 3) + 8 * (r >> 2) + 4 * slh;
-                a_store<FMT, SLABS>(A, row, wave * 32 + sli, hn);
+                if constexpr (GFMA) a_store_f16<SLABS>(A, row, wave * 32 + sli, hn);
+                else a_store<FMT, SLABS>(A, row, wave * 32 + sli, hn);
                 if constexpr (SAVE) {
                     const unsigned dr = rt * 32 + (r & 3) + 8 * (r >> 2);
                     sv_store<4>(sq, o128 + dr * 512u, q);
@@ -357,7 +494,7 @@ __global__ __launch_bounds__(256, (FMT == 2 && !SAVE) ? 3 : 2) void gru_head_ker
 #pragma unroll
     for (int r = 0; r < 16; ++r) ac1[0][0][r] = 0.f;
     const int col_1[1] = {0};
-    if (wave < 2) gemm192<1, 1, FMT, SLABS>(A, a.w1, 32, col_1, ac1, wave, li, lh);
+    if (wave < 2) gemm192<1, 1, FMT, SLABS, PKSLAB>(A, a.w1, 32, col_1, ac1, wave, li, lh);
     __syncthreads();                                            // A is dead from here: reuse it for y1 [64][32] float32
     float* Y = reinterpret_cast<float*>(A);
     if (wave < 2) {
