@@ -77,6 +77,9 @@ SIGNATURES = {
     "himo_boxfit_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
     "himo_boxfit": (c_int, [c_int64, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                             c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "himo_xsensor_workspace_bytes": (c_size_t, [c_int64, c_int]),
+    "himo_xsensor": (c_int, [c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p,
+                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "himo_boxeval_workspace_bytes": (c_size_t, [c_int, c_void_p, c_void_p]),
     "himo_boxeval_match": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_size_t, c_void_p]),

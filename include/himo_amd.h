@@ -717,6 +717,61 @@ int himo_boxfit(int64_t n, const float* d_pts, int pitch, const int32_t* d_label
                 size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Cross-sensor consistency (`python -m himo_amd.eval_xsensor`): inside every cluster of labelled points, the distance from each point
+ * to the nearest point ANOTHER SENSOR recorded -- large where the sensors' copies of a moving object are displaced, the sampling spacing
+ * where they lie on top of one another; a score that needs no ground truth (himo_amd/csrc/xsensor.hip).  The reference has no such
+ * stage: this one follows the build's own written rule, "cross-sensor consistency, v1" (the module docstring of
+ * himo_amd/eval_xsensor.py is normative): PARITY UNPINNED.  Timed on synthetic sweeps only (profiles/xsensor.txt); nothing has been
+ * tried on field data.
+ *
+ *   d_pts float[n][pitch], pitch >= 3 (x, y, z first), raw or compensated as the caller decides; d_labels int32[n], 0 = none, else
+ *   1..n_clusters; d_group uint8[n], the sensor id; d_dt float[n] or NULL, the capture time; d_motion float[n][3] or NULL, a
+ *   displacement per sweep period.  The labelled rows SORTED BY LABEL, as for himo_boxfit: d_rows int64[n_clustered] the buffer row of
+ *   every sorted row; cluster k owns the sorted rows offsets[k] .. offsets[k + 1], given on the host (validation) and on the device.
+ *   The clusters of several sweeps and results may be laid end to end in one call: more segments over one point buffer.
+ *   usable    a row is USABLE iff its label is in 1..n_clusters, x, y, z are finite, group <= 7 and, with d_dt, dt is finite;
+ *             n = the cluster's usable rows, n_g those of group g
+ *   state     TOO_FEW iff n < min_points; else TOO_LARGE iff n > max_points; else group g is LIVE iff n_g >= min_group and the
+ *             cluster is ONE_SENSOR iff fewer than two groups are live; else SCORED.  A cluster that is not SCORED writes its state, n
+ *             and the n_g, and zeros elsewhere
+ *   search    a QUERY is a usable row of a live group; its candidates are the usable rows of the same cluster in ANOTHER live group;
+ *             float32, every operation rounding on its own: dx = x_i - x_j, ..., d2 = (dx*dx + dy*dy) + dz*dz; m_i = the minimum
+ *             over the candidates (order-free: defined bit for bit; no index is reported)
+ *   terms     float64: d_i = sqrt(m_i); c_i = d_i < trunc ? d_i : trunc (+inf clips); NEAR iff d_i <= near; q(x) = llrint(x * 2^24);
+ *             every sum is an int64 sum, so no order is part of the rule
+ * Outputs: d_info int32[C][4] = state, n, live-group bit mask, query rows; d_rec int64[C][8][4], per group = n_g, the sum of q(dt) over
+ * the group's usable rows (dt clipped to +-1024 s; 0 without d_dt), the sum of q(c_i) over its query rows, its NEAR count; d_mot
+ * int64[C][2] = the usable rows with a finite motion and the sum of q(s_i) over them, s_i = sqrt((mx*mx + my*my) + mz*mz) in float64
+ * clipped at 1024 m (zeros without d_motion); d_min_d2 float[n_clustered] or NULL: m_i per sorted row, +inf for a row that is no query.
+ * All three are written whole: they need no clearing.
+ * Refused with HIMO_ERR_INVALID_ARGUMENT, nothing launched and nothing written: a negative count, pitch < 3, n_clustered > n,
+ * clustered rows without clusters, offsets that are negative, decreasing, do not start at 0 or end at n_clustered, NULL or misaligned
+ * where data is required, and parameters outside: trunc finite, > 0 and <= 1024, near finite and >= 0, min_group >= 1, min_points
+ * >= 2, min_points <= max_points <= 2^20.  n > 2^31 - 1: HIMO_ERR_UNSUPPORTED.  A short, NULL or misaligned (16 bytes) workspace:
+ * HIMO_ERR_WORKSPACE (himo_xsensor_workspace_bytes returns 0 for what it refuses).  n_clusters == 0: HIMO_OK, nothing launched.
+ * One clear and three launches (count, search, reduce), asynchronous on `stream`, whatever the clusters; no float atomics. */
+typedef struct himo_xsensor_params {
+    float trunc;           /* the distance a row's term is clipped at, metres */
+    float near;            /* a row at most this far from another sensor's point is NEAR, metres */
+    int32_t min_group;     /* fewer usable rows of a sensor in a cluster: that sensor is not live there */
+    int32_t min_points;    /* fewer usable rows: TOO_FEW */
+    int32_t max_points;    /* more usable rows: TOO_LARGE */
+} himo_xsensor_params;
+
+#define HIMO_XSENSOR_SCORED 0
+#define HIMO_XSENSOR_TOO_FEW 1
+#define HIMO_XSENSOR_ONE_SENSOR 2
+#define HIMO_XSENSOR_TOO_LARGE 3
+#define HIMO_XSENSOR_GROUPS 8
+#define HIMO_XSENSOR_CHUNK 1024    /* rows the search stages in LDS at a time (a size its tests straddle) */
+
+size_t himo_xsensor_workspace_bytes(int64_t n_clustered, int n_clusters);
+int himo_xsensor(int64_t n, const float* d_pts, int pitch, const int32_t* d_labels, const uint8_t* d_group, const float* d_dt,
+                 const float* d_motion, int64_t n_clustered, const int64_t* d_rows, int n_clusters, const int64_t* h_offsets,
+                 const int64_t* d_offsets, const himo_xsensor_params* params, int32_t* d_info, int64_t* d_rec, int64_t* d_mot,
+                 float* d_min_d2, void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Box evaluation (`python -m himo_amd.eval_box`): the rotated BEV IoU and the 3-D IoU of oriented boxes, and the greedy matching of
  * two sets of boxes per sweep by descending BEV IoU (himo_amd/csrc/boxeval.hip).  The reference has no such stage: this one follows
  * the build's own written rule, "box evaluation, v1" (the module docstring of himo_amd/eval_box.py is normative): PARITY UNPINNED.
