@@ -309,7 +309,7 @@ class Accumulator:
         return self._emit(True)
 
 
-def _device_rows(pc, dev):
+def device_rows(pc, dev):
     import torch
     t = pc if isinstance(pc, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(pc, dtype=np.float32))
     if t.dim() != 2 or t.shape[1] < 3:
@@ -324,7 +324,7 @@ def flow_motion(pc0, flow, pose0, pose1):
     import torch
     from . import _lib
     dev = pc0.device if isinstance(pc0, torch.Tensor) and pc0.is_cuda else _lib.require_gpu()
-    pts = _device_rows(pc0, dev)
+    pts = device_rows(pc0, dev)
     n = int(pts.shape[0])
     fl = flow if isinstance(flow, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(flow, dtype=np.float32))
     fl = fl.to(device=dev, dtype=torch.float32).contiguous()
@@ -362,7 +362,7 @@ def accumulate_target(sweeps, poses, t: int, window: int = 10, params: AccumPara
     from . import _lib
     dev = acc.device if acc is not None else _lib.require_gpu()
     src = sources(int(t), len(sweeps), window)
-    pts = {k: _device_rows(sweeps[k], dev) for k in src}
+    pts = {k: device_rows(sweeps[k], dev) for k in src}
     of = lambda seq, k, dtype: None if seq is None else _device_column(seq[k], dev, dtype)        # noqa: E731
     if acc is None:
         acc = Accumulator(dev, params, capacity_for(sum(int(p.shape[0]) for p in pts.values())))
@@ -448,7 +448,7 @@ def accumulate_scene(dataset, items: list, out_path, res_name: str = "seflowpp_b
         engine = CompDisEngine()
         moved, skips, motions, intens, labels = [], [], [], [], []
         for f in frames:
-            pc0 = _device_rows(f["pc0"], dev)
+            pc0 = device_rows(f["pc0"], dev)
             motions.append(flow_motion(pc0, f[motion_key], f["pose0"], f["pose1"]) if motion_key else None)
             if intensity:                                                     # column 3 of the raw rows, read in place where they have four
                 intens.append(pc0[:, 3] if pc0.shape[1] == 4 else _device_column(np.asarray(f["pc0"])[:, 3], dev, torch.float32))
@@ -484,10 +484,8 @@ def accumulate_scene(dataset, items: list, out_path, res_name: str = "seflowpp_b
             out.append((xyz.cpu().numpy(), lag.cpu().numpy(), count.cpu().numpy()) + extra)
     seconds = time.perf_counter() - t0
     if opener is None:
-        from .save import h5_writer
-        mod, how = h5_writer()
-        if mod is None:
-            raise RuntimeError(f"{out_path}: writing a scene file needs an HDF5 library (h5py, or libhdf5 for himo_amd.h5c; HIMO_LIBHDF5 names one): {how}")
+        from .stored import h5_module
+        mod = h5_module(f"{out_path}: writing a scene file")
         opener = lambda p: mod.File(p, "a")                                   # noqa: E731
     with opener(out_path) as h:
         for f, (xyz, lag, count, inten, lab) in zip(frames, out):
@@ -531,7 +529,8 @@ def main(data_dir: str, out_dir: str, res_name: str = "seflowpp_best", window: i
     import warnings
     from . import distenv
     from .dataset import HDF5Dataset
-    from .save import h5_writer
+    from .stored import check_motion_min, h5_module
+    from .sweeps import scene_items
     if data_name not in ("av2", "scania"):
         raise ValueError(f"data_name={data_name!r}: av2 or scania")
     if params is None:
@@ -542,16 +541,12 @@ def main(data_dir: str, out_dir: str, res_name: str = "seflowpp_best", window: i
     params.check()
     sources(0, 1, window)
     motion_key = _motion_key(res_name, advect, motion_key)
-    if not (np.isfinite(motion_min) and motion_min >= 0):
-        raise ValueError(f"motion_min={motion_min}: finite and >= 0")
+    check_motion_min(motion_min)
     if not (np.isfinite(np.float32(intensity_scale)) and np.float32(intensity_scale) > 0):
         raise ValueError(f"intensity_scale={intensity_scale}: finite and > 0")
     if not sorted(Path(data_dir).glob("*.h5")):
         raise FileNotFoundError(f"{data_dir}: no <scene>.h5 files")
-    mod, how = h5_writer()
-    if mod is None:
-        raise RuntimeError(f"writing scene files into {out_dir} needs an HDF5 library (h5py, or libhdf5 for himo_amd.h5c; HIMO_LIBHDF5 names "
-                           f"one): {how}")
+    mod = h5_module(f"writing scene files into {out_dir}")
     out_dir = Path(out_dir)
     out_dir.mkdir(parents=True, exist_ok=True)
     fields = {"pc0", "pose0", "pose1", "lidar_dt"} | ({"gm0"} if drop_ground else set()) | ({drop_label} if drop_label else set())
@@ -561,18 +556,14 @@ def main(data_dir: str, out_dir: str, res_name: str = "seflowpp_best", window: i
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")                                       # (the last sweep of a scene has no successor: no target)
         ds = HDF5Dataset(data_dir, vis_name=stored if stored else "", fields=tuple(fields))
-    by_scene: dict = {}
-    for i, (s, _) in enumerate(ds.index):
-        by_scene.setdefault(s, []).append(i)
+    by_scene = scene_items(ds)
     scenes = sorted(by_scene)
-    have = [s for s in scenes if (out_dir / f"{s}.h5").exists()]
-    if have and not overwrite:
-        ds.close()
-        raise FileExistsError(f"{out_dir}: {len(have)} of {len(scenes)} scene files exist already, {have[0]}.h5 among them (--overwrite replaces them)")
+    have = [s for s in scenes if (out_dir / f"{s}.h5").exists()]               # (looked up before the ranks meet: none has written yet)
     done = {}
     with distenv.process_group() as (rank, world):
-        err = None
-        try:
+        def loop():
+            if have and not overwrite:
+                raise FileExistsError(f"{out_dir}: {len(have)} of {len(scenes)} scene files exist already, {have[0]}.h5 among them (--overwrite replaces them)")
             for s in scenes[rank::world]:
                 path = out_dir / f"{s}.h5"
                 if path.exists():
@@ -582,11 +573,8 @@ def main(data_dir: str, out_dir: str, res_name: str = "seflowpp_best", window: i
                                                intensity=intensity, intensity_scale=intensity_scale, carry_label=carry_label, bin_dir=bin_dir)
                 rate = r["sweeps"] / r["seconds"] if r["seconds"] > 0 else float("inf")
                 print(f"{s}: {r['sweeps']} sweeps, {r['rows_in']} rows in, {r['rows_out']} rows out  ({rate:.1f} sweeps/s)")
-        except Exception as e:                                                # arrive at the rendezvous anyway, then re-raise
-            err = e
-        finally:
-            ds.close()
-        distenv.rendezvous(err, "its scene files")
+
+        distenv.run_shard(loop, "its scene files", closing=(ds,))
         if rank == 0:
             _write_index(out_dir, [[s, t] for s, t in ds.index])
     return done

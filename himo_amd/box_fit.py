@@ -72,6 +72,8 @@ from pathlib import Path
 
 import numpy as np
 
+from .stored import fmt, ratio
+
 FITTED, TOO_FEW, TOO_LARGE = 0, 1, 2
 STATE_NAMES = ("fitted", "too few", "too large")
 MAX_DIRS = 128
@@ -169,7 +171,7 @@ def fit_labelled(pts, labels, n_clusters: int, dirs, params: BoxParams | None = 
     wait, through pinned memory behind an event."""
     import torch
     from . import _lib
-    from .icpflow import _pinned_words
+    from .icpflow import pinned_words
     lib, P = _lib.load(), _lib.ptr
     params = params if params is not None else BoxParams()
     table = check_directions(dirs)
@@ -199,7 +201,7 @@ def fit_labelled(pts, labels, n_clusters: int, dirs, params: BoxParams | None = 
     count = (lab.max().to(torch.int64) if n else torch.zeros((), dtype=torch.int64, device=dev)).reshape(1)
     words = [count, offsets] + ([extra.to(torch.int64).reshape(-1)] if extra is not None else [])
     total = sum(int(w.numel()) for w in words)
-    host = _pinned_words(total)
+    host = pinned_words(total)
     host[:total].copy_(torch.cat(words), non_blocking=True)
     landed = torch.cuda.Event()
     landed.record(torch.cuda.current_stream(dev))
@@ -301,11 +303,11 @@ def boxes_key(name: str) -> str:
     return f"boxes_{name}"
 
 
-def _new_totals() -> dict:
+def new_totals() -> dict:
     return {"boxes": 0, "moving": 0, "sum_l_moving": 0.0, "sum_w_moving": 0.0}
 
 
-def _new_against() -> dict:
+def new_against() -> dict:
     zero = lambda: {"pairs": 0, "sum_dl": 0.0, "sum_dw": 0.0, "sum_centre": 0.0, "sum_yaw_deg": 0.0}      # noqa: E731
     return {"all": zero(), "moving": zero()}
 
@@ -338,45 +340,29 @@ def tally_against(acc: dict, rows, moving, labels, rows_b, moving_b, labels_b) -
 
 def summary(totals: dict, against: dict | None, against_name: str | None) -> dict:
     """the numbers of the table and of ``--json``, per result"""
-    mean = lambda s, n: s / n if n else None                        # noqa: E731
     out = {}
     for name, t in totals.items():
-        out[name] = {"boxes": t["boxes"], "moving": t["moving"], "mean_l_moving": mean(t["sum_l_moving"], t["moving"]),
-                     "mean_w_moving": mean(t["sum_w_moving"], t["moving"])}
+        out[name] = {"boxes": t["boxes"], "moving": t["moving"], "mean_l_moving": ratio(t["sum_l_moving"], t["moving"]),
+                     "mean_w_moving": ratio(t["sum_w_moving"], t["moving"])}
         if against is not None:
             out[name]["against"] = {"name": against_name}
             for key, a in against[name].items():
-                out[name]["against"][key] = {"pairs": a["pairs"], "mean_dl": mean(a["sum_dl"], a["pairs"]), "mean_dw": mean(a["sum_dw"], a["pairs"]),
-                                             "mean_centre": mean(a["sum_centre"], a["pairs"]), "mean_yaw_deg": mean(a["sum_yaw_deg"], a["pairs"])}
+                out[name]["against"][key] = {"pairs": a["pairs"], "mean_dl": ratio(a["sum_dl"], a["pairs"]), "mean_dw": ratio(a["sum_dw"], a["pairs"]),
+                                             "mean_centre": ratio(a["sum_centre"], a["pairs"]), "mean_yaw_deg": ratio(a["sum_yaw_deg"], a["pairs"])}
     return out
 
 
 def _table(numbers: dict) -> str:
-    f = lambda v, spec=".3f": "-" if v is None else format(v, spec)      # noqa: E731
     lines = []
     for name, r in numbers.items():
-        line = f"{name}: {r['boxes']} boxes, {r['moving']} moving, mean l {f(r['mean_l_moving'])} m, mean w {f(r['mean_w_moving'])} m (moving)"
+        line = f"{name}: {r['boxes']} boxes, {r['moving']} moving, mean l {fmt(r['mean_l_moving'])} m, mean w {fmt(r['mean_w_moving'])} m (moving)"
         if "against" in r:
             for key in ("all", "moving"):
                 a = r["against"][key]
-                line += (f"; against {r['against']['name']} ({key}, {a['pairs']} pairs): |dl| {f(a['mean_dl'])} m, |dw| {f(a['mean_dw'])} m, "
-                         f"centre {f(a['mean_centre'])} m, yaw {f(a['mean_yaw_deg'], '.2f')} deg")
+                line += (f"; against {r['against']['name']} ({key}, {a['pairs']} pairs): |dl| {fmt(a['mean_dl'])} m, |dw| {fmt(a['mean_dw'])} m, "
+                         f"centre {fmt(a['mean_centre'])} m, yaw {fmt(a['mean_yaw_deg'], '.2f')} deg")
         lines.append(line)
     return "\n".join(lines)
-
-
-def _merge(parts: list) -> tuple:
-    """the ranks' (totals, against) added up"""
-    totals, against = parts[0]
-    for t2, a2 in parts[1:]:
-        for name in totals:
-            for k in totals[name]:
-                totals[name][k] += t2[name][k]
-            if against is not None:
-                for key in against[name]:
-                    for k in against[name][key]:
-                        against[name][key][k] += a2[name][key][k]
-    return totals, against
 
 
 def sweep_boxes(fitter: BoxFitter, engine, frame: dict, name: str, label_key: str, motion_key: str | None, cluster: str = "dbscan",
@@ -385,9 +371,9 @@ def sweep_boxes(fitter: BoxFitter, engine, frame: dict, name: str, label_key: st
     recorded), the motion the stored flow ``name`` (``raw``: ``motion_key``, or none) less the ego motion (``himo_accum_motion``), the
     labels the stored ``label_key`` or, for ``cluster``, a clustering of the compensated non-ground in-range points."""
     import torch
-    from .accumulate import _device_rows, flow_motion
+    from .accumulate import device_rows, flow_motion
     dev = fitter.device
-    pc0 = _device_rows(frame["pc0"], dev)
+    pc0 = device_rows(frame["pc0"], dev)
     if name == "raw":
         pts = pc0
     else:
@@ -408,17 +394,6 @@ def sweep_boxes(fitter: BoxFitter, engine, frame: dict, name: str, label_key: st
     return fitter.fit(pts, ids, motion)
 
 
-def _stored_label(ds, i, key):
-    """(the stored label array ``key`` of item ``i``, the sweep's number of points), read without the sweep itself"""
-    from .dataset import NpzDataset
-    if isinstance(ds, NpzDataset):
-        scene_id, ts = ds.index[i]
-        with np.load(ds.directory / scene_id / f"{ts}.npz") as z:
-            return np.asarray(z[key]), int(z["pc0"].shape[0])
-    d = ds.read(i, fields=(key, "lidar_dt"))
-    return np.asarray(d[key]), int(len(d["lidar_dt"]))
-
-
 def main(data_dir: str, res_names, label_key: str, cluster: str = "dbscan", against: str | None = None, json_path: str | None = None,
          overwrite: bool = False, params: BoxParams | None = None, K: int = 90, motion_key: str | None = None,
          motion_min: float = MOTION_MIN, min_cluster_size: int | None = None, min_samples: int | None = None) -> dict:
@@ -428,15 +403,11 @@ def main(data_dir: str, res_names, label_key: str, cluster: str = "dbscan", agai
     ``motion_key`` (default: the first stored name of ``res_names``; none when there is none, and no box is MOVING then).  Under
     ``torchrun`` whole scenes per rank (h5).  Returns what ``--json`` writes: {name: {"boxes", "moving", "mean_l_moving",
     "mean_w_moving"[, "against"]}} over every rank."""
-    import json
-    from . import distenv
+    from . import distenv, stored
     from .dataset import NpzDataset, open_dataset
-    from .rigid_refine import _present
-    from .save import NpzResultSink, h5_writer
     from .seflow.ssl_label import CLUSTERINGS
-    names = [s for s in (res_names.split(",") if isinstance(res_names, str) else list(res_names)) if s]
-    if not names or len(set(names)) != len(names):
-        raise ValueError(f"res_names={res_names!r}: one or more different names ('raw' = the points as recorded)")
+    from .sweeps import sharded_items
+    names = stored.result_names(res_names, raw_ok=True)
     if not label_key:
         raise ValueError("label_key: a stored integer key (ray_label, flow_instance_id, ...) or 'cluster'")
     if against and label_key == "cluster":
@@ -447,39 +418,27 @@ def main(data_dir: str, res_names, label_key: str, cluster: str = "dbscan", agai
         raise ValueError(f"cluster={cluster!r}: one of {', '.join(CLUSTERINGS)}")
     params = params if params is not None else BoxParams()
     angles(K)
-    stored = [s for s in names if s != "raw"]
+    flows_of = [s for s in names if s != "raw"]
     if motion_key == "raw":
         raise ValueError("--motion_key raw: 'raw' is the zero-motion key, not a stored flow")
-    if motion_key is None and "raw" in names and stored:
-        motion_key = stored[0]
-    flows = list(dict.fromkeys(stored + ([motion_key] if motion_key and "raw" in names else [])))
+    if motion_key is None and "raw" in names and flows_of:
+        motion_key = flows_of[0]
+    flows = list(dict.fromkeys(flows_of + ([motion_key] if motion_key and "raw" in names else [])))
     root = Path(data_dir)
     needs = ["gm0"] if label_key == "cluster" else [label_key]
     keys = [boxes_key(s) for s in names]
-    totals = {s: _new_totals() for s in names}
-    versus = {s: _new_against() for s in names} if against else None
+    sums = {"totals": {s: new_totals() for s in names}, "against": {s: new_against() for s in names} if against else None}
     with distenv.process_group() as (rank, world):
         ds = open_dataset(root, vis_name=flows, eval=False, fields=tuple(["pc0", "pose0", "pose1", "lidar_dt"] + needs + flows))
         npz = isinstance(ds, NpzDataset)
-        if npz:
-            mine = list(range(rank, len(ds), world))
-        else:                                                     # whole scenes per rank: every scene file has one writer
-            scenes = {}
-            for sc, _ in ds.index:
-                scenes.setdefault(sc, len(scenes))
-            mine = [i for i, (sc, _) in enumerate(ds.index) if scenes[sc] % world == rank]
-        err = None
-        try:
+        mine = sharded_items(ds, whole_scenes=not npz)              # whole scenes per rank: every scene file has one writer
+
+        def loop():
             # the refusals, before anything touches the GPU or a file is written
-            mod = None
-            if not npz:
-                mod, how = h5_writer()
-                if mod is None:
-                    raise RuntimeError(f"writing '{keys[0]}' into the scene files of {data_dir} needs an HDF5 library (h5py, or libhdf5 for "
-                                       f"himo_amd.h5c; HIMO_LIBHDF5 names one): {how}")
+            sink = stored.KeySink(ds, root, f"writing '{keys[0]}' into the scene files of {data_dir}")
             for i in mine:
                 where = "/".join(map(str, ds.index[i]))
-                have = _present(ds, i, flows + needs + keys)
+                have = stored.present(ds, i, flows + needs + keys)
                 for s in flows:
                     if s not in have:
                         raise KeyError(f"{s}: {where} holds no result of that name (--res_names / --motion_key name stored flows; 'raw' needs none)")
@@ -488,64 +447,34 @@ def main(data_dir: str, res_names, label_key: str, cluster: str = "dbscan", agai
                 if label_key != "cluster" and label_key not in have:
                     raise KeyError(f"{label_key}: {where} holds no such label (`python -m himo_amd.raymap` writes ray_label)")
                 if label_key != "cluster":
-                    lab, rows = _stored_label(ds, i, label_key)
-                    if lab.ndim != 1 or lab.dtype.kind not in "iu" or len(lab) != rows:
-                        raise ValueError(f"{label_key}: {where} holds {lab.dtype} {lab.shape}, not one integer per point of its {rows} points")
+                    count_key = "pc0" if npz else "lidar_dt"        # a sweep's number of points: the cheapest array that has one row each
+                    got = stored.arrays(ds, i, (label_key, count_key))
+                    stored.check_point_labels(got[label_key], label_key, where, rows=len(got[count_key]))
                 done = [k for k in keys if k in have]
                 if done and not overwrite:
                     raise FileExistsError(f"{where} already holds '{done[0]}': pass --overwrite to replace it")
-            if mine:
-                from .compdis import CompDisEngine
-                fitter = BoxFitter(params=params, K=K, motion_min=motion_min)
-                engine = CompDisEngine()
-                sinks = {s: NpzResultSink(root, boxes_key(s)) for s in names} if npz else None
-                pending, scene = [], None
-
-                def flush():
-                    if pending:
-                        ds.forget(scene)
-                        with mod.File(ds.scene_path(scene), "a") as h:
-                            for ts, key, rows in pending:
-                                g = h[ts]
-                                if key in g:
-                                    del g[key]
-                                g.create_dataset(key, data=rows)
-                        pending.clear()
-
-                for i in mine:
-                    f = ds[i]
-                    if not npz and f["scene_id"] != scene:
-                        flush()
-                        scene = f["scene_id"]
-                    got = {}
+            if not mine:
+                return
+            from .compdis import CompDisEngine
+            fitter = BoxFitter(params=params, K=K, motion_min=motion_min)
+            engine = CompDisEngine()
+            for i in mine:
+                f = ds[i]
+                got = {}
+                for s in names:
+                    r = got[s] = sweep_boxes(fitter, engine, f, s, label_key, motion_key, cluster, min_cluster_size, min_samples)
+                    tally(sums["totals"][s], r.rows, r.moving)
+                    sink.put(f["scene_id"], f["timestamp"], boxes_key(s), r.rows)
+                if against:
+                    b = got[against]
                     for s in names:
-                        r = got[s] = sweep_boxes(fitter, engine, f, s, label_key, motion_key, cluster, min_cluster_size, min_samples)
-                        tally(totals[s], r.rows, r.moving)
-                        if npz:
-                            sinks[s](i, f, r.rows)
-                        else:
-                            pending.append((str(f["timestamp"]), boxes_key(s), r.rows))
-                    if against:
-                        b = got[against]
-                        for s in names:
-                            tally_against(versus[s], got[s].rows, got[s].moving, got[s].labels, b.rows, b.moving, b.labels)
-                flush()
-        except Exception as e:                                    # arrive at the rendezvous anyway, then re-raise
-            err = e
-        finally:
-            if hasattr(ds, "close"):
-                ds.close()
-        distenv.rendezvous(err, "its share of the boxes")
-        if world > 1:
-            import torch.distributed as dist
-            parts = [None] * world
-            dist.all_gather_object(parts, (totals, versus))
-            totals, versus = _merge(parts)
-        numbers = summary(totals, versus, against)
-        if rank == 0:
-            print(f"box_fit (cluster boxes, v1; parity unpinned), labels '{label_key}':\n{_table(numbers)}")
-            if json_path:
-                Path(json_path).write_text(json.dumps(numbers, indent=1) + "\n")
+                        tally_against(sums["against"][s], got[s].rows, got[s].moving, got[s].labels, b.rows, b.moving, b.labels)
+            sink.close()                                            # (on success only: a failed run leaves its last scene as it was)
+
+        distenv.run_shard(loop, "its share of the boxes", closing=(ds,))
+        total = distenv.gathered(sums)
+        numbers = summary(total["totals"], total["against"], against)
+        distenv.report(rank, f"box_fit (cluster boxes, v1; parity unpinned), labels '{label_key}':\n{_table(numbers)}", numbers, json_path)
     return numbers
 
 

@@ -112,12 +112,58 @@ def rendezvous(err: Exception | None, what: str = "its share of the frames") -> 
         raise RuntimeError(f"another rank failed; this rank finished {what}")
 
 
-def run_shard(loop, what: str = "its share of the frames") -> None:
+def run_shard(loop, what: str = "its share of the frames", closing=()) -> None:
     """``loop()`` -- this rank's share of the work -- then the rendezvous, which a rank whose loop raised an ``Exception`` reaches too
-    (``rendezvous`` raises it there)."""
+    (``rendezvous`` raises it there).  In between, whether or not the loop raised, every object of ``closing`` that has a ``close`` is
+    closed, in order (a dataset, a drain and then its sink); ``closing`` may be a callable that returns them, for objects the loop
+    makes.  An error of a close is kept only if the loop raised none."""
     err = None
     try:
         loop()
     except Exception as e:                                       # (an interrupt leaves at once; the launcher ends the job)
         err = e
+    for obj in (closing() if callable(closing) else closing):
+        if hasattr(obj, "close"):
+            try:
+                obj.close()
+            except Exception as e:
+                err = err or e
     rendezvous(err, what)
+
+
+def add_sums(a, b):
+    """The sum of two ranks' running sums of one shape: a dict is added key by key, a list of numbers element by element (``tp`` per
+    threshold, ``states`` per state), numbers add, None (a table that is not kept) stays None.  Returns a new structure."""
+    if a is None and b is None:
+        return None
+    if isinstance(a, dict):
+        if a.keys() != b.keys():
+            raise ValueError(f"sums of different shapes: {sorted(a)} and {sorted(b)}")
+        return {k: add_sums(v, b[k]) for k, v in a.items()}
+    if isinstance(a, list):
+        if len(a) != len(b):
+            raise ValueError(f"sums of different shapes: lists of {len(a)} and {len(b)}")
+        return [add_sums(x, y) for x, y in zip(a, b)]
+    return a + b
+
+
+def gathered(sums, add=add_sums):
+    """every rank's ``sums`` folded with ``add`` in rank order, on every rank; ``sums`` itself without a process group"""
+    import functools
+    import torch.distributed as dist
+    _, world = rank_world()
+    if world == 1:
+        return sums
+    parts = [None] * world
+    dist.all_gather_object(parts, sums)
+    return functools.reduce(add, parts)
+
+
+def report(rank: int, lines: str, numbers, json_path) -> None:
+    """the tail of a program that prints tables: rank 0 prints ``lines`` and writes ``numbers`` to ``json_path`` where one is given"""
+    import json
+    from pathlib import Path
+    if rank == 0:
+        print(lines)
+        if json_path:
+            Path(json_path).write_text(json.dumps(numbers, indent=1) + "\n")

@@ -75,6 +75,7 @@ from pathlib import Path
 import numpy as np
 
 from .box_fit import MOTION_MIN, SENSOR_DT, boxes_key
+from .stored import fmt, ratio
 
 MAX_BOXES = 1024                    # HIMO_BOXEVAL_MAX_BOXES
 TILE = 128                          # HIMO_BOXEVAL_TILE
@@ -236,10 +237,10 @@ def buckets_of(rows_gt: np.ndarray, motion_min: float = MOTION_MIN, sensor_dt: f
 
 def new_sums() -> dict:
     """the running sums of one result name: integers and floats only, so that ranks' sums add up"""
-    from .box_fit import _new_against
+    from .box_fit import new_against
     out = {"pred": 0, "buckets": {}}
     for key in bucket_keys():
-        out["buckets"][key] = {"gt": 0, "pairs": 0, "sum_iou": 0.0, "sum_iou3": 0.0, "tp": [0] * len(TAUS), "shape": _new_against()["all"]}
+        out["buckets"][key] = {"gt": 0, "pairs": 0, "sum_iou": 0.0, "sum_iou3": 0.0, "tp": [0] * len(TAUS), "shape": new_against()["all"]}
     return out
 
 
@@ -272,42 +273,25 @@ def tally(sums: dict, rows_gt, rows_pred, match_gt, iou_gt, motion_min: float = 
             tally_against(acc, rows_gt[kept], on, ids, rows_pred[match_gt[kept]], on, ids)
 
 
-def merge(parts: list) -> dict:
-    """the ranks' {name: sums} added up"""
-    def add(a, b):
-        for k, v in b.items():
-            if isinstance(v, dict):
-                add(a[k], v)
-            elif isinstance(v, list):
-                a[k] = [x + y for x, y in zip(a[k], v)]
-            else:
-                a[k] += v
-    total = parts[0]
-    for p in parts[1:]:
-        add(total, p)
-    return total
-
-
 def summary(sums: dict, pair_by: str = "iou") -> dict:
     """the numbers of the tables and of ``--json``: {name: {bucket: {...}}}"""
-    div = lambda a, b: a / b if b else None                         # noqa: E731
     out = {}
     for name, t in sums.items():
         out[name] = {"pred": t["pred"], "buckets": {}}
         for key, b in t["buckets"].items():
             sh = b["shape"]
-            r = {"gt": b["gt"], "pairs": b["pairs"], "mean_iou": div(b["sum_iou"], b["pairs"]), "mean_iou3": div(b["sum_iou3"], b["pairs"]),
-                 "mean_dl": div(sh["sum_dl"], sh["pairs"]), "mean_dw": div(sh["sum_dw"], sh["pairs"]),
-                 "mean_centre": div(sh["sum_centre"], sh["pairs"]), "mean_yaw_deg": div(sh["sum_yaw_deg"], sh["pairs"])}
+            r = {"gt": b["gt"], "pairs": b["pairs"], "mean_iou": ratio(b["sum_iou"], b["pairs"]), "mean_iou3": ratio(b["sum_iou3"], b["pairs"]),
+                 "mean_dl": ratio(sh["sum_dl"], sh["pairs"]), "mean_dw": ratio(sh["sum_dw"], sh["pairs"]),
+                 "mean_centre": ratio(sh["sum_centre"], sh["pairs"]), "mean_yaw_deg": ratio(sh["sum_yaw_deg"], sh["pairs"])}
             if pair_by == "iou":
                 r["at"] = {}
                 for n, tau in enumerate(TAUS):
                     tp = b["tp"][n]
                     fn = b["gt"] - tp
-                    at = {"tp": tp, "fn": fn, "recall": div(tp, tp + fn)}
+                    at = {"tp": tp, "fn": fn, "recall": ratio(tp, tp + fn)}
                     if key == "all":
                         fp = t["pred"] - tp
-                        p, rc = div(tp, tp + fp), at["recall"]
+                        p, rc = ratio(tp, tp + fp), at["recall"]
                         at.update(fp=fp, precision=p, f1=None if p is None or rc is None or p + rc == 0 else 2 * p * rc / (p + rc))
                     r["at"][f"{tau:g}"] = at
             out[name]["buckets"][key] = r
@@ -315,32 +299,20 @@ def summary(sums: dict, pair_by: str = "iou") -> dict:
 
 
 def _table(name: str, r: dict, gt: str, pair_by: str) -> str:
-    f = lambda v, spec=".3f": "-" if v is None else format(v, spec)      # noqa: E731
     lines = [f"{name} against {gt} ({'greedy matching by BEV IoU' if pair_by == 'iou' else 'pairs by label'}): {r['pred']} predicted boxes, "
              f"{r['buckets']['all']['gt']} ground-truth boxes"]
     for key, b in r["buckets"].items():
-        line = (f"  {key:<12} gt {b['gt']:>6} pairs {b['pairs']:>6}  iou {f(b['mean_iou'])} iou3 {f(b['mean_iou3'])}  |dl| {f(b['mean_dl'])} m "
-                f"|dw| {f(b['mean_dw'])} m centre {f(b['mean_centre'])} m yaw {f(b['mean_yaw_deg'], '.2f')} deg")
+        line = (f"  {key:<12} gt {b['gt']:>6} pairs {b['pairs']:>6}  iou {fmt(b['mean_iou'])} iou3 {fmt(b['mean_iou3'])}  |dl| {fmt(b['mean_dl'])} m "
+                f"|dw| {fmt(b['mean_dw'])} m centre {fmt(b['mean_centre'])} m yaw {fmt(b['mean_yaw_deg'], '.2f')} deg")
         for tau, at in b.get("at", {}).items():
-            line += f"  @{tau}: TP {at['tp']} FN {at['fn']} R {f(at['recall'])}"
+            line += f"  @{tau}: TP {at['tp']} FN {at['fn']} R {fmt(at['recall'])}"
             if "fp" in at:
-                line += f" FP {at['fp']} P {f(at['precision'])} F1 {f(at['f1'])}"
+                line += f" FP {at['fp']} P {fmt(at['precision'])} F1 {fmt(at['f1'])}"
         lines.append(line)
     return "\n".join(lines)
 
 
 # ---- the program ------------------------------------------------------------------------------------------------------------------------
-def _stored_boxes(ds, i, keys) -> dict:
-    """the stored arrays ``keys`` of item ``i`` that exist, read without the sweep itself"""
-    from .dataset import NpzDataset
-    if isinstance(ds, NpzDataset):
-        scene_id, ts = ds.index[i]
-        with np.load(ds.directory / scene_id / f"{ts}.npz") as z:
-            return {k: np.asarray(z[k]) for k in keys if k in z.files}
-    d = ds.read(i, fields=tuple(keys))
-    return {k: np.asarray(d[k]) for k in keys if k in d}
-
-
 def label_pairs(rows_gt: np.ndarray, rows_pred: np.ndarray):
     """rule G: (rows of gt, rows of pred) that carry the same label id in column 10, in ascending id (the first row of an id on a side)"""
     ia = np.unique(rows_gt[:, 10], return_index=True)
@@ -354,12 +326,10 @@ def main(data_dir: str, gt: str, res_names, pair_by: str = "iou", min_iou: float
     """The program: the stored ``boxes_<name>`` of every sweep of ``data_dir``, for every name of ``res_names``, against ``boxes_<gt>``;
     ``batch`` sweeps per launch.  Reads nothing but the boxes.  Under ``torchrun`` sweeps ``i % world`` per rank.  Returns what ``--json``
     writes: {name: {"pred", "buckets": {bucket: {...}}}} over every rank."""
-    import json
-    from . import distenv
+    from . import distenv, stored
     from .dataset import open_dataset
-    names = [s for s in (res_names.split(",") if isinstance(res_names, str) else list(res_names)) if s]
-    if not names or len(set(names)) != len(names):
-        raise ValueError(f"res_names={res_names!r}: one or more different names")
+    from .sweeps import sharded_items
+    names = stored.result_names(res_names, raw_ok=False)
     if not gt:
         raise ValueError("--gt: the name whose boxes are the ground truth (`python -m himo_amd.box_fit --res_names flow --label_key flow_instance_id`)")
     if gt in names:
@@ -367,69 +337,49 @@ def main(data_dir: str, gt: str, res_names, pair_by: str = "iou", min_iou: float
     if pair_by not in ("iou", "label"):
         raise ValueError(f"pair_by={pair_by!r}: 'iou' or 'label'")
     min_iou = check_min_iou(min_iou)
-    if isinstance(batch, bool) or not isinstance(batch, (int, np.integer)) or batch < 1:
-        raise ValueError(f"batch={batch!r}: at least 1 sweep per launch")
-    if not (math.isfinite(motion_min) and motion_min >= 0):
-        raise ValueError(f"motion_min={motion_min}: finite and >= 0")
-    root = Path(data_dir)
+    stored.at_least_one("batch", batch, " sweep per launch")
+    stored.check_motion_min(motion_min)
     keys = [boxes_key(s) for s in [gt] + names]
     sums = {s: new_sums() for s in names}
     with distenv.process_group() as (rank, world):
-        ds = open_dataset(root, vis_name="", eval=False, fields=tuple(keys))
-        mine = list(range(rank, len(ds), world))
-        err = None
-        try:
+        ds = open_dataset(Path(data_dir), vis_name="", eval=False, fields=tuple(keys))
+        mine = sharded_items(ds, whole_scenes=False)
+
+        def loop():
             # the refusals, before anything touches the GPU
-            stored = {}
+            held = {}
             for i in mine:
                 where = "/".join(map(str, ds.index[i]))
-                have = _stored_boxes(ds, i, keys)
+                have = held[i] = stored.arrays(ds, i, keys)
                 for s, k in zip([gt] + names, keys):
                     if k not in have:
                         raise KeyError(f"{k}: {where} holds no boxes of the name '{s}' (`python -m himo_amd.box_fit --res_names {s} ...` writes them)")
-                    b = have[k]
-                    if b.ndim != 2 or b.shape[1] != 12 or b.dtype != np.float32:
-                        raise ValueError(f"{k}: {where} holds {b.dtype} {b.shape}, not float32 [F][12] box rows")
-                    if len(b) > MAX_BOXES:
-                        raise ValueError(f"{k}: {where} holds {len(b)} boxes: at most {MAX_BOXES} per sweep")
-                stored[i] = have
-            if mine:
-                ev = BoxEvaluator(min_iou=min_iou)
-                for lo in range(0, len(mine), int(batch)):
-                    chunk = mine[lo:lo + int(batch)]
-                    for s in names:
-                        g = [stored[i][boxes_key(gt)] for i in chunk]
-                        p = [stored[i][boxes_key(s)] for i in chunk]
-                        if pair_by == "iou":
-                            res = ev.match(g, p)
-                            for k in range(len(chunk)):
-                                ma, _, ia = res.sweep(k)
-                                tally(sums[s], g[k], p[k], ma, ia, motion_min)
-                        else:
-                            for k in range(len(chunk)):
-                                ig, ip = label_pairs(g[k], p[k])
-                                iou = ev.iou_pairs(g[k], p[k], np.stack([ig, ip], axis=1)).cpu().numpy()
-                                ma, ia = np.full(len(g[k]), -1, dtype=np.int64), np.zeros((len(g[k]), 2))
-                                ma[ig], ia[ig] = ip, iou
-                                tally(sums[s], g[k], p[k], ma, ia, motion_min)
-        except Exception as e:                                    # arrive at the rendezvous anyway, then re-raise
-            err = e
-        finally:
-            if hasattr(ds, "close"):
-                ds.close()
-        distenv.rendezvous(err, "its share of the boxes")
-        if world > 1:
-            import torch.distributed as dist
-            parts = [None] * world
-            dist.all_gather_object(parts, sums)
-            sums = merge(parts)
-        numbers = summary(sums, pair_by)
-        if rank == 0:
-            print(f"eval_box (box evaluation, v1; parity unpinned), min_iou {min_iou:g}:")
-            for s in names:
-                print(_table(s, numbers[s], gt, pair_by))
-            if json_path:
-                Path(json_path).write_text(json.dumps(numbers, indent=1) + "\n")
+                    stored.check_box_rows(have[k], k, where, MAX_BOXES)
+            if not mine:
+                return
+            ev = BoxEvaluator(min_iou=min_iou)
+            for lo in range(0, len(mine), int(batch)):
+                chunk = mine[lo:lo + int(batch)]
+                for s in names:
+                    g = [held[i][boxes_key(gt)] for i in chunk]
+                    p = [held[i][boxes_key(s)] for i in chunk]
+                    if pair_by == "iou":
+                        res = ev.match(g, p)
+                        for k in range(len(chunk)):
+                            ma, _, ia = res.sweep(k)
+                            tally(sums[s], g[k], p[k], ma, ia, motion_min)
+                    else:
+                        for k in range(len(chunk)):
+                            ig, ip = label_pairs(g[k], p[k])
+                            iou = ev.iou_pairs(g[k], p[k], np.stack([ig, ip], axis=1)).cpu().numpy()
+                            ma, ia = np.full(len(g[k]), -1, dtype=np.int64), np.zeros((len(g[k]), 2))
+                            ma[ig], ia[ig] = ip, iou
+                            tally(sums[s], g[k], p[k], ma, ia, motion_min)
+
+        distenv.run_shard(loop, "its share of the boxes", closing=(ds,))
+        numbers = summary(distenv.gathered(sums), pair_by)
+        distenv.report(rank, "\n".join([f"eval_box (box evaluation, v1; parity unpinned), min_iou {min_iou:g}:"] +
+                                       [_table(s, numbers[s], gt, pair_by) for s in names]), numbers, json_path)
     return numbers
 
 

@@ -64,6 +64,8 @@ from pathlib import Path
 
 import numpy as np
 
+from .stored import check_point_labels, fmt, ratio
+
 SCORED, TOO_FEW, ONE_SENSOR, TOO_LARGE = 0, 1, 2, 3
 STATE_NAMES = ("scored", "too few", "one sensor", "too large")
 GROUPS = 8
@@ -151,7 +153,7 @@ def xsensor_labelled(pts, labels, group, n_clusters: int, params: XSensorParams 
     event."""
     import torch
     from . import _lib
-    from .icpflow import _pinned_words
+    from .icpflow import pinned_words
     lib, P = _lib.load(), _lib.ptr
     params = params if params is not None else XSensorParams()
     dev = pts.device
@@ -182,7 +184,7 @@ def xsensor_labelled(pts, labels, group, n_clusters: int, params: XSensorParams 
     offsets = torch.zeros(C + 1, dtype=torch.int64, device=dev)
     if C:
         torch.cumsum(sizes, 0, out=offsets[1:])
-    host = _pinned_words(C + 1)
+    host = pinned_words(C + 1)
     host[:C + 1].copy_(offsets, non_blocking=True)
     landed = torch.cuda.Event()
     landed.record(torch.cuda.current_stream(dev))
@@ -331,56 +333,36 @@ def tally_against(acc: dict, g: dict, keys, g_b: dict, keys_b, with_motion: bool
 
 def summary(totals: dict, against: dict | None, against_name: str | None) -> dict:
     """the numbers of the table and of ``--json``, per name: the derived values and, under "totals", the raw sums"""
-    div = lambda a, b: a / b if b else None                           # noqa: E731
     out = {}
     for name, t in totals.items():
         res = {"states": dict(zip(STATE_NAMES, t["states"])), "buckets": {}, "totals": t}
         for key, b in t["buckets"].items():
-            res["buckets"][key] = {"clusters": b["clusters"], "queries": b["queries"], "mean_X": div(b["sum_X"], b["clusters"]),
-                                   "mean_X_rows": div(b["sum_qc"] / float(UNIT), b["queries"]), "near_share": div(b["near"], b["queries"])}
+            res["buckets"][key] = {"clusters": b["clusters"], "queries": b["queries"], "mean_X": ratio(b["sum_X"], b["clusters"]),
+                                   "mean_X_rows": ratio(b["sum_qc"] / float(UNIT), b["queries"]), "near_share": ratio(b["near"], b["queries"])}
         if against is not None:
-            res["against"] = {"name": against_name, "buckets": {key: {"pairs": a["pairs"], "ratio": div(a["sum_X"], a["sum_X_against"])}
+            res["against"] = {"name": against_name, "buckets": {key: {"pairs": a["pairs"], "ratio": ratio(a["sum_X"], a["sum_X_against"])}
                                                                 for key, a in against[name].items()}, "totals": against[name]}
         out[name] = res
     return out
 
 
 def _table(numbers: dict) -> str:
-    f = lambda v, spec=".4f": "-" if v is None else format(v, spec)      # noqa: E731
     lines = []
     for name, r in numbers.items():
         lines.append(f"{name}: clusters " + ", ".join(f"{k} {v}" for k, v in r["states"].items()))
         for key, b in r["buckets"].items():
-            line = (f"  {key:<14} {b['clusters']:>7} clusters {b['queries']:>9} rows  X {f(b['mean_X'])} m  by rows {f(b['mean_X_rows'])} m  "
-                    f"near {f(b['near_share'], '.3f')}")
+            line = (f"  {key:<14} {b['clusters']:>7} clusters {b['queries']:>9} rows  X {fmt(b['mean_X'], '.4f')} m  by rows {fmt(b['mean_X_rows'], '.4f')} m  "
+                    f"near {fmt(b['near_share'], '.3f')}")
             if "against" in r:
                 a = r["against"]["buckets"][key]
-                line += f"  / {r['against']['name']} {f(a['ratio'], '.3f')} ({a['pairs']} pairs)"
+                line += f"  / {r['against']['name']} {fmt(a['ratio'], '.3f')} ({a['pairs']} pairs)"
             lines.append(line)
     return "\n".join(lines)
 
 
-def _merge(parts: list) -> tuple:
-    """the ranks' (totals, against) added up"""
-    totals, against = parts[0]
-    for t2, a2 in parts[1:]:
-        for name in totals:
-            for s in range(4):
-                totals[name]["states"][s] += t2[name]["states"][s]
-            for key, b in totals[name]["buckets"].items():
-                for k in b:
-                    b[k] += t2[name]["buckets"][key][k]
-            if against is not None:
-                for key, a in against[name].items():
-                    for k in a:
-                        a[k] += a2[name][key][k]
-    return totals, against
-
-
 def _ids_host(a, where: str, key: str, rows: int) -> np.ndarray:
     a = np.asarray(a)
-    if a.ndim != 1 or a.dtype.kind not in "iu" or len(a) != rows:
-        raise ValueError(f"{key}: {where} holds {a.dtype} {a.shape}, not one integer per point of its {rows} points")
+    check_point_labels(a, key, where, rows=rows)
     a = a.astype(np.int64)
     if len(a) and (a.min() < 0 or a.max() >= 1 << _ID_BITS):
         raise ValueError(f"{key}: {where} holds an id outside 0..2^{_ID_BITS} - 1")
@@ -435,15 +417,11 @@ def main(data_dir: str, res_names, label_key: str, motion_key: str | None = None
     (``motion_key``, default the first stored name of ``res_names``), so a cluster lands in the same bucket under every name; with no
     stored name there is no motion and the speed buckets are omitted.  Writes nothing into the scene files.  Under ``torchrun`` sweep i
     is scored by rank i % world and the totals are gathered.  Returns what ``--json`` writes."""
-    import json
-    from . import distenv
+    from . import distenv, stored
     from .dataset import open_dataset
-    from .rigid_refine import _present
     from .seflow.ssl_label import CLUSTERINGS
     from .sweeps import MissingKey, SweepPacker, fed, raise_missing, sharded_batches
-    names = [s for s in (res_names.split(",") if isinstance(res_names, str) else list(res_names)) if s]
-    if not names or len(set(names)) != len(names):
-        raise ValueError(f"res_names={res_names!r}: one or more different names ('raw' = the points as recorded)")
+    names = stored.result_names(res_names, raw_ok=True)
     if not label_key:
         raise ValueError("label_key: a stored integer key (ray_label, flow_instance_id, ...) or 'cluster'")
     if against and against not in names:
@@ -455,26 +433,25 @@ def main(data_dir: str, res_names, label_key: str, motion_key: str | None = None
     if isinstance(batch, bool) or not isinstance(batch, (int, np.integer)) or batch < 1:
         raise ValueError(f"batch={batch!r}: at least one sweep a call")
     params = params if params is not None else XSensorParams()
-    stored = [s for s in names if s != "raw"]
+    flows_of = [s for s in names if s != "raw"]
     if motion_key == "raw":
         raise ValueError("--motion_key raw: 'raw' is the zero-motion key, not a stored flow")
-    if motion_key is None and stored:
-        motion_key = stored[0]
+    if motion_key is None and flows_of:
+        motion_key = flows_of[0]
     with_motion = bool(motion_key)
-    flows = list(dict.fromkeys(stored + ([motion_key] if motion_key else [])))
+    flows = list(dict.fromkeys(flows_of + ([motion_key] if motion_key else [])))
     needs = ["lidar_id"] + (["gm0"] if label_key == "cluster" else [label_key])
-    totals = {s: new_totals(with_motion) for s in names}
-    versus = {s: new_against(with_motion) for s in names} if against else None
+    sums = {"totals": {s: new_totals(with_motion) for s in names}, "against": {s: new_against(with_motion) for s in names} if against else None}
     with distenv.process_group() as (rank, world):
         ds = open_dataset(Path(data_dir), vis_name=flows, eval=False, fields=tuple(["pc0", "pose0", "pose1", "lidar_dt"] + needs + flows))
-        err = None
-        try:
+
+        def loop():
             mine = sharded_batches(ds, int(batch))
             # the refusals, before anything touches the GPU
             try:
                 for i in (i for b in mine for i in b):
                     where = "/".join(map(str, ds.index[i]))
-                    have = _present(ds, i, flows + needs)
+                    have = stored.present(ds, i, flows + needs)
                     for key, hint in [("lidar_id", "the sensor id per point: the extractors write it")] + \
                             [(s, "--res_names / --motion_key name stored flows; 'raw' needs none") for s in flows] + \
                             [("gm0", "--label_key cluster needs the sweep's ground mask: `python -m himo_amd.ground_seg` writes it")
@@ -483,57 +460,47 @@ def main(data_dir: str, res_names, label_key: str, motion_key: str | None = None
                             raise MissingKey(key, [f"[Warning]: No {key} in {where} ({hint}), check the data."])
             except MissingKey as e:
                 raise_missing(e)
-            if mine:
-                from .compdis import CompDisEngine
-                scorer = XSensor(params=params, sensor_dt=sensor_dt)
-                engine = CompDisEngine()
-                dev = scorer.device
+            if not mine:
+                return
+            from .compdis import CompDisEngine
+            scorer = XSensor(params=params, sensor_dt=sensor_dt)
+            engine = CompDisEngine()
+            dev = scorer.device
 
-                def build(idx, upload):
-                    frames = [ds[i] for i in idx]
-                    pk = SweepPacker(frames, upload=upload, device=dev)
-                    packed = {"offsets": pk.offsets_host, "pc0": pk.cat("pc0", np.float32), "lidar_dt": pk.cat("lidar_dt", np.float32),
-                              "lidar_id": pk.cat("lidar_id", np.uint8)}
-                    if packed["pc0"].dim() != 2 or packed["pc0"].shape[1] not in (3, 4):
-                        raise ValueError(f"pc0 is rows of x, y, z[, intensity], not {tuple(packed['pc0'].shape)}")
-                    for s in flows:
-                        packed[s] = pk.cat(s, np.float32, width=3)
-                    if label_key == "cluster":
-                        packed["gm0"] = pk.cat("gm0", np.uint8)
-                    else:
-                        ids = [_ids_host(f[label_key], f"{f['scene_id']}/{f['timestamp']}", label_key, n) for f, n in zip(frames, pk.counts)]
-                        packed["ids"] = pk.upload(ids, np.int64)
-                    return frames, packed
+            def build(idx, upload):
+                frames = [ds[i] for i in idx]
+                pk = SweepPacker(frames, upload=upload, device=dev)
+                packed = {"offsets": pk.offsets_host, "pc0": pk.cat("pc0", np.float32), "lidar_dt": pk.cat("lidar_dt", np.float32),
+                          "lidar_id": pk.cat("lidar_id", np.uint8)}
+                if packed["pc0"].dim() != 2 or packed["pc0"].shape[1] not in (3, 4):
+                    raise ValueError(f"pc0 is rows of x, y, z[, intensity], not {tuple(packed['pc0'].shape)}")
+                for s in flows:
+                    packed[s] = pk.cat(s, np.float32, width=3)
+                if label_key == "cluster":
+                    packed["gm0"] = pk.cat("gm0", np.uint8)
+                else:
+                    ids = [_ids_host(f[label_key], f"{f['scene_id']}/{f['timestamp']}", label_key, n) for f, n in zip(frames, pk.counts)]
+                    packed["ids"] = pk.upload(ids, np.int64)
+                return frames, packed
 
-                for frames, packed in fed(iter(mine), build, device=dev, overlap=overlap):
-                    res, which, keys = score_batch(scorer, engine, frames, packed, names, label_key, motion_key, cluster, min_cluster_size,
-                                                   min_samples)
-                    g, rec = res.glue, res.rec
-                    per = {}
-                    for r, s in enumerate(names):
-                        sel = np.flatnonzero(which == r)
-                        per[s] = ({k: v[sel] for k, v in g.items()}, rec[sel], keys[sel])
-                        tally(totals[s], per[s][0], per[s][1], with_motion)
-                    if against:
-                        for s in names:
-                            tally_against(versus[s], per[s][0], per[s][2], per[against][0], per[against][2], with_motion)
-        except Exception as e:                                    # arrive at the rendezvous anyway, then re-raise
-            err = e
-        finally:
-            if hasattr(ds, "close"):
-                ds.close()
-        distenv.rendezvous(err, "its share of the sweeps")
-        if world > 1:
-            import torch.distributed as dist
-            parts = [None] * world
-            dist.all_gather_object(parts, (totals, versus))
-            totals, versus = _merge(parts)
-        numbers = summary(totals, versus, against)
-        if rank == 0:
-            print(f"eval_xsensor (cross-sensor consistency, v1; parity unpinned), labels '{label_key}'"
-                  f"{', speed from ' + repr(motion_key) if motion_key else ''}:\n{_table(numbers)}")
-            if json_path:
-                Path(json_path).write_text(json.dumps(numbers, indent=1) + "\n")
+            for frames, packed in fed(iter(mine), build, device=dev, overlap=overlap):
+                res, which, keys = score_batch(scorer, engine, frames, packed, names, label_key, motion_key, cluster, min_cluster_size,
+                                               min_samples)
+                g, rec = res.glue, res.rec
+                per = {}
+                for r, s in enumerate(names):
+                    sel = np.flatnonzero(which == r)
+                    per[s] = ({k: v[sel] for k, v in g.items()}, rec[sel], keys[sel])
+                    tally(sums["totals"][s], per[s][0], per[s][1], with_motion)
+                if against:
+                    for s in names:
+                        tally_against(sums["against"][s], per[s][0], per[s][2], per[against][0], per[against][2], with_motion)
+
+        distenv.run_shard(loop, "its share of the sweeps", closing=(ds,))
+        total = distenv.gathered(sums)
+        numbers = summary(total["totals"], total["against"], against)
+        distenv.report(rank, f"eval_xsensor (cross-sensor consistency, v1; parity unpinned), labels '{label_key}'"
+                             f"{', speed from ' + repr(motion_key) if motion_key else ''}:\n{_table(numbers)}", numbers, json_path)
     return numbers
 
 

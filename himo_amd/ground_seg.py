@@ -141,6 +141,7 @@ def segment_scene(path, params: GroundParams, key: str = "ground_mask", overwrit
     """One scene file: read every sweep's ``lidar`` (nothing else), compute the masks ``batch`` sweeps per launch, and only once
     the reads are done open the file for modification and write ``<timestamp>/<key>``.  Returns {"sweeps", "points", "ground"}."""
     from .dataset import h5_reader
+    from .stored import h5_module, put_keys
     path = Path(path)
     masks = []
     with h5_reader().File(path, "r") as f:
@@ -152,18 +153,11 @@ def segment_scene(path, params: GroundParams, key: str = "ground_mask", overwrit
             part = stamps[lo:lo + max(1, int(batch))]
             masks += ground_masks([np.asarray(f[ts]["lidar"][:], dtype=np.float32) for ts in part], params)
     if opener is None:
-        from .save import h5_writer
-        mod, how = h5_writer()
-        if mod is None:
-            raise RuntimeError(f"{path}: writing '{key}' into a scene file needs an HDF5 library (h5py, or libhdf5 for himo_amd.h5c; "
-                               f"HIMO_LIBHDF5 names one): {how}")
+        mod = h5_module(f"{path}: writing '{key}' into a scene file")
         opener = lambda p: mod.File(p, "a")                               # noqa: E731
     with opener(path) as f:
         for ts, m in zip(stamps, masks):
-            g = f[ts]
-            if key in g:
-                del g[key]
-            g.create_dataset(key, data=np.asarray(m, dtype=bool))
+            put_keys(f, ts, {key: np.asarray(m, dtype=bool)})
     points = int(sum(len(m) for m in masks))
     return {"sweeps": len(stamps), "points": points, "ground": int(sum(int(m.sum()) for m in masks))}
 
@@ -173,26 +167,21 @@ def main(data_dir: str, sensor_height: float = 0.0, key: str = "ground_mask", ov
     """The program.  Under ``torchrun`` (one rank per GPU) the scenes are dealt round-robin to the ranks, so every file has one
     writer.  Returns {scene: {"sweeps", "points", "ground"}} of this rank."""
     from . import distenv
-    from .save import h5_writer
+    from .stored import h5_module
     params = params if params is not None else GroundParams(sensor_height=sensor_height)
     scenes = sorted(Path(data_dir).glob("*.h5"))
     if not scenes:
         raise FileNotFoundError(f"{data_dir}: no <scene>.h5 files")
-    mod, how = h5_writer()
-    if mod is None:
-        raise RuntimeError(f"writing '{key}' into the scene files of {data_dir} needs an HDF5 library (h5py, or libhdf5 for himo_amd.h5c; "
-                           f"HIMO_LIBHDF5 names one): {how}")
+    mod = h5_module(f"writing '{key}' into the scene files of {data_dir}")
     done = {}
     with distenv.process_group() as (rank, world):
-        err = None
-        try:
+        def loop():
             for path in scenes[rank::world]:
                 s = done[path.stem] = segment_scene(path, params, key, overwrite, batch, opener=lambda p: mod.File(p, "a"))
                 share = s["ground"] / s["points"] if s["points"] else 0.0
                 print(f"{path.stem}: {s['sweeps']} sweeps, {s['points']} points, {100.0 * share:.1f} % ground -> '{key}'")
-        except Exception as e:                                            # arrive at the rendezvous anyway, then re-raise
-            err = e
-        distenv.rendezvous(err, "its scene files")
+
+        distenv.run_shard(loop, "its scene files")
     return done
 
 

@@ -107,7 +107,7 @@ class IcpParams:
 _tls = __import__("threading").local()
 
 
-def _pinned_words(n: int):
+def pinned_words(n: int):
     """this thread's pinned int64 buffer of at least ``n`` words (one outstanding read-back per thread)"""
     import torch
     buf = getattr(_tls, "words", None)
@@ -193,7 +193,7 @@ class IcpFlow:
         sizes = torch.bincount(labels, minlength=n0 + 1)[1:n0 + 1]
         offsets = torch.zeros(n0 + 1, dtype=torch.int64, device=dev)
         torch.cumsum(sizes, 0, out=offsets[1:])
-        host = _pinned_words(n0 + 3)
+        host = pinned_words(n0 + 3)
         host[:n0 + 3].copy_(torch.cat([count.to(torch.int64), cnt_b.to(torch.int64), offsets]), non_blocking=True)
         landed = torch.cuda.Event()
         landed.record(torch.cuda.current_stream(dev))

@@ -266,6 +266,7 @@ def label_scene(path, params: RaymapParams | None = None, window: int = 5, key: 
     import torch
     from . import _lib
     from .dataset import h5_reader
+    from .stored import h5_module, put_keys
     path = Path(path)
     params = params if params is not None else RaymapParams()
     neighbours(0, 1, window)
@@ -296,19 +297,11 @@ def label_scene(path, params: RaymapParams | None = None, window: int = 5, key: 
             flags.append(dyn.cpu().numpy().astype(np.uint8))
     seconds = time.perf_counter() - t0
     if opener is None:
-        from .save import h5_writer
-        mod, how = h5_writer()
-        if mod is None:
-            raise RuntimeError(f"{path}: writing '{key}' into a scene file needs an HDF5 library (h5py, or libhdf5 for himo_amd.h5c; "
-                               f"HIMO_LIBHDF5 names one): {how}")
+        mod = h5_module(f"{path}: writing '{key}' into a scene file")
         opener = lambda p: mod.File(p, "a")                               # noqa: E731
     with opener(path) as f:
         for ts, lab, dyn in zip(stamps, labels, flags):
-            g = f[ts]
-            for name, data in ((key, lab), (dynamic_key, dyn)):
-                if name in g:
-                    del g[name]
-                g.create_dataset(name, data=data)
+            put_keys(f, ts, {key: lab, dynamic_key: dyn})
     return {"sweeps": len(stamps), "points": int(sum(len(x) for x in labels)), "dynamic": int(sum(int(x.sum()) for x in flags)),
             "clusters": int(sum(int(x.max(initial=0)) for x in labels)), "seconds": seconds}
 
@@ -319,32 +312,27 @@ def main(data_dir: str, window: int = 5, key: str = "ray_label", dynamic_key: st
     """The program.  Under ``torchrun`` (one rank per GPU) the scenes are dealt round-robin to the ranks, so every file has one
     writer.  Returns {scene: what ``label_scene`` returned} of this rank."""
     from . import distenv
-    from .save import h5_writer
     from .seflow.ssl_label import CLUSTERINGS
+    from .stored import h5_module
     if cluster not in CLUSTERINGS:
         raise ValueError(f"cluster={cluster!r}: one of {', '.join(CLUSTERINGS)}")
     params = params if params is not None else RaymapParams()
     scenes = sorted(Path(data_dir).glob("*.h5"))
     if not scenes:
         raise FileNotFoundError(f"{data_dir}: no <scene>.h5 files")
-    mod, how = h5_writer()
-    if mod is None:
-        raise RuntimeError(f"writing '{key}' into the scene files of {data_dir} needs an HDF5 library (h5py, or libhdf5 for himo_amd.h5c; "
-                           f"HIMO_LIBHDF5 names one): {how}")
+    mod = h5_module(f"writing '{key}' into the scene files of {data_dir}")
     done = {}
     with distenv.process_group() as (rank, world):
-        err = None
-        try:
+        def loop():
             for path in scenes[rank::world]:
                 s = done[path.stem] = label_scene(path, params, window, key, dynamic_key, overwrite, opener=lambda p: mod.File(p, "a"),
-                                                       cluster=cluster, min_cluster_size=min_cluster_size, min_samples=min_samples)
+                                                  cluster=cluster, min_cluster_size=min_cluster_size, min_samples=min_samples)
                 share = s["dynamic"] / s["points"] if s["points"] else 0.0
                 rate = s["sweeps"] / s["seconds"] if s["seconds"] > 0 else float("inf")
                 print(f"{path.stem}: {s['sweeps']} sweeps, {s['points']} points, {100.0 * share:.1f} % dynamic, {s['clusters']} clusters "
                       f"-> '{key}', '{dynamic_key}'  ({rate:.1f} sweeps/s)")
-        except Exception as e:                                            # arrive at the rendezvous anyway, then re-raise
-            err = e
-        distenv.rendezvous(err, "its scene files")
+
+        distenv.run_shard(loop, "its scene files")
     return done
 
 

@@ -149,7 +149,7 @@ class RigidRefine:
     def refine(self, pc0, flow, gm0, pose0, pose1):
         import torch
         from . import _lib
-        from .icpflow import _pinned_words
+        from .icpflow import pinned_words
         from .seflow.ssl_label import RANGE_NET, _moved, cluster_points
         lib, dev, s, P = self.lib, self.device, _lib.stream_handle, _lib.ptr
         up = lambda x, dt: (x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))).to(device=dev, dtype=dt)
@@ -178,7 +178,7 @@ class RigidRefine:
         sizes = torch.bincount(labels, minlength=n0 + 1)[1:n0 + 1]
         offsets = torch.zeros(n0 + 1, dtype=torch.int64, device=dev)
         torch.cumsum(sizes, 0, out=offsets[1:])
-        host = _pinned_words(n0 + 2)
+        host = pinned_words(n0 + 2)
         host[:n0 + 2].copy_(torch.cat([count.to(torch.int64), offsets]), non_blocking=True)
         landed = torch.cuda.Event()
         landed.record(torch.cuda.current_stream(dev))
@@ -215,24 +215,15 @@ class RigidRefine:
 
 
 # ---- the program ------------------------------------------------------------------------------------------------------------------------
-def _present(ds, i, names) -> set:
-    """which of ``names`` item ``i`` of the dataset holds, without reading the sweep"""
-    from .dataset import NpzDataset
-    if isinstance(ds, NpzDataset):
-        scene_id, ts = ds.index[i]
-        with np.load(ds.directory / scene_id / f"{ts}.npz") as z:
-            return set(z.files) & set(names)
-    return set(ds.read(i, fields=tuple(names))) & set(names)
-
-
 def main(data_dir: str, res_name: str, out_name: str = "", cluster: str = "dbscan", min_cluster_size=None, min_samples=None,
          params: RigidParams | None = None, overwrite: bool = False) -> dict:
     """The program: for every sweep of ``data_dir`` that has ``res_name`` stored and a successor pose, ``<timestamp>/<out_name>``
     (default ``<res_name>_rigid``) = the refined flow, written through ``save``'s sinks; under ``torchrun`` whole scenes per rank (h5).
     Returns this rank's {"sweeps", "skipped", "clusters", "rounds": {state name: count}}."""
-    from . import distenv
+    from . import distenv, stored
     from .dataset import NpzDataset, open_dataset
     from .save import H5ResultSink, NpzResultSink
+    from .sweeps import sharded_items
     if not res_name or res_name == "raw":
         raise ValueError(f"res_name={res_name!r}: 'raw' is the zero-motion key, not a stored flow; name the result to refine")
     out_name = out_name or f"{res_name}_rigid"
@@ -248,19 +239,15 @@ def main(data_dir: str, res_name: str, out_name: str = "", cluster: str = "dbsca
     with distenv.process_group() as (rank, world):
         ds = open_dataset(root, vis_name=[res_name, out_name], eval=False, fields=("pc0", "pose0", "pose1", "gm0", res_name), zero_copy=True)
         npz = isinstance(ds, NpzDataset)
-        if npz:
-            mine = list(range(rank, len(ds), world))
-        else:                                                     # whole scenes per rank: every scene file has one writer
-            scenes = {}
-            for sc, _ in ds.index:
-                scenes.setdefault(sc, len(scenes))
-            mine = [i for i, (sc, _) in enumerate(ds.index) if scenes[sc] % world == rank]
-        err, sink, drain = None, None, None
-        try:
+        mine = sharded_items(ds, whole_scenes=not npz)              # whole scenes per rank: every scene file has one writer
+        drain = sink = None
+
+        def loop():
+            nonlocal drain, sink
             # the refusals, before anything touches the GPU or a file is written
             todo = []
             for i in mine:
-                have = _present(ds, i, (res_name, out_name, "gm0"))
+                have = stored.present(ds, i, (res_name, out_name, "gm0"))
                 if res_name not in have:
                     totals["skipped"] += 1
                     continue
@@ -269,35 +256,24 @@ def main(data_dir: str, res_name: str, out_name: str = "", cluster: str = "dbsca
                 if "gm0" not in have:
                     raise KeyError("gm0: the refinement needs the sweep's ground mask (`python -m himo_amd.ground_seg` writes it)")
                 todo.append(i)
-            if todo:
-                import torch
-                from .feeder import ResultDrain
-                engine = RigidRefine(params=params, cluster=cluster, min_cluster_size=min_cluster_size, min_samples=min_samples)
-                sink = NpzResultSink(root, out_name) if npz else H5ResultSink(root, out_name, before_write=ds.forget)
-                drain = ResultDrain(lambda key, flow: sink(key[0], key[1], flow), device=engine.device)
-                states = torch.zeros(len(STATE_NAMES), dtype=torch.int64, device=engine.device)
-                for i in todo:
-                    f = ds[i]
-                    flow = engine.refine(np.asarray(f["pc0"]), np.asarray(f[res_name]), np.asarray(f["gm0"]), f["pose0"], f["pose1"])
-                    drain.put((i, f), flow)
-                    states += torch.bincount(engine._last[0][:, :, 0].reshape(-1).to(torch.int64), minlength=len(STATE_NAMES))
-                    totals["sweeps"] += 1
-                    totals["clusters"] += engine.last_clusters
-                totals["rounds"] = dict(zip(STATE_NAMES, (int(v) for v in states.cpu())))
-        except Exception as e:                                    # arrive at the rendezvous anyway, then re-raise
-            err = e
-        finally:
-            if drain is not None:
-                try:
-                    drain.close()
-                except Exception as e:
-                    err = err or e
-            if sink is not None:
-                try:
-                    sink.close()
-                except Exception as e:
-                    err = err or e
-        distenv.rendezvous(err, "its share of the refined flows")
+            if not todo:
+                return
+            import torch
+            from .feeder import ResultDrain
+            engine = RigidRefine(params=params, cluster=cluster, min_cluster_size=min_cluster_size, min_samples=min_samples)
+            sink = NpzResultSink(root, out_name) if npz else H5ResultSink(root, out_name, before_write=ds.forget)
+            drain = ResultDrain(lambda key, flow: sink(key[0], key[1], flow), device=engine.device)
+            states = torch.zeros(len(STATE_NAMES), dtype=torch.int64, device=engine.device)
+            for i in todo:
+                f = ds[i]
+                flow = engine.refine(np.asarray(f["pc0"]), np.asarray(f[res_name]), np.asarray(f["gm0"]), f["pose0"], f["pose1"])
+                drain.put((i, f), flow)
+                states += torch.bincount(engine._last[0][:, :, 0].reshape(-1).to(torch.int64), minlength=len(STATE_NAMES))
+                totals["sweeps"] += 1
+                totals["clusters"] += engine.last_clusters
+            totals["rounds"] = dict(zip(STATE_NAMES, (int(v) for v in states.cpu())))
+
+        distenv.run_shard(loop, "its share of the refined flows", closing=lambda: (drain, sink))
         who = f"rank {rank}: " if world > 1 else ""
         print(f"{who}rigid_refine '{res_name}' -> '{out_name}': {totals['sweeps']} sweeps ({totals['skipped']} without '{res_name}'), "
               f"{totals['clusters']} clusters, rounds " + ", ".join(f"{k} {v}" for k, v in totals["rounds"].items()))

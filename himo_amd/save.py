@@ -14,12 +14,12 @@ file and says so (``dataset.result_file``; the loader reads it back), no sink ke
 """
 from __future__ import annotations
 
-import os
 from pathlib import Path
 
 import numpy as np
 
 from .pipeline import HiMoPipeline, Sample
+from .stored import put_keys, put_npz
 
 
 class _FrameCache:
@@ -112,13 +112,8 @@ class NpzResultSink:
         self.directory, self.res_name = Path(directory), res_name
 
     def __call__(self, index: int, frame: dict, flow: np.ndarray):
-        path = self.directory / frame["scene_id"] / f"{frame['timestamp']}.npz"
-        with np.load(path) as z:
-            arrays = {k: z[k] for k in z.files}
-        arrays[self.res_name] = flow.astype(np.float32)
-        tmp = path.with_name(path.stem + ".writing.npz")       # written aside, then renamed: the feeder thread may be reading
-        np.savez(tmp, **arrays)                                 # this very file as a later frame's history sweep
-        os.replace(tmp, path)
+        # (written aside, then renamed: the feeder thread may be reading this very file as a later frame's history sweep)
+        put_npz(self.directory, frame["scene_id"], frame["timestamp"], {self.res_name: flow.astype(np.float32)})
 
 
 def h5_writer():
@@ -173,10 +168,7 @@ class H5ResultSink:
         if self._open is not None:
             with self._open(self.directory / f"{self._scene}.h5") as f:
                 for ts, flow in self._pending:
-                    g = f[ts]
-                    if self.res_name in g:
-                        del g[self.res_name]                       # re-running a checkpoint replaces its result
-                    g.create_dataset(self.res_name, data=flow)
+                    put_keys(f, ts, {self.res_name: flow})          # re-running a checkpoint replaces its result
             self._supersede_beside()
         else:
             self._flush_beside()

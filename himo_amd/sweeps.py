@@ -2,7 +2,8 @@
 
 * packing: sweeps laid end to end (``sweep_offsets``, ``SweepPacker``), every device tensor made by one ``upload(parts, dtype)``
   call -- ``host_upload`` by default, the staging hook of ``feeder.BatchFeeder`` when the batch is fed;
-* the loop: this rank's share of a dataset in batches (``sharded_batches``), the batches built on the calling thread or two ahead
+* the loop: this rank's share of a dataset in batches (``sharded_batches``), by whole scenes (``sharded_scenes``) or as item indices
+  (``sharded_items``), the batches built on the calling thread or two ahead
   by ``feeder.BatchFeeder`` (``fed``), warnings that travel with a missing key (``MissingKey``), the order in which feeder and
   ``feeder.ResultDrain`` are closed (``draining``) and the one-Feather-file-per-sweep writer (``FeatherSink``);
 * ``timed``: the "Time used" tail of the command lines.
@@ -87,6 +88,29 @@ def sharded_batches(dataset, batch_frames: int) -> list:
     rank, world = distenv.rank_world()
     mine = range(rank, len(dataset), world)
     return [list(mine[lo:lo + batch_frames]) for lo in range(0, len(mine), batch_frames)]
+
+
+def scene_items(ds) -> dict:
+    """scene -> its item indices, from the dataset's index: scenes in the order they first appear, items in index order"""
+    scenes = {}
+    for i, (scene, _) in enumerate(ds.index):
+        scenes.setdefault(scene, []).append(i)
+    return scenes
+
+
+def sharded_scenes(ds) -> list:
+    """This rank's ``(scene, items)``: scene number n of ``scene_items`` belongs to rank n % world, so a scene file has one writer"""
+    rank, world = distenv.rank_world()
+    return [(scene, items) for n, (scene, items) in enumerate(scene_items(ds).items()) if n % world == rank]
+
+
+def sharded_items(ds, whole_scenes: bool) -> list:
+    """This rank's item indices, ascending: item i % world (the npz container: a file per sweep), or with ``whole_scenes`` the items
+    of ``sharded_scenes``"""
+    rank, world = distenv.rank_world()
+    if not whole_scenes:
+        return list(range(rank, len(ds), world))
+    return sorted(i for _, items in sharded_scenes(ds) for i in items)
 
 
 def fed(source, build, device=None, overlap: bool = True):

@@ -89,6 +89,7 @@ import numpy as np
 
 from .box_fit import MOTION_MIN, SENSOR_DT, boxes_key
 from .eval_box import MIN_IOU, SPEED_BUCKETS, check_min_iou, speed_bucket
+from .stored import fmt, ratio
 
 MAX_BOXES = 512                     # HIMO_BOXTRACK_MAX
 MIN_HITS = 3
@@ -349,29 +350,21 @@ def tally_mot(sums: dict, sweeps, motion_min: float = MOTION_MIN, sensor_dt: flo
             prev[ident] = tid
 
 
-def merge(parts: list) -> dict:
-    """the ranks' {name: sums} added up (lists: joined)"""
-    def add(a, b):
-        for k, v in b.items():
-            if isinstance(v, dict):
-                add(a[k], v)
-            else:
-                a[k] = a[k] + v
-    total = parts[0]
-    for p in parts[1:]:
-        add(total, p)
-    return total
+def add_sums(a: dict, b: dict) -> dict:
+    """two ranks' {name: sums} added up: ``distenv.add_sums``, except that ``lengths`` -- one entry per confirmed track -- is joined"""
+    from .distenv import add_sums as add
+    less = lambda sums: {s: {k: v for k, v in t.items() if k != "lengths"} for s, t in sums.items()}     # noqa: E731
+    return {s: dict(t, lengths=a[s]["lengths"] + b[s]["lengths"]) for s, t in add(less(a), less(b)).items()}
 
 
 def summary(sums: dict, with_gt: bool) -> dict:
     """the numbers of the tables and of ``--json``: {name: {...}}"""
-    div = lambda a, b: a / b if b else None                         # noqa: E731
     out = {}
     for name, t in sums.items():
         lengths = sorted(t["lengths"])
-        r = {"ids": t["ids"], "confirmed": len(lengths), "mean_length": div(sum(lengths), len(lengths)),
+        r = {"ids": t["ids"], "confirmed": len(lengths), "mean_length": ratio(sum(lengths), len(lengths)),
              "median_length": float(np.median(lengths)) if lengths else None, "boxes": t["boxes"],
-             "confirmed_share": div(t["confirmed_boxes"], t["boxes"]), "overflow": t["overflow"], "velocity_jitter": div(t["jitter_sum"], t["jitter_n"])}
+             "confirmed_share": ratio(t["confirmed_boxes"], t["boxes"]), "overflow": t["overflow"], "velocity_jitter": ratio(t["jitter_sum"], t["jitter_n"])}
         if with_gt:
             r["mot"] = {}
             for key, b in t["mot"].items():
@@ -386,15 +379,14 @@ def summary(sums: dict, with_gt: bool) -> dict:
 
 
 def _table(name: str, r: dict, gt: str | None) -> str:
-    f = lambda v, spec=".3f": "-" if v is None else format(v, spec)      # noqa: E731
-    lines = [f"{name}: {r['ids']} ids, {r['confirmed']} confirmed tracks, length mean {f(r['mean_length'], '.2f')} median {f(r['median_length'], '.1f')} "
-             f"sweeps, {f(r['confirmed_share'])} of {r['boxes']} boxes on a confirmed track, overflow {r['overflow']}, velocity jitter "
-             f"{f(r['velocity_jitter'])} m/s"]
+    lines = [f"{name}: {r['ids']} ids, {r['confirmed']} confirmed tracks, length mean {fmt(r['mean_length'], '.2f')} median {fmt(r['median_length'], '.1f')} "
+             f"sweeps, {fmt(r['confirmed_share'])} of {r['boxes']} boxes on a confirmed track, overflow {r['overflow']}, velocity jitter "
+             f"{fmt(r['velocity_jitter'])} m/s"]
     for key, m in r.get("mot", {}).items():
         line = f"  against {gt} {key:<12} gt {m['gt']:>6} TP {m['tp']} FN {m['fn']}"
         if "fp" in m:
             line += f" FP {m['fp']}"
-        lines.append(line + f" IDSW {m['idsw']} frag {m['frag']} MOTA {f(m['mota'])}")
+        lines.append(line + f" IDSW {m['idsw']} frag {m['frag']} MOTA {fmt(m['mota'])}")
     return "\n".join(lines)
 
 
@@ -421,43 +413,26 @@ def track_label_key(name: str) -> str:
     return f"track_label_{name}"
 
 
-def _write_npz(root: Path, scene_id: str, ts, arrays: dict) -> None:
-    """add ``arrays`` to a sweep's npz with their own dtypes (``save.NpzResultSink`` stores float32 flows only); written aside, then renamed"""
-    path = root / scene_id / f"{ts}.npz"
-    with np.load(path) as z:
-        have = {k: z[k] for k in z.files}
-    have.update(arrays)
-    tmp = path.with_name(path.stem + ".writing.npz")
-    np.savez(tmp, **have)
-    tmp.replace(path)
-
-
 def main(data_dir: str, res_names, gt: str | None = None, json_path: str | None = None, overwrite: bool = False, batch: int = 16,
          min_hits: int = MIN_HITS, sensor_dt: float = SENSOR_DT, point_label_key: str | None = None, motion_min: float = MOTION_MIN, **params) -> dict:
     """The program: for every scene of ``data_dir`` and every name of ``res_names``, the stored ``boxes_<name>`` and ``pose0`` of its
     sweeps in index order through ``BoxTracker.track``, ``batch`` scenes per launch; writes ``<timestamp>/tracks_<name>`` float64 [F, 6]
     (rule F) into the scene files or the npz container, the way ``box_fit`` stores its boxes.  Reads no point data.  Under ``torchrun``
     whole scenes per rank, scene ``i % world``.  Returns what ``--json`` writes: {name: {...}} over every rank."""
-    import json
-    from . import distenv
-    from .dataset import NpzDataset, open_dataset
-    from .eval_box import MAX_BOXES as GT_MAX, _stored_boxes
-    from .save import h5_writer
-    names = [s for s in (res_names.split(",") if isinstance(res_names, str) else list(res_names)) if s]
-    if not names or len(set(names)) != len(names):
-        raise ValueError(f"res_names={res_names!r}: one or more different names")
+    from . import distenv, stored
+    from .dataset import open_dataset
+    from .eval_box import MAX_BOXES as GT_MAX
+    from .sweeps import sharded_scenes
+    names = stored.result_names(res_names, raw_ok=False)
     if gt is not None and not gt:
         raise ValueError("--gt: the name whose boxes are the ground truth (`python -m himo_amd.box_fit --res_names flow --label_key flow_instance_id`)")
     if gt in names:
         raise ValueError(f"--gt {gt} is among --res_names {','.join(names)}: the ground truth is not scored against itself")
     prm = TrackParams(**params)
     sensor_dt = check_sensor_dt(sensor_dt)
-    if isinstance(batch, bool) or not isinstance(batch, (int, np.integer)) or batch < 1:
-        raise ValueError(f"batch={batch!r}: at least 1 scene per launch")
-    if isinstance(min_hits, bool) or not isinstance(min_hits, (int, np.integer)) or min_hits < 1:
-        raise ValueError(f"min_hits={min_hits!r}: at least 1")
-    if not (math.isfinite(motion_min) and motion_min >= 0):
-        raise ValueError(f"motion_min={motion_min}: finite and >= 0")
+    stored.at_least_one("batch", batch, " scene per launch")
+    stored.at_least_one("min_hits", min_hits)
+    stored.check_motion_min(motion_min)
     if point_label_key == "cluster":
         raise ValueError("--point_label_key cluster: clusters made by `box_fit --label_key cluster` are not stored; name the stored per-point key the "
                          "boxes were fitted on")
@@ -468,109 +443,68 @@ def main(data_dir: str, res_names, gt: str | None = None, json_path: str | None 
     sums = {s: new_sums() for s in names}
     with distenv.process_group() as (rank, world):
         ds = open_dataset(root, vis_name="", eval=False, fields=tuple(box_keys + out_keys + extra + ["pose0"]))
-        npz = isinstance(ds, NpzDataset)
-        scenes = {}
-        for i, (sc, _) in enumerate(ds.index):
-            scenes.setdefault(sc, []).append(i)
-        mine = [(sc, items) for n, (sc, items) in enumerate(scenes.items()) if n % world == rank]
-        err = None
-        try:
+        mine = sharded_scenes(ds)
+
+        def loop():
             # the refusals, before anything touches the GPU or a file is written
-            mod = None
-            if not npz:
-                mod, how = h5_writer()
-                if mod is None:
-                    raise RuntimeError(f"writing '{out_keys[0]}' into the scene files of {data_dir} needs an HDF5 library (h5py, or libhdf5 for "
-                                       f"himo_amd.h5c; HIMO_LIBHDF5 names one): {how}")
-            stored = {}
+            sink = stored.KeySink(ds, root, f"writing '{out_keys[0]}' into the scene files of {data_dir}")
+            held = {}
             for sc, items in mine:
                 for i in items:
                     where = "/".join(map(str, ds.index[i]))
-                    have = _stored_boxes(ds, i, box_keys + out_keys + extra + ["pose0"])
+                    have = held[i] = stored.arrays(ds, i, box_keys + out_keys + extra + ["pose0"])
                     for s, k in zip(names + ([gt] if gt else []), box_keys):
                         if k not in have:
                             raise KeyError(f"{k}: {where} holds no boxes of the name '{s}' (`python -m himo_amd.box_fit --data_dir {data_dir} --res_names "
                                            f"{s} --label_key ...` writes them)")
-                        b = have[k]
-                        if b.ndim != 2 or b.shape[1] != 12 or b.dtype != np.float32:
-                            raise ValueError(f"{k}: {where} holds {b.dtype} {b.shape}, not float32 [F][12] box rows")
-                        most = GT_MAX if s == gt else MAX_BOXES
-                        if len(b) > most:
-                            raise ValueError(f"{k}: {where} holds {len(b)} boxes: at most {most} per sweep")
-                    if "pose0" not in have or np.asarray(have["pose0"]).shape != (4, 4):
-                        raise ValueError(f"pose0: {where} holds no [4, 4] pose")
+                        stored.check_box_rows(have[k], k, where, GT_MAX if s == gt else MAX_BOXES)
+                    stored.check_pose(have, where)
                     if point_label_key:
                         if point_label_key not in have:
                             raise KeyError(f"{point_label_key}: {where} holds no such per-point label")
-                        lab = have[point_label_key]
-                        if lab.ndim != 1 or lab.dtype.kind not in "iu":
-                            raise ValueError(f"{point_label_key}: {where} holds {lab.dtype} {lab.shape}, not one integer per point")
+                        stored.check_point_labels(have[point_label_key], point_label_key, where)
                     done = [k for k in out_keys if k in have]
                     if done and not overwrite:
                         raise FileExistsError(f"{where} already holds '{done[0]}': pass --overwrite to replace it")
-                    stored[i] = have
-            if mine:
-                tracker = BoxTracker(sensor_dt=sensor_dt, **params)
-                ev = None
-                if gt:
-                    from .eval_box import BoxEvaluator
-                    ev = BoxEvaluator(min_iou=prm.min_iou)
-                for lo in range(0, len(mine), int(batch)):
-                    chunk = mine[lo:lo + int(batch)]
-                    writes = {}                                     # (scene, timestamp) -> {key: array}
-                    for s in names:
-                        key = boxes_key(s)
-                        dets = [[detections(stored[i][key], stored[i]["pose0"], stored[items[0]]["pose0"]) for i in items] for _, items in chunk]
-                        res = tracker.track(dets)
-                        info = res.scene_info
-                        for n, (sc, items) in enumerate(chunk):
-                            rows = []
-                            for k, i in enumerate(items):
-                                tid, age, state, _ = res.sweep(n, k)
-                                rows.append(stored_rows(tid, age, state, dets[n][k], stored[i]["pose0"], stored[items[0]]["pose0"]))
-                                w = writes.setdefault((sc, ds.index[i][1]), {})
-                                w[tracks_key(s)] = rows[-1]
-                                if point_label_key:
-                                    w[track_label_key(s)] = point_labels(stored[i][point_label_key], stored[i][key], tid)
-                            tally_scene(sums[s], [stored[i][key] for i in items], rows, int(info[n, 0]), int(info[n, 1]), min_hits)
-                            if gt:
-                                g = [stored[i][boxes_key(gt)] for i in items]
-                                m = ev.match(g, [stored[i][key] for i in items])
-                                tally_mot(sums[s], [(g[k], rows[k][:, 0]) + m.sweep(k)[0::2] for k in range(len(items))], motion_min, sensor_dt)
-                    if npz:
-                        for (sc, ts), arrays in writes.items():
-                            _write_npz(root, sc, ts, arrays)
-                    else:
-                        for sc, _ in chunk:
-                            ds.forget(sc)
-                            with mod.File(ds.scene_path(sc), "a") as h:
-                                for (sc2, ts), arrays in writes.items():
-                                    if sc2 != sc:
-                                        continue
-                                    g = h[str(ts)]
-                                    for k, a in arrays.items():
-                                        if k in g:
-                                            del g[k]
-                                        g.create_dataset(k, data=a)
-        except Exception as e:                                    # arrive at the rendezvous anyway, then re-raise
-            err = e
-        finally:
-            if hasattr(ds, "close"):
-                ds.close()
-        distenv.rendezvous(err, "its share of the scenes")
-        if world > 1:
-            import torch.distributed as dist
-            parts = [None] * world
-            dist.all_gather_object(parts, sums)
-            sums = merge(parts)
-        numbers = summary(sums, bool(gt))
-        if rank == 0:
-            print(f"track (box tracking, v1; parity unpinned), min_iou {prm.min_iou:g}, alpha {prm.alpha:g}, beta {prm.beta:g}, max_age {prm.max_age}, "
-                  f"velocity from the {VEL_MODES[prm.vel_mode]}, min_hits {min_hits}:")
-            for s in names:
-                print(_table(s, numbers[s], gt))
-            if json_path:
-                Path(json_path).write_text(json.dumps(numbers, indent=1) + "\n")
+            if not mine:
+                return
+            tracker = BoxTracker(sensor_dt=sensor_dt, **params)
+            ev = None
+            if gt:
+                from .eval_box import BoxEvaluator
+                ev = BoxEvaluator(min_iou=prm.min_iou)
+            for lo in range(0, len(mine), int(batch)):
+                chunk = mine[lo:lo + int(batch)]
+                writes = {}                                         # (scene, timestamp) -> {key: array}
+                for s in names:
+                    key = boxes_key(s)
+                    dets = [[detections(held[i][key], held[i]["pose0"], held[items[0]]["pose0"]) for i in items] for _, items in chunk]
+                    res = tracker.track(dets)
+                    info = res.scene_info
+                    for n, (sc, items) in enumerate(chunk):
+                        rows = []
+                        for k, i in enumerate(items):
+                            tid, age, state, _ = res.sweep(n, k)
+                            rows.append(stored_rows(tid, age, state, dets[n][k], held[i]["pose0"], held[items[0]]["pose0"]))
+                            w = writes.setdefault((sc, ds.index[i][1]), {})
+                            w[tracks_key(s)] = rows[-1]
+                            if point_label_key:
+                                w[track_label_key(s)] = point_labels(held[i][point_label_key], held[i][key], tid)
+                        tally_scene(sums[s], [held[i][key] for i in items], rows, int(info[n, 0]), int(info[n, 1]), min_hits)
+                        if gt:
+                            g = [held[i][boxes_key(gt)] for i in items]
+                            m = ev.match(g, [held[i][key] for i in items])
+                            tally_mot(sums[s], [(g[k], rows[k][:, 0]) + m.sweep(k)[0::2] for k in range(len(items))], motion_min, sensor_dt)
+                for (sc, ts), arrays in writes.items():             # (scene by scene, in chunk order: the first name's loop made the entries)
+                    for k, a in arrays.items():
+                        sink.put(sc, ts, k, a)
+            sink.close()                                            # (on success only: a failed run leaves its last scene as it was)
+
+        distenv.run_shard(loop, "its share of the scenes", closing=(ds,))
+        numbers = summary(distenv.gathered(sums, add_sums), bool(gt))
+        distenv.report(rank, "\n".join([f"track (box tracking, v1; parity unpinned), min_iou {prm.min_iou:g}, alpha {prm.alpha:g}, beta {prm.beta:g}, "
+                                        f"max_age {prm.max_age}, velocity from the {VEL_MODES[prm.vel_mode]}, min_hits {min_hits}:"] +
+                                       [_table(s, numbers[s], gt) for s in names]), numbers, json_path)
     return numbers
 
 

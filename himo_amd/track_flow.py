@@ -67,6 +67,7 @@ from pathlib import Path
 import numpy as np
 
 from .box_fit import MOTION_MIN, SENSOR_DT, boxes_key
+from .stored import fmt, ratio
 from .track import MAX_BOXES, MIN_HITS, check_sensor_dt, scene_transform, tracks_key
 
 NONE, MOVING, STATIC = 0, 1, 2
@@ -271,13 +272,13 @@ class TrackFlow:
         device tensor per sweep ((N, >= 3) float32, (N, 3) float32, (N,) integer), ``E`` one ``ego_transform`` per sweep."""
         import torch
         from . import _lib
-        from .accumulate import _device_rows
+        from .accumulate import device_rows
         P, dev = _lib.ptr, self.device
         sweeps = [(int(n), int(k)) for n, k in sweeps]
         if not (len(sweeps) == len(pc0) == len(flow) == len(label) == len(E)):
             raise ValueError("apply: one pc0, flow, label and E per sweep")
         dev_of = lambda x, dt: (x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))).to(device=dev, dtype=dt)   # noqa: E731
-        pts = [_device_rows(p, dev) for p in pc0]
+        pts = [device_rows(p, dev) for p in pc0]
         fls = [dev_of(f, torch.float32).reshape(-1, 3) for f in flow]
         labs = []
         for j, lab in enumerate(label):
@@ -359,29 +360,18 @@ def tally_plan(sums: dict, plan: TrackFlowPlan, scenes, sensor_dt: float) -> Non
         sums["tracks"] += len(used)
 
 
-def merge(parts: list) -> dict:
-    """the ranks' {name: sums} added up"""
-    total = parts[0]
-    for p in parts[1:]:
-        for name, t in p.items():
-            for k, v in t.items():
-                total[name][k] += v
-    return total
-
-
 def summary(sums: dict) -> dict:
     """the numbers of the tables and of ``--json``: {name: {...}}"""
     return {name: {"confirmed_tracks": t["tracks"], "boxes_moving": t["moving"], "boxes_static": t["static"], "boxes_left_alone": t["none"],
                    "points": t["points"], "points_rewritten": t["points_moving"] + t["points_static"], "points_moving": t["points_moving"],
-                   "points_static": t["points_static"], "mean_shift": t["diff_sum"] / t["diff_n"] if t["diff_n"] else None}
+                   "points_static": t["points_static"], "mean_shift": ratio(t["diff_sum"], t["diff_n"])}
             for name, t in sums.items()}
 
 
 def _table(name: str, r: dict) -> str:
-    shift = "-" if r["mean_shift"] is None else format(r["mean_shift"], ".4f")
     return (f"{name} -> {track_flow_key(name)}: {r['confirmed_tracks']} confirmed tracks used, boxes MOVING {r['boxes_moving']} STATIC {r['boxes_static']} "
             f"left alone {r['boxes_left_alone']}, {r['points_rewritten']} of {r['points']} points rewritten ({r['points_moving']} moving, "
-            f"{r['points_static']} static), mean |d_s - d_b| {shift} m")
+            f"{r['points_static']} static), mean |d_s - d_b| {fmt(r['mean_shift'], '.4f')} m")
 
 
 # ---- the program ------------------------------------------------------------------------------------------------------------------------
@@ -392,15 +382,11 @@ def main(data_dir: str, res_names, label_key: str, mode: str = "shift", half: in
     ``label_key`` through ``TrackFlow.apply`` (``sweeps_per_launch`` sweeps per launch); writes ``<timestamp>/<name>_track`` float32
     (N, 3) through ``save``'s sinks (h5 scene files or the npz container).  Under ``torchrun`` whole scenes per rank, scene ``i %
     world``.  Returns what ``--json`` writes: {name: {...}} over every rank."""
-    import json
-    from . import distenv
+    from . import distenv, stored
     from .dataset import NpzDataset, open_dataset
-    from .eval_box import _stored_boxes
-    from .rigid_refine import _present
     from .save import H5ResultSink, NpzResultSink
-    names = [s for s in (res_names.split(",") if isinstance(res_names, str) else list(res_names)) if s]
-    if not names or len(set(names)) != len(names):
-        raise ValueError(f"res_names={res_names!r}: one or more different names")
+    from .sweeps import sharded_scenes
+    names = stored.result_names(res_names, raw_ok=False)
     if "raw" in names:
         raise ValueError("res_names: 'raw' is the zero-motion key, not a stored flow; name the results whose boxes were tracked")
     if mode not in MODES:
@@ -411,28 +397,24 @@ def main(data_dir: str, res_names, label_key: str, mode: str = "shift", half: in
         raise ValueError("--label_key cluster: clusters made by `box_fit --label_key cluster` are not stored; name the stored per-point key the "
                          "boxes were fitted on")
     prm = TrackFlowParams(sensor_dt=sensor_dt, motion_min=motion_min, half=half, min_len=min_len, mode=MODES.index(mode))
-    for name, v in (("batch", batch), ("sweeps_per_launch", sweeps_per_launch)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
-            raise ValueError(f"{name}={v!r}: at least 1")
+    stored.at_least_one("batch", batch)
+    stored.at_least_one("sweeps_per_launch", sweeps_per_launch)
     root = Path(data_dir)
     box_keys, trk_keys, out_keys = [boxes_key(s) for s in names], [tracks_key(s) for s in names], [track_flow_key(s) for s in names]
     sums = {s: new_sums() for s in names}
     with distenv.process_group() as (rank, world):
         ds = open_dataset(root, vis_name=names, eval=False, fields=tuple(["pc0", "pose0", "pose1", label_key] + names))
         npz = isinstance(ds, NpzDataset)
-        scenes = {}
-        for i, (sc, _) in enumerate(ds.index):
-            scenes.setdefault(sc, []).append(i)
-        mine = [(sc, items) for n, (sc, items) in enumerate(scenes.items()) if n % world == rank]
-        err, sinks = None, {}
-        try:
+        mine = sharded_scenes(ds)
+
+        def loop():
             # the refusals, before anything touches the GPU or a file is written
-            stored = {}
+            held = {}
             for sc, items in mine:
                 for i in items:
                     where = "/".join(map(str, ds.index[i]))
-                    have = _stored_boxes(ds, i, box_keys + trk_keys + ["pose0"])
-                    present = _present(ds, i, names + out_keys + [label_key])
+                    have = held[i] = stored.arrays(ds, i, box_keys + trk_keys + ["pose0"])
+                    present = stored.present(ds, i, names + out_keys + [label_key])
                     for s, bk, tk in zip(names, box_keys, trk_keys):
                         if bk not in have:
                             raise KeyError(f"{bk}: {where} holds no boxes of the name '{s}' (`python -m himo_amd.box_fit --data_dir {data_dir} "
@@ -441,82 +423,55 @@ def main(data_dir: str, res_names, label_key: str, mode: str = "shift", half: in
                             raise KeyError(f"{tk}: {where} holds no tracks of the name '{s}' (`python -m himo_amd.track --data_dir {data_dir} "
                                            f"--res_names {s}` writes them)")
                         b, t = have[bk], have[tk]
-                        if b.ndim != 2 or b.shape[1] != 12 or b.dtype != np.float32:
-                            raise ValueError(f"{bk}: {where} holds {b.dtype} {b.shape}, not float32 [F][12] box rows")
-                        if t.ndim != 2 or t.shape[1] != 6 or t.dtype != np.float64:
-                            raise ValueError(f"{tk}: {where} holds {t.dtype} {t.shape}, not float64 [F][6] track rows")
-                        if len(t) != len(b):
-                            raise ValueError(f"{tk}: {where} holds {len(t)} rows for the {len(b)} boxes of {bk}: stale tracks (run `python -m "
-                                             f"himo_amd.track --res_names {s} --overwrite` after box_fit)")
-                        if len(b) > MAX_BOXES:
-                            raise ValueError(f"{bk}: {where} holds {len(b)} boxes: at most {MAX_BOXES} per sweep")
+                        stored.check_box_rows(b, bk, where, None)   # (the count is refused after stale tracks, below)
+                        stored.check_track_rows(t, b, tk, bk, where, f"python -m himo_amd.track --res_names {s} --overwrite")
+                        stored.check_box_rows(b, bk, where, MAX_BOXES)
                         if s not in present:
                             raise KeyError(f"{s}: {where} holds no result of that name")
-                    if "pose0" not in have or np.asarray(have["pose0"]).shape != (4, 4):
-                        raise ValueError(f"pose0: {where} holds no [4, 4] pose")
+                    stored.check_pose(have, where)
                     if label_key not in present:
                         raise KeyError(f"{label_key}: {where} holds no such per-point label")
                     done = [k for k in out_keys if k in present]
                     if done and not overwrite:
                         raise FileExistsError(f"{where} already holds '{done[0]}': pass --overwrite to replace it")
-                    stored[i] = have
-            if mine:
-                engine = TrackFlow(**{k: getattr(prm, k) for k in ("sensor_dt", "motion_min", "half", "min_len", "mode")})
-                sinks = {s: NpzResultSink(root, track_flow_key(s)) if npz else H5ResultSink(root, track_flow_key(s), before_write=ds.forget)
-                         for s in names}
-                for lo in range(0, len(mine), int(batch)):
-                    chunk = mine[lo:lo + int(batch)]
-                    plans = {}
-                    for s in names:
-                        prep = [[prepare(stored[i][boxes_key(s)], stored[i][tracks_key(s)], stored[i]["pose0"], stored[items[0]]["pose0"])
-                                 for i in items] for _, items in chunk]
-                        plans[s] = engine.plan(prep)
-                        tally_plan(sums[s], plans[s], prep, prm.sensor_dt)
-                    for n, (sc, items) in enumerate(chunk):
-                        for g in range(0, len(items), int(sweeps_per_launch)):
-                            part = items[g:g + int(sweeps_per_launch)]
-                            frames = [ds[i] for i in part]
-                            for f in frames:
-                                lab = np.asarray(f[label_key])
-                                if lab.ndim != 1 or lab.dtype.kind not in "iu" or len(lab) != len(f["pc0"]):
-                                    raise ValueError(f"{label_key}: {f['scene_id']}/{f['timestamp']} holds {lab.dtype} {lab.shape}, not one integer "
-                                                     f"per point of its {len(f['pc0'])} points")
-                            Es = [ego_transform(f["pose0"], f["pose1"]) for f in frames]
-                            for s in names:
-                                res = engine.apply(plans[s], [(n, g + j) for j in range(len(part))], [np.asarray(f["pc0"]) for f in frames],
-                                                   [np.asarray(f[s]) for f in frames], [np.asarray(f[label_key]) for f in frames], Es)
-                                host, counts = res.flow.cpu().numpy(), res.counts
-                                for j, (i, f) in enumerate(zip(part, frames)):
-                                    sinks[s](i, f, host[int(res.pt_off[j]):int(res.pt_off[j + 1])])
-                                sums[s]["points"] += int(res.pt_off[-1])
-                                sums[s]["points_moving"] += int(counts[:, 0].sum())
-                                sums[s]["points_static"] += int(counts[:, 1].sum())
-        except Exception as e:                                    # arrive at the rendezvous anyway, then re-raise
-            err = e
-        finally:
-            for sink in sinks.values():
+            if not mine:
+                return
+            engine = TrackFlow(**{k: getattr(prm, k) for k in ("sensor_dt", "motion_min", "half", "min_len", "mode")})
+            sinks = {s: NpzResultSink(root, track_flow_key(s)) if npz else H5ResultSink(root, track_flow_key(s), before_write=ds.forget)
+                     for s in names}
+            for lo in range(0, len(mine), int(batch)):
+                chunk = mine[lo:lo + int(batch)]
+                plans = {}
+                for s in names:
+                    prep = [[prepare(held[i][boxes_key(s)], held[i][tracks_key(s)], held[i]["pose0"], held[items[0]]["pose0"])
+                             for i in items] for _, items in chunk]
+                    plans[s] = engine.plan(prep)
+                    tally_plan(sums[s], plans[s], prep, prm.sensor_dt)
+                for n, (sc, items) in enumerate(chunk):
+                    for g in range(0, len(items), int(sweeps_per_launch)):
+                        part = items[g:g + int(sweeps_per_launch)]
+                        frames = [ds[i] for i in part]
+                        for f in frames:
+                            stored.check_point_labels(np.asarray(f[label_key]), label_key, f"{f['scene_id']}/{f['timestamp']}", rows=len(f["pc0"]))
+                        Es = [ego_transform(f["pose0"], f["pose1"]) for f in frames]
+                        for s in names:
+                            res = engine.apply(plans[s], [(n, g + j) for j in range(len(part))], [np.asarray(f["pc0"]) for f in frames],
+                                               [np.asarray(f[s]) for f in frames], [np.asarray(f[label_key]) for f in frames], Es)
+                            host, counts = res.flow.cpu().numpy(), res.counts
+                            for j, (i, f) in enumerate(zip(part, frames)):
+                                sinks[s](i, f, host[int(res.pt_off[j]):int(res.pt_off[j + 1])])
+                            sums[s]["points"] += int(res.pt_off[-1])
+                            sums[s]["points_moving"] += int(counts[:, 0].sum())
+                            sums[s]["points_static"] += int(counts[:, 1].sum())
+            for sink in sinks.values():                             # (on success only: a failed run leaves its last scene as it was)
                 if hasattr(sink, "close"):
-                    try:
-                        if err is None:
-                            sink.close()
-                    except Exception as e:
-                        err = err or e
-            if hasattr(ds, "close"):
-                ds.close()
-        distenv.rendezvous(err, "its share of the scenes")
-        if world > 1:
-            import torch.distributed as dist
-            parts = [None] * world
-            dist.all_gather_object(parts, sums)
-            sums = merge(parts)
-        numbers = summary(sums)
-        if rank == 0:
-            print(f"track_flow (track flow, v1; parity unpinned), labels '{label_key}', mode {mode}, half {prm.half}, min_len {prm.min_len}, "
-                  f"motion_min {prm.motion_min:g}, sensor_dt {prm.sensor_dt:g}:")
-            for s in names:
-                print(_table(s, numbers[s]))
-            if json_path:
-                Path(json_path).write_text(json.dumps(numbers, indent=1) + "\n")
+                    sink.close()
+
+        distenv.run_shard(loop, "its share of the scenes", closing=(ds,))
+        numbers = summary(distenv.gathered(sums))
+        distenv.report(rank, "\n".join([f"track_flow (track flow, v1; parity unpinned), labels '{label_key}', mode {mode}, half {prm.half}, "
+                                        f"min_len {prm.min_len}, motion_min {prm.motion_min:g}, sensor_dt {prm.sensor_dt:g}:"] +
+                                       [_table(s, numbers[s]) for s in names]), numbers, json_path)
     return numbers
 
 

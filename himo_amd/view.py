@@ -561,8 +561,8 @@ def box_segments(rows, sensor_dt: float = 0.1, motion_min: float = 0.05, arrow_s
 def _stored(ds, i, keys) -> dict:
     """the arrays ``keys`` of item ``i`` that exist (and its ``scene_id``), read without the sweep itself where the dataset can"""
     if hasattr(ds, "index"):
-        from .eval_box import _stored_boxes
-        return {**_stored_boxes(ds, i, keys), "scene_id": ds.index[i][0], "timestamp": ds.index[i][1]}
+        from .stored import arrays
+        return {**arrays(ds, i, keys), "scene_id": ds.index[i][0], "timestamp": ds.index[i][1]}
     d = ds[i]
     return {**{k: np.asarray(d[k]) for k in keys if k in d}, "scene_id": d.get("scene_id"), "timestamp": d.get("timestamp")}
 

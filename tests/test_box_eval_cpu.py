@@ -228,7 +228,8 @@ def test_host_glue_is_the_restatements_and_ranks_merge():
     parts = [{"x": eval_box.new_sums()}, {"x": eval_box.new_sums()}]
     for n, s in enumerate(sweeps):
         eval_box.tally(parts[n % 2]["x"], *s)
-    same_numbers(eval_box.summary(eval_box.merge(parts))["x"], got)
+    from himo_amd import distenv
+    same_numbers(eval_box.summary(distenv.add_sums(*parts))["x"], got)
     # rule G: given pairs, no TP / FP / FN
     labelled = eval_box.summary(sums, "label")["x"]
     assert "at" not in labelled["buckets"]["all"] and labelled["buckets"]["all"]["mean_iou"] == a["mean_iou"]

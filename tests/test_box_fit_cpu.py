@@ -343,17 +343,17 @@ def test_the_against_numbers():
     b = np.zeros((2, 12), np.float32)
     a[:, 3], a[:, 4], a[:, 6], a[:, 0] = [7.0, 5.0, 4.0], [2.0, 2.0, 2.0], [0.1, math.pi / 2, 0.0], [0.0, 3.0, 0.0]
     b[:, 3], b[:, 4], b[:, 6], b[:, 1] = [4.5, 4.0], [1.9, 2.5], [0.1 + math.radians(100), 0.0], [4.0, 0.0]
-    acc = box_fit._new_against()
+    acc = box_fit.new_against()
     box_fit.tally_against(acc, a, np.array([True, True, False]), np.array([5, 9, 11]), b, np.array([True, False]), np.array([5, 11]))
     assert acc["all"]["pairs"] == 2 and acc["moving"]["pairs"] == 1
     assert abs(acc["all"]["sum_dl"] - 2.5) < 1e-6 and abs(acc["all"]["sum_dw"] - 0.6) < 1e-6 and abs(acc["all"]["sum_centre"] - 4.0) < 1e-6
     assert abs(acc["all"]["sum_yaw_deg"] - 10.0) < 1e-4 and abs(acc["moving"]["sum_yaw_deg"] - 10.0) < 1e-4    # 100 degrees folds to 10
-    totals = {"x": box_fit._new_totals()}
+    totals = {"x": box_fit.new_totals()}
     box_fit.tally(totals["x"], a, np.array([True, True, False]))
     out = box_fit.summary(totals, {"x": acc}, "y")
     assert out["x"]["boxes"] == 3 and out["x"]["moving"] == 2 and out["x"]["mean_l_moving"] == 6.0 and out["x"]["against"]["name"] == "y"
     assert abs(out["x"]["against"]["all"]["mean_dl"] - 1.25) < 1e-6 and out["x"]["against"]["moving"]["pairs"] == 1
-    assert box_fit.summary({"x": box_fit._new_totals()}, None, None)["x"]["mean_l_moving"] is None
+    assert box_fit.summary({"x": box_fit.new_totals()}, None, None)["x"]["mean_l_moving"] is None
 
 
 def test_without_a_gpu_it_raises(monkeypatch):

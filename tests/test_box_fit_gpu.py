@@ -343,8 +343,8 @@ def test_program_writes_boxes_and_its_numbers_are_the_restatements(gpu, tmp_path
     assert "cluster boxes, v1; parity unpinned" in capsys.readouterr().out
     # the same numbers from the restatement, on the points and motions the package's own earlier stages give
     engine = CompDisEngine()
-    totals = {s: box_fit._new_totals() for s in ("raw", "flow")}
-    versus = {s: box_fit._new_against() for s in ("raw", "flow")}
+    totals = {s: box_fit.new_totals() for s in ("raw", "flow")}
+    versus = {s: box_fit.new_against() for s in ("raw", "flow")}
     for f in frames:
         pc0 = torch.from_numpy(f["pc0"]).to(gpu)
         comp = engine.run_frame(pc0, torch.from_numpy(f["flow"]).to(gpu), torch.from_numpy(f["lidar_dt"]).to(gpu), f["pose0"], f["pose1"],

@@ -195,7 +195,7 @@ def test_track_tables_on_hand_written_arrays():
     track.tally_scene(sums, boxes, tracks, 3, 1, min_hits=3)
     assert (sums["ids"], sums["overflow"], sums["boxes"], sums["confirmed_boxes"], sums["lengths"], sums["jitter_n"]) == (3, 1, 8, 4, [4], 2)
     assert sums["jitter_sum"] == 5.0                                # hypot(3 - 0, 0 - 4) + 0
-    two = track.merge([{"x": sums}, {"x": {**track.new_sums(), "ids": 2, "lengths": [3, 9], "boxes": 2}}])
+    two = track.add_sums({"x": sums}, {"x": {**track.new_sums(), "ids": 2, "lengths": [3, 9], "boxes": 2}})
     out = track.summary(two, False)["x"]
     assert out == {"ids": 5, "confirmed": 3, "mean_length": 16 / 3, "median_length": 4.0, "boxes": 10, "confirmed_share": 0.4, "overflow": 1,
                    "velocity_jitter": 2.5}

@@ -228,9 +228,10 @@ def test_tally_summary_and_the_merge_of_ranks():
     assert numbers["x"]["against"]["buckets"]["all"] == {"pairs": 1, "ratio": 0.5} and numbers["x"]["against"]["buckets"]["dt:10-30ms"]["ratio"] is None
     assert numbers["x"]["states"] == {"scored": 2, "too few": 1, "one sensor": 1, "too large": 0}
     assert "x: clusters scored 2" in ex._table(numbers)
-    totals, versus = ex._merge([({"x": copy.deepcopy(t)}, {"x": copy.deepcopy(a)}), ({"x": copy.deepcopy(t)}, {"x": copy.deepcopy(a)})])
+    from himo_amd.distenv import add_sums
+    totals, versus = add_sums([{"x": copy.deepcopy(t)}, {"x": copy.deepcopy(a)}], [{"x": copy.deepcopy(t)}, {"x": copy.deepcopy(a)}])
     assert totals["x"]["states"] == [4, 2, 2, 0] and totals["x"]["buckets"]["all"]["sum_qc"] == 26 * U and versus["x"]["all"]["pairs"] == 2
-    assert ex._merge([({"x": copy.deepcopy(t)}, None), ({"x": copy.deepcopy(t)}, None)])[0]["x"]["buckets"]["all"]["clusters"] == 4
+    assert add_sums([{"x": copy.deepcopy(t)}, None], [{"x": copy.deepcopy(t)}, None])[0]["x"]["buckets"]["all"]["clusters"] == 4
 
 
 # ---- binding -----------------------------------------------------------------------------------------------------------------------------
