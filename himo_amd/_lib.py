@@ -71,6 +71,12 @@ SIGNATURES = {
                               c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "himo_icp_apply": (c_int, [c_int64, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p,
                                c_void_p]),
+    "himo_odom_workspace_bytes": (c_size_t, [c_int64, c_void_p]),
+    "himo_odom_init": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "himo_odom_map": (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "himo_odom_step": (c_int, [c_int64, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                               c_void_p]),
+    "himo_odom_register": (c_int, [c_int64, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "himo_rigid_refine_workspace_bytes": (c_size_t, [c_int64, c_int, c_int, c_int]),
     "himo_rigid_refine": (c_int, [c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

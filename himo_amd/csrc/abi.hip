@@ -85,6 +85,8 @@ extern "C" size_t himo_abi_sizeof(const char* struct_name) {
     if (!strcmp(struct_name, "himo_instance_record")) return sizeof(himo_instance_record);
     if (!strcmp(struct_name, "himo_ground_params")) return sizeof(himo_ground_params);
     if (!strcmp(struct_name, "himo_icp_params")) return sizeof(himo_icp_params);
+    if (!strcmp(struct_name, "himo_odom_params")) return sizeof(himo_odom_params);
+    if (!strcmp(struct_name, "himo_odom_state")) return sizeof(himo_odom_state);
     if (!strcmp(struct_name, "himo_rigid_params")) return sizeof(himo_rigid_params);
     if (!strcmp(struct_name, "himo_boxfit_params")) return sizeof(himo_boxfit_params);
     if (!strcmp(struct_name, "himo_xsensor_params")) return sizeof(himo_xsensor_params);

@@ -41,13 +41,31 @@ class ListDataset:
         return self.frames[i]
 
 
-class NpzDataset:
-    """``<dir>/<scene_id>/<timestamp>.npz`` + ``index_total.pkl`` (same index format as the reference)."""
+POSE_KEY = "pose"            # the recorded pose of a sweep: dataset ``pose`` of its group (``pose0`` / ``pose1`` of an npz sweep)
 
-    def __init__(self, directory, vis_name: str = "", eval: bool = False):  # noqa: A002
+
+def resolve_pose_key(pose_key: str | None) -> str:
+    """``pose_key`` of the loaders: the name given, else the environment variable ``HIMO_POSE_KEY`` when set, else ``"pose"``"""
+    key = pose_key if pose_key is not None else os.environ.get("HIMO_POSE_KEY") or POSE_KEY
+    if not isinstance(key, str) or not key:
+        raise ValueError(f"pose_key={pose_key!r}: the name of a stored [4, 4] pose")
+    return key
+
+
+def _no_pose(key: str, where: str) -> KeyError:
+    return KeyError(f"{key}: {where} holds no such pose (`python -m himo_amd.odometry --data_dir ... --out_key {key}` writes estimated poses)")
+
+
+class NpzDataset:
+    """``<dir>/<scene_id>/<timestamp>.npz`` + ``index_total.pkl`` (same index format as the reference).
+    ``pose_key`` (``resolve_pose_key``): with a name other than ``"pose"``, ``pose0`` is served from ``<pose_key>`` of the sweep's npz
+    and ``pose1`` from ``<pose_key>_next`` (an npz sweep carries its own successor's pose); a sweep without them is a ``KeyError``."""
+
+    def __init__(self, directory, vis_name: str = "", eval: bool = False, pose_key: str | None = None):  # noqa: A002
         self.directory = Path(directory)
         self.index = load_index(self.directory, eval=eval)
         self.vis_name = vis_name
+        self.pose_key = resolve_pose_key(pose_key)
 
     def __len__(self):
         return len(self.index)
@@ -56,6 +74,11 @@ class NpzDataset:
         scene_id, ts = self.index[i]
         with np.load(self.directory / scene_id / f"{ts}.npz") as z:
             d = {k: z[k] for k in z.files}
+        if self.pose_key != POSE_KEY:
+            for frame_key, name in (("pose0", self.pose_key), ("pose1", self.pose_key + "_next")):
+                if name not in d:
+                    raise _no_pose(name, f"{scene_id}/{ts}")
+                d[frame_key] = d[name]
         d["scene_id"], d["timestamp"] = scene_id, int(ts)
         return d
 
@@ -216,13 +239,17 @@ class HDF5Dataset:
     labels of both sweeps of a pair: ``seflow.fit --ssl_label <name>``).
     ``allow_dropped_eval`` (default: env ``HIMO_ALLOW_DROPPED_EVAL``, else False): see the KeyError below.
     ``need_next=False``: for consumers that read a sweep alone (no ``pose1`` / ``pc1``): every index entry stays, the last sweep
-    of a scene included, and asking such an item for a successor's key is a KeyError."""
+    of a scene included, and asking such an item for a successor's key is a KeyError.
+    ``pose_key`` (``resolve_pose_key``: the name, else env ``HIMO_POSE_KEY``, else ``"pose"``): the dataset of a sweep's group that
+    ``pose0`` is read from, and of its successor's group for ``pose1`` (``pose_odom`` of ``python -m himo_amd.odometry``); a sweep
+    without it is a KeyError that names that program.  With ``"pose"`` every byte read is what it always was."""
 
     carries_next = True        # every item holds its successor's ``pc1`` / ``pose1``: a walk never reads item i + 1 for them
 
     def __init__(self, directory, vis_name="", eval: bool = False, n_frames: int = 2, opener=None,  # noqa: A002
                  allow_dropped_eval: bool | None = None, fields=None, zero_copy: bool = False, keep_open: int = 8,
-                 need_next: bool = True):
+                 need_next: bool = True, pose_key: str | None = None):
+        self.pose_key = resolve_pose_key(pose_key)
         self._files = _OpenFiles(opener if opener is not None else _open_h5, keep=keep_open)
         # reader PROCESSES (feeder.ReaderPool) may inherit this object through fork(): h5lite holds a read-only file mapping and
         # nothing else; libhdf5's global state under h5py does not survive a fork with files open
@@ -308,6 +335,11 @@ class HDF5Dataset:
     def __getitem__(self, i):
         return self.read(i)
 
+    def _pose(self, g, scene_id, ts):
+        if self.pose_key != POSE_KEY and self.pose_key not in g:
+            raise _no_pose(self.pose_key, f"{scene_id}/{ts}")
+        return np.asarray(g[self.pose_key][:])
+
     def read(self, i, fields=None):
         """item ``i`` restricted to ``fields`` (None: the dataset's own ``fields``) -- a caller that needs only part of a frame it
         has no other use for (the training loop's history sweep: ``pc0`` and ``pose0``) does not touch the rest"""
@@ -320,7 +352,7 @@ class HDF5Dataset:
         if need("pc0"):
             d["pc0"] = self._array(g["lidar"])
         if need("pose0"):
-            d["pose0"] = np.asarray(g["pose"][:])
+            d["pose0"] = self._pose(g, scene_id, ts)
         if need("lidar_dt"):
             d["lidar_dt"] = self._array(g["lidar_dt"]) if "lidar_dt" in g else np.zeros(g["lidar"].shape[0], np.float32)
         if need("gm0") and "ground_mask" in g:
@@ -357,7 +389,7 @@ class HDF5Dataset:
             return d
         nxt = f[self._next[(scene_id, ts)]]
         if need("pose1"):
-            d["pose1"] = np.asarray(nxt["pose"][:])
+            d["pose1"] = self._pose(nxt, scene_id, self._next[(scene_id, ts)])
         if need("pc1"):
             d["pc1"] = self._array(nxt["lidar"])
         if need("gm1") and "ground_mask" in nxt:               # the label generator needs both sweeps' ground masks (seflow/ssl_label.py)
@@ -370,12 +402,14 @@ class HDF5Dataset:
         return d
 
 
-def open_dataset(directory, vis_name="", eval: bool = False, allow_dropped_eval: bool | None = None, **h5_options):  # noqa: A002
+def open_dataset(directory, vis_name="", eval: bool = False, allow_dropped_eval: bool | None = None, pose_key: str | None = None,  # noqa: A002
+                 **h5_options):
     """The frame source behind ``HDF5Dataset(dir, vis_name=<res>, eval=True)`` at save_zip.py:111 / eval.py:279: the h5
     scene files when the directory holds them, this package's npz container (``NpzDataset.write``) when it holds that.
     ``allow_dropped_eval`` only concerns h5 scene files: an npz frame carries its own ``pose1`` / ``pc1``, so no entry of
-    an npz index can lack a successor."""
+    an npz index can lack a successor.  ``pose_key``: the stored pose both loaders serve ``pose0`` / ``pose1`` from
+    (``resolve_pose_key``: None = env ``HIMO_POSE_KEY`` when set, else ``"pose"``)."""
     directory = Path(directory)
     if any(directory.glob("*/*.npz")) and not any(directory.glob("*.h5")):
-        return NpzDataset(directory, vis_name=vis_name, eval=eval)
-    return HDF5Dataset(directory, vis_name=vis_name, eval=eval, allow_dropped_eval=allow_dropped_eval, **h5_options)
+        return NpzDataset(directory, vis_name=vis_name, eval=eval, pose_key=pose_key)
+    return HDF5Dataset(directory, vis_name=vis_name, eval=eval, allow_dropped_eval=allow_dropped_eval, pose_key=pose_key, **h5_options)

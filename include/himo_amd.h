@@ -619,6 +619,67 @@ int himo_icp_apply(int64_t n, const float* d_pts, int pitch, const int32_t* d_la
                    const int32_t* d_status, int mode, const float* d_base, int base_pitch, float* d_out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Sweep odometry (`python -m himo_amd.odometry`, stored key `pose_odom`): whole-sweep, 6-DoF scan-to-map ICP.  The reference has no
+ * such stage: this one follows the build's own written rule, "sweep odometry, v1" (the module docstring of himo_amd/odometry.py is
+ * normative): PARITY UNPINNED.
+ *
+ * d_src float[n][pitch] (pitch 3 or 4: x, y, z first) the source rows; d_map float[n_map][3] the map rows, finite (the centroids of
+ * himo_accum_emit in ascending key order).  The state is ONE himo_odom_state in device memory: T, the first three rows of the
+ * row-major transform source -> map frame, the status and what the last pass left.
+ *   himo_odom_init      writes a fresh RUNNING state: T = h_transform (12 doubles on the HOST, NULL = the identity; passed by value, no
+ *                       copy is enqueued); with d_vote (the double[5] transform himo_icp_vote wrote for ONE cluster) the translation x, y
+ *                       is taken from d_vote[2], d_vote[3] on the device.
+ *   himo_odom_map       bins the map on the BEV cell grid of the parameters (cell edge max_dist, gw x gh cells from (x0, y0); rows
+ *                       outside go to the border cells) into the workspace: once per sweep.
+ *   himo_odom_step      one iteration of rule 3 on the binned map: m = float32(T p) in float64, the nearest map row among the 3 x 3
+ *                       cells around m's cell (float32 d2, ties keep the lowest row), inliers d2 <= max_dist^2, Geman-McClure weights,
+ *                       the 28 float64 sums in a fixed reduction shape (no floating-point atomics), unpivoted Cholesky, Cayley update,
+ *                       status.  d_nn_idx int32[n] / d_nn_d2 float[n], each or NULL: the neighbour row and d2 of every source row
+ *                       (-1 and +inf without a candidate or for a non-finite m).  A state that is not RUNNING: nothing is written,
+ *                       the per-row outputs included.  The workspace must hold what himo_odom_map left for the same map.
+ *   himo_odom_register  himo_odom_map, then `iters` steps, enqueued with no host wait; nothing allocates or synchronises.
+ * n == 0 and n_map == 0 are defined outcomes (the first step ends FAILED_PAIRS), not errors; d_src / d_map may then be NULL.
+ * Refuse (HIMO_ERR_INVALID_ARGUMENT, nothing launched, nothing written): a pitch other than 3 or 4, a negative count, NULL or
+ * misaligned (4 bytes; the state 8) where data is required, parameters that are NULL, not finite, max_dist / gm_scale / eps_t2 /
+ * eps_r2 not > 0, gw / gh / min_pairs < 1 or iters outside 1 .. 1024, a non-finite h_transform.  gw * gh > 2^20 or a count above
+ * 2^31 - 1: HIMO_ERR_UNSUPPORTED.  A short, NULL or misaligned (16 bytes) workspace: HIMO_ERR_WORKSPACE (himo_odom_workspace_bytes
+ * returns 0 for what it refuses).  Asynchronous on `stream`; the same inputs give the same bytes on every run. */
+typedef struct himo_odom_params {
+    float x0, y0;          /* minimum corner of the BEV cell grid */
+    float max_dist;        /* cell edge; inlier iff d2 <= max_dist^2 (one float32 product) */
+    int32_t gw, gh;        /* cells in x and in y */
+    float gm_scale;        /* s of the Geman-McClure weight (s / (s + r.r))^2 */
+    int32_t min_pairs;     /* fewer inliers: FAILED_PAIRS */
+    int32_t iters;         /* steps of himo_odom_register */
+    double eps_t2, eps_r2; /* CONVERGED iff |t_xi|^2 < eps_t2 and |omega|^2 < eps_r2 */
+} himo_odom_params;
+
+typedef struct himo_odom_state {
+    double T[12];          /* rows of the 3 x 4 transform */
+    double cost;           /* sum w r.r of the last pass */
+    double xi[6];          /* t_xi, omega of the last solved step */
+    double sums[28];       /* the last pass: the 21 upper entries of H (row-major), the 6 of g, the cost */
+    int32_t status;        /* HIMO_ODOM_* */
+    int32_t iters;         /* passes run on this state */
+    int32_t pairs;         /* inliers of the last pass */
+    int32_t reserved;
+} himo_odom_state;
+
+#define HIMO_ODOM_RUNNING 0
+#define HIMO_ODOM_CONVERGED 1
+#define HIMO_ODOM_FAILED_PAIRS 2
+#define HIMO_ODOM_FAILED_SOLVE 3
+
+size_t himo_odom_workspace_bytes(int64_t n_map, const himo_odom_params* params);
+int himo_odom_init(const double* h_transform, const double* d_vote, himo_odom_state* d_state, void* stream);
+int himo_odom_map(int64_t n_map, const float* d_map, const himo_odom_params* params, void* d_workspace, size_t workspace_bytes,
+                  void* stream);
+int himo_odom_step(int64_t n, const float* d_src, int pitch, int64_t n_map, const float* d_map, const himo_odom_params* params,
+                   himo_odom_state* d_state, int32_t* d_nn_idx, float* d_nn_d2, void* d_workspace, size_t workspace_bytes, void* stream);
+int himo_odom_register(int64_t n, const float* d_src, int pitch, int64_t n_map, const float* d_map, const himo_odom_params* params,
+                       himo_odom_state* d_state, void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Cluster-rigid flow refinement (`python -m himo_amd.rigid_refine`, result key `<res_name>_rigid`): a stored flow is projected
  * onto at most `models` rigid motions (yaw + 3-D translation) per cluster of the non-ground points of pc0; a motion that moves no
  * claimed point by static_disp becomes the identity, i.e. the ego-motion flow.  The reference has no such stage: this one follows
