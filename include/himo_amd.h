@@ -1373,7 +1373,11 @@ int himo_transpose(const float* d_w, int rows, int cols, float* d_wt, void* stre
 int himo_adam_step(int64_t n, float* d_param, const float* d_grad, float* d_m, float* d_v, float lr, float beta1,
                    float beta2, float eps, int step, void* stream);
 /* loss = mean_i [d_a_i <= trunc^2] d_a_i + mean_j [d_b_j <= trunc^2] d_b_j on squared NN distances (from himo_nn_grid),
- * and d loss / d moved (correspondences constant) */
+ * and d loss / d moved (correspondences constant).  The distances and indices are used as given: a term is kept iff d <= t2 with
+ * t2 = trunc_dist * trunc_dist in float32 (NaN and +inf distances are dropped, and the index of a dropped term is not read); the
+ * pc1 -> moved half is summed in 2^-40 fixed point, so the result does not depend on the order.  trunc_dist is only ever squared: a
+ * negative one acts as its magnitude, a NaN one drops every term (himo_nsfp_objective refuses both).  n0 == 0 or n1 == 0: loss 0 and
+ * a zero gradient; no correspondence is read and none need be passed.  A short workspace: HIMO_ERR_WORKSPACE. */
 size_t himo_chamfer_trunc_workspace_bytes(int n0, int n1);
 int himo_chamfer_trunc(int n0, int n1, const float* d_moved, const float* d_pc1, const float* d_dist_a,
                        const int32_t* d_idx_a, const float* d_dist_b, const int32_t* d_idx_b, float trunc_dist,
@@ -1577,7 +1581,11 @@ int himo_mlp_forward_fused(int64_t n, const float* d_x0, int n_hidden, const flo
 int himo_mlp_backward_fused(int64_t n, const float* d_dout, int n_hidden, const void* const* h_wT_hidden_packed,
                             const float* d_w_last, float* const* h_H, float* const* h_dZ, void* stream);
 /* the same, also yielding the hidden layers' bias gradients h_db[k] [128] (column sums of dZ_k, taken while dZ_k passes through the kernel:
- * one reduction launch for all layers instead of a column-sum pass per layer); the padding rows of d_dout must be zero */
+ * one reduction launch for all layers instead of a column-sum pass per layer); the padding rows of d_dout must be zero.
+ * himo_mlp_bias_workspace_bytes(n, n_hidden) = max(n_hidden, 1) * ceil(n / 64) * 512 + 64; a workspace that is missing, shorter than
+ * that or not 16-byte aligned is refused with HIMO_ERR_INVALID_ARGUMENT (not HIMO_ERR_WORKSPACE), as are n_hidden outside 1 .. 12, a
+ * NULL h_H[k] / h_dZ[k] / h_db[k], a packed weight or d_x0 / d_dout / d_w_last off its 16-byte alignment; n == 0 writes nothing.
+ * dZ_k is the same bits from either backward entry point. */
 size_t himo_mlp_bias_workspace_bytes(int64_t n, int n_hidden);
 int himo_mlp_backward_fused_bias(int64_t n, const float* d_dout, int n_hidden, const void* const* h_wT_hidden_packed,
                                  const float* d_w_last, float* const* h_H, float* const* h_dZ, float* const* h_db,

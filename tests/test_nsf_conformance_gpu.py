@@ -16,8 +16,8 @@ the backward pass.
 himo_nsf_update alone: the issue's "random partials and m = 0" is read as Adam moments m = v = 0 with a NON-zero point count (a
 zero count makes every gradient exactly zero and would hide the four-run split); the zero count is one more case.
 
-Out of scope: csrc/mlpfused.hip (tests/test_fastnsf_gpu.py ties it to csrc/nsffused.hip, which anchors it transitively), and
-csrc/nsfp.hip's objective, himo_chamfer_trunc and himo_nn_grid (brute-force tests of their own).
+The layer-kernel path -- csrc/mlpfused.hip, himo_chamfer_trunc and csrc/nsfp.hip's objective and keep-best rule -- is pinned in
+tests/test_mlpfused_conformance_gpu.py (oracle/mlpfused_oracle.py); himo_nn_grid in tests/test_sslloss_conformance_gpu.py.
 """
 import ctypes
 
