@@ -86,6 +86,11 @@ SIGNATURES = {
     "himo_xsensor_workspace_bytes": (c_size_t, [c_int64, c_int]),
     "himo_xsensor": (c_int, [c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p,
                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "himo_xalign_workspace_bytes": (c_size_t, [c_int64, c_int]),
+    "himo_xalign": (c_int, [c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                            c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "himo_xalign_apply": (c_int, [c_int64, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_float, c_void_p, c_void_p]),
     "himo_boxeval_workspace_bytes": (c_size_t, [c_int, c_void_p, c_void_p]),
     "himo_boxeval_match": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_size_t, c_void_p]),

@@ -90,6 +90,7 @@ extern "C" size_t himo_abi_sizeof(const char* struct_name) {
     if (!strcmp(struct_name, "himo_rigid_params")) return sizeof(himo_rigid_params);
     if (!strcmp(struct_name, "himo_boxfit_params")) return sizeof(himo_boxfit_params);
     if (!strcmp(struct_name, "himo_xsensor_params")) return sizeof(himo_xsensor_params);
+    if (!strcmp(struct_name, "himo_xalign_params")) return sizeof(himo_xalign_params);
     if (!strcmp(struct_name, "himo_boxeval_params")) return sizeof(himo_boxeval_params);
     if (!strcmp(struct_name, "himo_boxtrack_params")) return sizeof(himo_boxtrack_params);
     if (!strcmp(struct_name, "himo_trackflow_params")) return sizeof(himo_trackflow_params);

@@ -29,17 +29,16 @@
 // Built with -ffp-contract=off: every float operation rounds on its own, as numpy does; sqrt is correctly rounded.
 #include "himo_common.h"
 #include "blockops.h"
+#include "xsensor_rows.h"
 #include <limits.h>
 #include <math.h>
 
 namespace himo {
 
-constexpr int kXsThreads = 256;
-constexpr int kXsChunk = HIMO_XSENSOR_CHUNK;
-constexpr int kXsGroups = HIMO_XSENSOR_GROUPS;
+constexpr int kXsChunk = HIMO_XSENSOR_CHUNK;         // (kXsThreads, kXsGroups and rules A and B: xsensor_rows.h)
 constexpr double kXsUnit = 16777216.0;         // 2^24: the unit of eval_flow's q()
 constexpr double kXsClip = 1024.0;             // |dt| [s] and the motion length [m] are clipped here before q()
-static_assert(kXsChunk % kXsThreads == 0 && kXsGroups == 8, "xsensor tiling");
+static_assert(kXsChunk % kXsThreads == 0, "xsensor tiling");
 
 struct XsArgs {
     int64_t n;                       // rows of the point buffer
@@ -62,52 +61,14 @@ struct XsArgs {
     long long* mot;                  // [C][2]
 };
 
-__device__ inline bool xs_finite(float v) { return fabsf(v) <= 3.402823466e+38f; }
-
-// rule B from a cluster's eight counts: the state, n and the live mask
-__device__ inline int xs_state(const int32_t* __restrict__ c, int min_group, int min_points, int max_points, int& n, int& live) {
-    const int4 a = *reinterpret_cast<const int4*>(c), b = *reinterpret_cast<const int4*>(c + 4);
-    const int g[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    n = 0; live = 0;
-    int lives = 0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        n += g[k];
-        if (g[k] >= min_group) { live |= 1 << k; ++lives; }
-    }
-    if (n < min_points) return HIMO_XSENSOR_TOO_FEW;
-    if (n > max_points) return HIMO_XSENSOR_TOO_LARGE;
-    if (lives < 2) return HIMO_XSENSOR_ONE_SENSOR;
-    return HIMO_XSENSOR_SCORED;
-}
-
-__device__ inline void xs_range(const XsArgs& p, int k, int& lo, int& hi) {       // (validated on the host; clamped all the same)
-    int64_t a = p.offsets[k], b = p.offsets[k + 1];
-    a = a < 0 ? 0 : (a > p.nc ? p.nc : a);
-    b = b < a ? a : (b > p.nc ? p.nc : b);
-    lo = (int)a; hi = (int)b;
-}
+__device__ inline void xs_range(const XsArgs& p, int k, int& lo, int& hi) { xs_range(p.offsets, p.nc, k, lo, hi); }
 
 // ---- count: rules A and B's counts ----
 __global__ __launch_bounds__(kXsThreads) void xs_count_kernel(XsArgs p) {
     const int64_t i64 = (int64_t)blockIdx.x * kXsThreads + threadIdx.x;
     if (i64 >= p.nc) return;
     const int i = (int)i64;
-    const int64_t r = p.rows[i];
-    float4 out = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (r >= 0 && r < p.n) {
-        const int lab = p.labels[r];
-        const unsigned g = p.group[r];
-        const float* row = p.pts + r * p.pitch;
-        const float x = row[0], y = row[1], z = row[2];
-        bool ok = lab >= 1 && lab <= p.C && g < (unsigned)kXsGroups && xs_finite(x) && xs_finite(y) && xs_finite(z);
-        if (ok && p.dt) ok = xs_finite(p.dt[r]);
-        if (ok) {
-            out = make_float4(x, y, z, __int_as_float(1 << g));
-            atomicAdd(&p.cnt[kXsGroups * (size_t)segment_of(p.offsets, p.C, i) + g], 1);
-        }
-    }
-    p.staged[i] = out;
+    p.staged[i] = xs_stage_row(p.n, p.pts, p.pitch, p.labels, p.group, p.dt, p.rows, p.offsets, p.C, i, p.cnt);
 }
 
 // ---- search: rule C ----
@@ -222,15 +183,6 @@ static bool xs_params_ok(const himo_xsensor_params* p) {
     if (!isfinite(p->near) || !(p->near >= 0.f)) return false;
     return p->min_group >= 1 && p->min_points >= 2 && p->max_points >= p->min_points && p->max_points <= (1 << 20);
 }
-
-static bool xs_offsets_ok(int64_t n, int C, const int64_t* h) {
-    if (h[0] != 0 || h[C] != n) return false;
-    for (int k = 0; k < C; ++k)
-        if (h[k] < 0 || h[k + 1] < h[k]) return false;
-    return true;
-}
-
-static bool xs_misaligned(const void* q, uintptr_t al) { return (reinterpret_cast<uintptr_t>(q) & (al - 1)) != 0; }
 
 // the workspace: staged float4 [nc] | m float [nc] | cnt int32 [C][8], each part rounded up to 256 bytes
 static size_t xs_part_staged(int64_t nc) { return round_up((size_t)(nc > 0 ? nc : 1) * sizeof(float4), 256); }

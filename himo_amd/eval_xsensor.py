@@ -369,6 +369,37 @@ def _ids_host(a, where: str, key: str, rows: int) -> np.ndarray:
     return a
 
 
+def cluster_ids(xyz, gm0, cluster: str = "dbscan", min_cluster_size=None, min_samples=None):
+    """``--label_key cluster``: the ids (device int64 [n], 0 = none) of a clustering of one sweep's points ``xyz`` (device float32 [n, 3]):
+    the points that are not ground (``gm0``), finite and inside the network's range, clustered as ``ssl_label.cluster_points`` does"""
+    import torch
+    from .seflow.ssl_label import EPS, HDB_MIN_CLUSTER, HDB_MIN_SAMPLES, MIN_PTS, RANGE_NET, cluster_points
+    xyz = xyz.contiguous()
+    skip = gm0.bool() | ~torch.isfinite(xyz).all(dim=1) | ~(xyz[:, :2].abs().amax(dim=1) <= RANGE_NET)
+    return cluster_points(xyz, skip, cluster, EPS, MIN_PTS, HDB_MIN_CLUSTER if min_cluster_size is None else min_cluster_size,
+                          HDB_MIN_SAMPLES if min_samples is None else min_samples)[0].to(torch.int64)
+
+
+def pack_sweeps(ds, idx, upload, dev, flows, label_key: str):
+    """The sweeps ``idx`` of ``ds`` laid end to end on ``dev`` for a per-cluster program: (frames, packed) with ``packed`` = ``offsets``
+    (host), ``pc0``, ``lidar_dt``, ``lidar_id``, every stored flow of ``flows`` and ``gm0`` (``label_key`` "cluster") or ``ids``"""
+    from .sweeps import SweepPacker
+    frames = [ds[i] for i in idx]
+    pk = SweepPacker(frames, upload=upload, device=dev)
+    packed = {"offsets": pk.offsets_host, "pc0": pk.cat("pc0", np.float32), "lidar_dt": pk.cat("lidar_dt", np.float32),
+              "lidar_id": pk.cat("lidar_id", np.uint8)}
+    if packed["pc0"].dim() != 2 or packed["pc0"].shape[1] not in (3, 4):
+        raise ValueError(f"pc0 is rows of x, y, z[, intensity], not {tuple(packed['pc0'].shape)}")
+    for s in flows:
+        packed[s] = pk.cat(s, np.float32, width=3)
+    if label_key == "cluster":
+        packed["gm0"] = pk.cat("gm0", np.uint8)
+    else:
+        ids = [_ids_host(f[label_key], f"{f['scene_id']}/{f['timestamp']}", label_key, n) for f, n in zip(frames, pk.counts)]
+        packed["ids"] = pk.upload(ids, np.int64)
+    return frames, packed
+
+
 def score_batch(scorer: XSensor, engine, frames: list, packed: dict, names: list, label_key: str, motion_key: str | None,
                 cluster: str = "dbscan", min_cluster_size=None, min_samples=None):
     """One ``himo_xsensor`` call for the sweeps of ``frames`` under every name of ``names``: the point buffer is the sweeps laid end to
@@ -391,11 +422,7 @@ def score_batch(scorer: XSensor, engine, frames: list, packed: dict, names: list
                 pts = engine.run_frame(rows, packed[name][lo:hi], packed["lidar_dt"][lo:hi], f["pose0"], f["pose1"], refined=True)[1]
             parts.append(pts)
             if label_key == "cluster":
-                from .seflow.ssl_label import EPS, HDB_MIN_CLUSTER, HDB_MIN_SAMPLES, MIN_PTS, RANGE_NET, cluster_points
-                xyz = pts.contiguous()
-                skip = packed["gm0"][lo:hi].bool() | ~torch.isfinite(xyz).all(dim=1) | ~(xyz[:, :2].abs().amax(dim=1) <= RANGE_NET)
-                ids = cluster_points(xyz, skip, cluster, EPS, MIN_PTS, HDB_MIN_CLUSTER if min_cluster_size is None else min_cluster_size,
-                                     HDB_MIN_SAMPLES if min_samples is None else min_samples)[0].to(torch.int64)
+                ids = cluster_ids(pts, packed["gm0"][lo:hi], cluster, min_cluster_size, min_samples)
             else:
                 ids = packed["ids"][lo:hi]
             keys.append(torch.where(ids != 0, ids + ((r * S + s + 1) << _ID_BITS), torch.zeros_like(ids)))
@@ -420,7 +447,7 @@ def main(data_dir: str, res_names, label_key: str, motion_key: str | None = None
     from . import distenv, stored
     from .dataset import open_dataset
     from .seflow.ssl_label import CLUSTERINGS
-    from .sweeps import MissingKey, SweepPacker, fed, raise_missing, sharded_batches
+    from .sweeps import MissingKey, fed, raise_missing, sharded_batches
     names = stored.result_names(res_names, raw_ok=True)
     if not label_key:
         raise ValueError("label_key: a stored integer key (ray_label, flow_instance_id, ...) or 'cluster'")
@@ -468,20 +495,7 @@ def main(data_dir: str, res_names, label_key: str, motion_key: str | None = None
             dev = scorer.device
 
             def build(idx, upload):
-                frames = [ds[i] for i in idx]
-                pk = SweepPacker(frames, upload=upload, device=dev)
-                packed = {"offsets": pk.offsets_host, "pc0": pk.cat("pc0", np.float32), "lidar_dt": pk.cat("lidar_dt", np.float32),
-                          "lidar_id": pk.cat("lidar_id", np.uint8)}
-                if packed["pc0"].dim() != 2 or packed["pc0"].shape[1] not in (3, 4):
-                    raise ValueError(f"pc0 is rows of x, y, z[, intensity], not {tuple(packed['pc0'].shape)}")
-                for s in flows:
-                    packed[s] = pk.cat(s, np.float32, width=3)
-                if label_key == "cluster":
-                    packed["gm0"] = pk.cat("gm0", np.uint8)
-                else:
-                    ids = [_ids_host(f[label_key], f"{f['scene_id']}/{f['timestamp']}", label_key, n) for f, n in zip(frames, pk.counts)]
-                    packed["ids"] = pk.upload(ids, np.int64)
-                return frames, packed
+                return pack_sweeps(ds, idx, upload, dev, flows, label_key)
 
             for frames, packed in fed(iter(mine), build, device=dev, overlap=overlap):
                 res, which, keys = score_batch(scorer, engine, frames, packed, names, label_key, motion_key, cluster, min_cluster_size,

@@ -833,6 +833,93 @@ int himo_xsensor(int64_t n, const float* d_pts, int pitch, const int32_t* d_labe
                  float* d_min_d2, void* d_workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Cross-sensor alignment (`python -m himo_amd.xalign`, an ordinary flow key `xalign`): the planar velocity of every cluster from the
+ * capture times inside ONE sweep -- the sensors record a moving object at different instants, r_i = P + v tau_i, so the v that lays
+ * their copies on top of one another is the object's; no second sweep, no network, no training (himo_amd/csrc/xalign.hip).  The
+ * reference names this route ("dynamic segmentation + ICP alignment across LiDARs") and ships no program for it: this one follows the
+ * build's own written rule, "cross-sensor alignment, v1" (the module docstring of himo_amd/xalign.py is normative): PARITY UNPINNED.
+ * Timed on synthetic sweeps only (profiles/xalign.txt); nothing has been tried on field data.
+ *
+ *   Inputs as for himo_xsensor; d_tau float[n], the capture time, is REQUIRED.  The labelled rows SORTED BY LABEL, the clusters of
+ *   several sweeps laid end to end in one call.
+ *   usable    rules A and B of cross-sensor consistency v1, word for word (one header states them for both files): the usable rows,
+ *   state     the live groups, and TOO_FEW, TOO_LARGE, ONE_SENSOR in that order; then NO_BASELINE iff max t_g - min t_g < tau_min over
+ *             the live groups, t_g = (sum of q24(tau clipped to +-1024 s)) / (2^24 n_g) in float64.  The ROWS below are the usable rows
+ *             of live groups.  A cluster that ends in one of these states writes its state, n (and for NO_BASELINE the live mask and
+ *             the rows), v = 0 and zeros elsewhere.  A cluster that ends as NO_BASELINE later -- no vote, or A == 0 -- writes v = 0
+ *             and zero sums too, but keeps in d_info what it had counted by then: the votes and the winning bin, and after A == 0
+ *             the iterations used and the pairs of the last one
+ *   vote      every pair of rows (i, j) of live groups with group(i) < group(j), |tau_i - tau_j| >= tau_min and |z_i - z_j| < z_gate
+ *             (float32) votes for (dx / dtau, dy / dtau) in float64; bin = floor(v / bin + nb / 2) per axis, nb = 2 ceil(v_max / bin)
+ *             + 1; a vote outside the table is dropped; a bin's score is the sum of the counts of its 3 x 3 neighbourhood clipped at
+ *             the edge; v_0 is the centre of the bin with the greatest score, ties to the smallest flat index bx nb + by; no vote:
+ *             NO_BASELINE
+ *   iterate   k = 0 .. iters - 1: moved rows x = r_x - (float)v_x tau, y likewise, z as recorded (float32, every operation rounding on
+ *             its own); per row the nearest moved row of another live group by d2 = (dx*dx + dy*dy) + dz*dz, as the minimum of the
+ *             64-bit key (bits of d2 << 32 | sorted row) -- ties to the smallest sorted row, a NaN orders as 0x7fc00000, after +inf;
+ *             float64: d = sqrt(d2), the pair is kept iff d <= trunc, w = (sigma^2 / (sigma^2 + d^2))^2, dtau = tau_i - tau_j, dp = r_i
+ *             - r_j on the RECORDED rows; A = sum q40((w dtau) dtau), b = sum q40((w dtau) dp_{x,y}), every term clipped to +-256 before
+ *             q40(x) = llrint(x 2^40), int64 sums: no order is part of the rule; A == 0: NO_BASELINE; v_{k+1} = b / A; the loop ends
+ *             after the step in which |v_{k+1} - v_k| < tol
+ *   score     X(v) = sum over the rows of q24(min(d, trunc)) (a NaN counts as trunc) at v = 0 (X0) and at the final v (X1)
+ *   decide    REJECTED iff |v| > v_max or (double)X1 > (1 - min_gain) (double)X0; else STATIC iff |v| < static_speed; else ALIGNED.
+ *             Only ALIGNED clusters carry a non-zero v
+ * Outputs, written whole (they need no clearing): d_info int32[C][8] = state, n, live-group bit mask, rows, votes cast, the winning
+ * flat bin, iterations used, pairs kept in the last iteration; d_v float[C][4] = v_x, v_y, 0, |v|; d_x int64[C][2] = X0, X1.
+ * himo_xalign_apply (rule G) over one point buffer of n_sweeps sweeps laid end to end (sweep s owns the rows pt_off[s] .. pt_off[s + 1];
+ * d_E float[n_sweeps][12], the first three rows of inv(pose1) @ pose0): a row whose label is in 1..n_clusters, whose x, y, z are finite
+ * and whose cluster is ALIGNED gets (E p - p) + v * sensor_dt -- E p by the arithmetic of himo_rigid_transform, as in
+ * himo_trackflow_apply's replace mode; every other row keeps the bytes of d_base, or, with d_base NULL ("raw"), gets E p - p.
+ * Refused with HIMO_ERR_INVALID_ARGUMENT, nothing launched and nothing written: what himo_xsensor refuses, d_tau NULL where rows are
+ * clustered, and parameters outside: min_group >= 1, min_points >= 2, min_points <= max_points <= HIMO_XALIGN_MAX_POINTS; v_max, bin
+ * finite and > 0, v_max <= 1024 and nb * nb <= HIMO_XALIGN_TABLE_CELLS (the vote table lives in LDS); tau_min, sigma, trunc finite, > 0
+ * and <= 1024; z_gate finite and > 0; iters 1..HIMO_XALIGN_MAX_ITERS with iters * max_points^2 <= HIMO_XALIGN_MAX_WORK (2^32: one
+ * workgroup walks a cluster, so the work of one is bounded); tol, static_speed finite and >= 0; min_gain finite in [0, 1).  n > 2^31 - 1:
+ * HIMO_ERR_UNSUPPORTED.  A short, NULL or misaligned (16 bytes) workspace: HIMO_ERR_WORKSPACE (himo_xalign_workspace_bytes returns 0 for
+ * what it refuses).  n_clusters == 0: HIMO_OK, nothing launched.  himo_xalign_apply refuses a negative count, pitch < 3, sensor_dt not
+ * finite and > 0, rows without sweeps, offsets that do not start at 0, decrease or do not end at n, NULL or misaligned where data is
+ * required; n == 0: HIMO_OK.
+ * himo_xalign: one clear and two launches (count; one workgroup per cluster for everything else), asynchronous on `stream`, no host
+ * wait; no float atomics; the same inputs give the same bytes. */
+typedef struct himo_xalign_params {
+    int32_t min_group;     /* fewer usable rows of a sensor in a cluster: that sensor is not live there */
+    int32_t min_points;    /* fewer usable rows: TOO_FEW */
+    int32_t max_points;    /* more usable rows: TOO_LARGE */
+    int32_t iters;         /* the most iterations */
+    float v_max;           /* the vote covers |v_x|, |v_y| <= v_max, and a faster result is REJECTED, m/s */
+    float bin;             /* m/s per vote bin */
+    float tau_min;         /* the smallest difference of capture times of a voting pair, and of the live groups' mean times, s */
+    float z_gate;          /* a voting pair lies closer than this in z, metres */
+    float sigma;           /* the scale of the weight, metres */
+    float trunc;           /* a pair farther apart is dropped, and a row's score term is clipped here, metres */
+    float tol;             /* the loop ends when v changes by less, m/s */
+    float min_gain;        /* REJECTED unless X1 <= (1 - min_gain) X0 */
+    float static_speed;    /* slower: STATIC, m/s */
+} himo_xalign_params;
+
+#define HIMO_XALIGN_ALIGNED 0
+#define HIMO_XALIGN_TOO_FEW 1      /* = HIMO_XSENSOR_TOO_FEW */
+#define HIMO_XALIGN_ONE_SENSOR 2   /* = HIMO_XSENSOR_ONE_SENSOR */
+#define HIMO_XALIGN_TOO_LARGE 3    /* = HIMO_XSENSOR_TOO_LARGE */
+#define HIMO_XALIGN_NO_BASELINE 4
+#define HIMO_XALIGN_REJECTED 5
+#define HIMO_XALIGN_STATIC 6
+#define HIMO_XALIGN_CHUNK 1024           /* moved rows a nearest-neighbour pass stages in LDS at a time (a size its tests straddle) */
+#define HIMO_XALIGN_TABLE_CELLS 15360    /* int32 cells of the LDS buffer the vote table must fit: nb <= 123 */
+#define HIMO_XALIGN_MAX_POINTS 16384
+#define HIMO_XALIGN_MAX_ITERS 100
+#define HIMO_XALIGN_MAX_WORK 4294967296LL   /* iters * max_points^2 at the most: what ONE workgroup may be asked to walk */
+
+size_t himo_xalign_workspace_bytes(int64_t n_clustered, int n_clusters);
+int himo_xalign(int64_t n, const float* d_pts, int pitch, const int32_t* d_labels, const uint8_t* d_group, const float* d_tau,
+                int64_t n_clustered, const int64_t* d_rows, int n_clusters, const int64_t* h_offsets, const int64_t* d_offsets,
+                const himo_xalign_params* params, int32_t* d_info, float* d_v, int64_t* d_x, void* d_workspace, size_t workspace_bytes,
+                void* stream);
+int himo_xalign_apply(int64_t n, const float* d_pts, int pitch, const int32_t* d_labels, int n_clusters, const int32_t* d_info,
+                      const float* d_v, int n_sweeps, const int64_t* h_pt_off, const int64_t* d_pt_off, const float* d_E,
+                      const float* d_base, float sensor_dt, float* d_out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Box evaluation (`python -m himo_amd.eval_box`): the rotated BEV IoU and the 3-D IoU of oriented boxes, and the greedy matching of
  * two sets of boxes per sweep by descending BEV IoU (himo_amd/csrc/boxeval.hip).  The reference has no such stage: this one follows
  * the build's own written rule, "box evaluation, v1" (the module docstring of himo_amd/eval_box.py is normative): PARITY UNPINNED.
