@@ -77,6 +77,9 @@ SIGNATURES = {
     "himo_odom_step": (c_int, [c_int64, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                c_void_p]),
     "himo_odom_register": (c_int, [c_int64, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "himo_deskew_tref": (c_int, [c_int, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "himo_deskew_rows": (c_int, [c_int, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                 c_int, c_void_p, c_void_p, c_void_p]),
     "himo_rigid_refine_workspace_bytes": (c_size_t, [c_int64, c_int, c_int, c_int]),
     "himo_rigid_refine": (c_int, [c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

@@ -66,7 +66,7 @@ Parameters (``OdomParams``; this build's own choices): ``voxel`` 0.5 m, ``window
    event, as ``icpflow`` reads its counts: the next map is built with the new pose.  (Each of the two accumulations of a sweep waits
    once as well, for its row count, as ``Accumulator.result`` always does.)
 
-Not part of v1: de-skewing by ``lidar_dt``, point-to-plane or normals, an adaptive threshold, a map that persists beyond the window,
+Not part of v1: de-skewing by ``lidar_dt`` (a program of its own: ``python -m himo_amd.deskew --pose_key pose_odom``), point-to-plane or normals, an adaptive threshold, a map that persists beyond the window,
 loop closure, several scenes in flight, IMU or wheel input, any use of ``SensorsCenter``.
 
 The program: ``python -m himo_amd.odometry --data_dir D [--out_key pose_odom] [--window 10] [--voxel 0.5] [--skip_label KEY]

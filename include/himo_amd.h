@@ -680,6 +680,38 @@ int himo_odom_register(int64_t n, const float* d_src, int pitch, int64_t n_map, 
                        himo_odom_state* d_state, void* d_workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Ego-motion de-skew (`python -m himo_amd.deskew`): every row of a sweep is moved along the sweep's constant body twist from its own
+ * capture time to the sweep's reference time.  The reference has no such stage: this one follows the build's own written rule, "ego
+ * de-skew, v1" (the module docstring of himo_amd/deskew.py is normative): PARITY UNPINNED.
+ *
+ * A ragged batch of n_sweeps sweeps in one call: the rows laid end to end, d_pts float[n][in_pitch] and d_lidar_dt float[n]; offsets
+ * int64[n_sweeps + 1] on the HOST (validated) and on the device (sweep b owns rows offsets[b] .. offsets[b + 1]); twists
+ * double[n_sweeps][8] on the HOST (validated) and on the device: v, w (per `span`, in the sweep's own frame), span [s], one spare.
+ *   himo_deskew_tref   d_tref float[n_sweeps]: per sweep the greatest (HIMO_DESKEW_REF_MAX) or least (.._MIN) finite lidar_dt, or 0
+ *                      (.._ZERO, and a sweep without a finite lidar_dt).
+ *   himo_deskew_rows   p' = Exp(-s xi) p (inverse = 1: Exp(+s xi) p) with s = (t_ref - lidar_dt) / span, in float64, rounded once
+ *                      to float32, into d_out float[n][out_pitch].  A row with s == 0, with a non-finite coordinate or lidar_dt, or
+ *                      of a sweep whose twist is all zeros passes through with its bytes.  Column 3 is copied (0 when the input has
+ *                      none).  d_out == d_pts is the in-place run (equal pitches only).  d_counts int32[n_sweeps][2]: rows moved,
+ *                      rows passed through; d_max_disp float[n_sweeps]: the greatest |p' - p| of the moved rows (float64, rounded
+ *                      once; an integer atomic max on the bits of a non-negative float).
+ * n_sweeps == 0 and sweeps without rows are defined outcomes, not errors.  Refuse (HIMO_ERR_INVALID_ARGUMENT, nothing launched,
+ * nothing written): a pitch other than 3 or 4, a negative count, offsets that do not start at 0, decrease or do not end at n, NULL or
+ * misaligned (4 bytes; offsets and twists 8) where data is required, a twist or span that is not finite, a span not > 0, an unknown
+ * mode or `inverse`, d_pts and d_out that overlap other than as one buffer of one pitch.  n above 2^31 - 1: HIMO_ERR_UNSUPPORTED.
+ * Both calls are asynchronous on `stream`, allocate nothing and wait for nothing; no floating-point atomics: the same inputs give the
+ * same bytes on every run. */
+#define HIMO_DESKEW_REF_MAX 0
+#define HIMO_DESKEW_REF_MIN 1
+#define HIMO_DESKEW_REF_ZERO 2
+
+int himo_deskew_tref(int n_sweeps, int64_t n, const int64_t* h_offsets, const int64_t* d_offsets, const float* d_lidar_dt, int mode,
+                     float* d_tref, void* stream);
+int himo_deskew_rows(int n_sweeps, int64_t n, const int64_t* h_offsets, const int64_t* d_offsets, const float* d_pts, int in_pitch,
+                     const float* d_lidar_dt, const double* h_twists, const double* d_twists, const float* d_tref, int inverse,
+                     float* d_out, int out_pitch, int32_t* d_counts, float* d_max_disp, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Cluster-rigid flow refinement (`python -m himo_amd.rigid_refine`, result key `<res_name>_rigid`): a stored flow is projected
  * onto at most `models` rigid motions (yaw + 3-D translation) per cluster of the non-ground points of pc0; a motion that moves no
  * claimed point by static_disp becomes the identity, i.e. the ego-motion flow.  The reference has no such stage: this one follows
