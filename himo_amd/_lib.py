@@ -122,6 +122,12 @@ SIGNATURES = {
     "himo_raymap_carve": (c_int, [c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "himo_raymap_query": (c_int, [c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "himo_raymap_status": (c_int, [c_void_p]),
+    "himo_drivemap_bytes": (c_size_t, [c_void_p]),
+    "himo_drivemap_carve": (c_int, [c_int64, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "himo_drivemap_query": (c_int, [c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "himo_drivemap_emit_workspace_bytes": (c_size_t, [c_void_p]),
+    "himo_drivemap_emit": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "himo_drivemap_status": (c_int, [c_void_p]),
     "himo_accum_table_bytes": (c_size_t, [c_int64]),
     "himo_accum_clear": (c_int, [c_void_p, c_int64, c_void_p]),
     "himo_accum_insert": (c_int, [c_int64, c_void_p, c_int, c_void_p, ctypes.POINTER(c_float), c_int, c_void_p, c_void_p, c_int64, c_void_p]),

@@ -95,6 +95,7 @@ extern "C" size_t himo_abi_sizeof(const char* struct_name) {
     if (!strcmp(struct_name, "himo_boxtrack_params")) return sizeof(himo_boxtrack_params);
     if (!strcmp(struct_name, "himo_trackflow_params")) return sizeof(himo_trackflow_params);
     if (!strcmp(struct_name, "himo_raymap_params")) return sizeof(himo_raymap_params);
+    if (!strcmp(struct_name, "himo_drivemap_params")) return sizeof(himo_drivemap_params);
     if (!strcmp(struct_name, "himo_accum_params")) return sizeof(himo_accum_params);
     if (!strcmp(struct_name, "himo_camera")) return sizeof(himo_camera);
     if (!strcmp(struct_name, "himo_shade")) return sizeof(himo_shade);

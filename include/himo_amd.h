@@ -407,6 +407,60 @@ int himo_raymap_query(int64_t n, const float* d_pts, int pitch, const unsigned c
 int himo_raymap_status(void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Whole-drive free-space map: one map carved from EVERY sweep of a scene, each walked once, that labels points and names the voxels
+ * that are reliably static (himo_amd/csrc/drivemap.hip).  The reference has no such stage: this one follows the build's own written
+ * rule, "free-space drive map, v1" (the module docstring of himo_amd/drivemap.py is normative): PARITY UNPINNED.
+ *   quantise, rays, walk   rules A-C of "free-space ray map, v1" above, unchanged; the origin of ray i is d_origins[d_src[i]]
+ *   carve     sweep s marks a voxel FREE if one of its rays visits it in the grid at Chebyshev index distance > guard from that ray's
+ *             end voxel, and HIT if one of its rays ends in it.  hit_n counts the sweeps that marked the voxel HIT, free_n those that
+ *             marked it FREE and not HIT.  One uint64 per voxel, [nz][ny][nx], cleared by the caller:
+ *             stamp (s + 1) in bits 63..48 | HIT bit 33 | FREE bit 32 | free_n in bits 31..16 | hit_n in bits 15..0,
+ *             the state bits being what the sweep of the stamp did (HIT replaces FREE).  The word after a sweep depends on the set of
+ *             that sweep's marks only: not on ray order, on how its rays are split over calls, or on carving rays twice.
+ *             PRECONDITION: the sweep numbers of the calls on one map do not decrease (a sweep that comes back after another has
+ *             stamped a voxel is counted again there); 0 <= sweep <= 65534.
+ *   query     fv = free_n, hv = hit_n of a point's voxel, both 0 for a skipped, unusable or out-of-grid point; the point is DYNAMIC
+ *             iff it is not skipped, fv >= min_votes and fv > hv
+ *   emit      a voxel is STATIC iff hit_n >= min_hits and not (free_n >= min_votes and free_n > hit_n).  One row per STATIC voxel in
+ *             ascending linear index (vz*ny + vy)*nx + vx: float[4] = {x, y, z, 0} with x = ((float)vx + 0.5f) * voxel + x0 (every
+ *             operation rounding on its own), beside it hit_n and free_n as int32.  Count, scan, write: no atomic orders the rows.
+ *             *d_count receives the number of STATIC voxels whatever `capacity` is; rows at and beyond `capacity` are not written
+ *             (capacity 0: the count alone, the row pointers may be NULL).
+ * d_pts: float[n][pitch], pitch 3 or 4, in the map's frame; d_src: one byte per ray, 0..15 = the row of d_origins (float[16][3]) the
+ * ray starts from, 255 = the ray takes no part; d_skip: uint8[n] or NULL; d_free_n / d_hit_n: uint16[n], d_dynamic: uint8[n], each
+ * may be NULL.  The workspace of emit: himo_drivemap_emit_workspace_bytes(params) bytes, 4-byte aligned.
+ * Refused with HIMO_ERR_INVALID_ARGUMENT, nothing launched and nothing written: n < 0, a pitch other than 3 or 4, a sweep outside
+ * 0..65534, a capacity < 0, NULL where data is required, d_pts / d_origins / row outputs / the workspace not 4-byte aligned, the map
+ * or d_count not 8-byte aligned, d_free_n / d_hit_n not 2-byte aligned, and parameters outside: every float finite, voxel > 0, scale ==
+ * (float)(256.0 / voxel), 1 <= nx, ny <= 16384, 1 <= nz <= 256, nx*ny*nz <= 2^29, 0 <= guard <= 8, 1 <= min_votes <= 65535,
+ * 1 <= min_hits <= 65535 (himo_drivemap_bytes and himo_drivemap_emit_workspace_bytes return 0 for them).  A workspace that is too
+ * small: HIMO_ERR_WORKSPACE.  n > 2^31 - 1: HIMO_ERR_UNSUPPORTED.  n == 0: HIMO_OK without a launch.
+ * A src byte in 16..254 makes the WHOLE carve call a refused one, found on the device exactly as himo_raymap_carve finds a slot byte:
+ * the call marks nothing, himo_drivemap_carve itself still returns HIMO_OK, and himo_drivemap_status(stream) waits for `stream`,
+ * returns HIMO_ERR_INVALID_ARGUMENT when a carve call on the current device was refused in this way since the last
+ * himo_drivemap_status, and clears the flag.  Every call is asynchronous on `stream` but that one; only 32- and 64-bit integer atomics
+ * touch the map, and the map after equal calls is the same bytes on every run. */
+typedef struct himo_drivemap_params {
+    float x0, y0, z0;      /* grid minimum */
+    float voxel;           /* voxel edge, m */
+    float scale;           /* (float)(256.0 / voxel), the division in double */
+    int32_t nx, ny, nz;
+    int32_t guard;         /* voxels in front of a return (Chebyshev) that its ray does not carve */
+    int32_t min_votes;     /* sweeps that must have seen through a voxel and not returned from it */
+    int32_t min_hits;      /* sweeps that must have returned from a voxel of the static map */
+} himo_drivemap_params;
+
+size_t himo_drivemap_bytes(const himo_drivemap_params* params);          /* 8*nx*ny*nz; 0 = parameters refused */
+int himo_drivemap_carve(int64_t n_rays, const float* d_pts, int pitch, const unsigned char* d_src, const float* d_origins, int sweep,
+                        const himo_drivemap_params* params, uint64_t* d_map, void* stream);
+int himo_drivemap_query(int64_t n, const float* d_pts, int pitch, const unsigned char* d_skip, const himo_drivemap_params* params,
+                        const uint64_t* d_map, uint16_t* d_free_n, uint16_t* d_hit_n, unsigned char* d_dynamic, void* stream);
+size_t himo_drivemap_emit_workspace_bytes(const himo_drivemap_params* params);
+int himo_drivemap_emit(const himo_drivemap_params* params, const uint64_t* d_map, int64_t capacity, float* d_rows4, int32_t* d_hits,
+                       int32_t* d_free_n, int64_t* d_count, void* d_workspace, size_t workspace_bytes, void* stream);
+int himo_drivemap_status(void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Multi-sweep accumulation: several compensated sweeps moved into one target frame and reduced to one centroid per occupied voxel,
  * each with the least time lag of its rows (himo_amd/csrc/accumulate.hip).  The reference has no such program in its tree, so this
  * stage follows the build's own written rule, "sweep accumulation, v1" (the module docstring of himo_amd/accumulate.py is
